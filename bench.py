@@ -25,7 +25,9 @@ KD-tree.  Every 20 steps a new Fit starts (state reset), as in the reference's M
           `value_same_mode_n1` is what ONE of these GPUs does in the same mode without the exchange:
           the base of a scaling curve in one numeric mode.
 
-The timed loop runs with profiling off; the kernel times of `roofline` come from a second, untimed pass.
+The timed loop runs exactly --steps steps with profiling off; the kernel times of `roofline` come from a second,
+untimed pass.  --dump-outputs DIR writes what the last timed step computed (the Fit's pose and Stat) as
+DIR/<name>.npy; the inputs are seeded, so two builds run with the same arguments can be compared output for output.
 Launched as `python bench.py --gpus N` this script starts the N ranks itself
 (torch.distributed.run as a child process, before anything touches the GPU); launched under
 torch.distributed.run it is one of those ranks.  Prints ONE JSON line on rank 0.
@@ -337,6 +339,22 @@ def side_benchmarks(torch, L, kdtree, voxelgrid, synth, tree, stream, visits, ic
     return out
 
 
+def dump_outputs(out_dir, trans, stat, converged):
+    """--dump-outputs: what a caller of the timed path receives after its last step -- the pose and the Stat of
+    pcgx_icp_session_result -- one float32 / float64 array per field (counts as float64, exact)."""
+    os.makedirs(out_dir, exist_ok=True)
+    ev = stat.Evaluated
+    arrays = {"trans": np.asarray(trans, np.float32),
+              "evaluated_value": np.array([ev.Value], np.float32),
+              "evaluated_gradient": np.asarray(ev.Gradient, np.float32),
+              "evaluated_dist_rms": np.array([ev.DistRMS], np.float32),
+              "evaluated_num_pairs": np.array([ev.NumPairs], np.float64),
+              "num_iteration": np.array([stat.NumIteration], np.float64),
+              "converged": np.array([float(converged)], np.float64)}
+    for name, a in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+
+
 def launch_ranks(args):
     """`python bench.py --gpus N` outside torch.distributed.run: start the N ranks as a child (the
     parent never touches the GPU), pass its output through."""
@@ -362,7 +380,10 @@ def main():
     ap.add_argument("--no-extras", action="store_true")
     ap.add_argument("--f64-tree", action="store_true", help="N = 1: time the float64-tree reduction instead of the reference's sums")
     ap.add_argument("--no-reference-sharded", action="store_true", help="N > 1: skip the second timing (the float64-tree step beside the headline)")
+    ap.add_argument("--dump-outputs", metavar="DIR", help="after the timed steps, write what the last one computed as DIR/<name>.npy")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         sys.exit(launch_ranks(args))
@@ -541,31 +562,26 @@ def main():
                 step()
             barrier()
     L.prof_enable(0)   # nothing but the step's own launches inside the timed region
-    # the driver's K may cover less than a millisecond of GPU work: repeat the K steps until >= 50 ms
-    # have been timed and report per step (the JSON's `steps` stays the driver's K)
-    rounds = 0
-    elapsed = 0.0
-    round_ms = []   # per step, of every timed round of K steps: the line's spread
+    # exactly --steps timed steps, clocked as one stretch: the state they leave is the same from run to run, and it is
+    # what --dump-outputs writes
     barrier()
-    while True:
-        t0 = time.perf_counter()
-        for _ in range(args.steps):
-            step()
-        L.check(L.lib().pcgx_sync(L.ptr(stream)))
-        torch.cuda.synchronize()
-        dt = time.perf_counter() - t0
-        if world > 1:
-            t = torch.tensor([dt], dtype=torch.float64)
-            dist.all_reduce(t, op=dist.ReduceOp.MAX)
-            dt = float(t.item())
-        elapsed += dt
-        rounds += 1
-        round_ms.append(dt / args.steps * 1e3)
-        barrier()
-        if elapsed >= 0.05 or rounds >= 200:
-            break
-    per_step = elapsed / (rounds * args.steps)
-    trans, stat, _ = sess.result(stream)
+    t0 = time.perf_counter()
+    for _ in range(args.steps):
+        step()
+    L.check(L.lib().pcgx_sync(L.ptr(stream)))
+    torch.cuda.synchronize()
+    elapsed = time.perf_counter() - t0
+    if world > 1:
+        t = torch.tensor([elapsed], dtype=torch.float64)
+        dist.all_reduce(t, op=dist.ReduceOp.MAX)
+        elapsed = float(t.item())
+    rounds = 1
+    round_ms = [elapsed / args.steps * 1e3]   # (the line's spread fields: one timed stretch)
+    barrier()
+    per_step = elapsed / args.steps
+    trans, stat, converged = sess.result(stream)
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, trans, stat, converged)
     # ---- kernel times: a pass of its own (HIP events around every launch cost stream time), two Fits
     kinds = {"icp_grid_kernel": L.PROF_ICP_GRID, "icp_corr_kernel": L.PROF_ICP_WALK,
              "icp_corr_kernel (behind the grid pass)": L.PROF_ICP_LEFTOVER,
