@@ -254,7 +254,9 @@ __global__ __launch_bounds__(kIcpBlock) void icp_corr_kernel(
   auto emit = [&](int64_t i, const float4 &bp, float best_d) {
     const float4 rec = make_float4(bp.x, bp.y, bp.z, __float_as_int(bp.w) >= 0 ? best_d : -1.0f);
     match[i] = rec;
-    if (match_caller) match_caller[orig_of[i]] = rec;  // strict sums: see icp_grid_kernel
+    if (match_caller)  // strict sums: see icp_grid_kernel (w: the partner's certificate)
+      match_caller[orig_of[i]] = make_float4(rec.x, rec.y, rec.z,
+                                             rec.w >= 0.0f ? (cert_by_id ? cert_by_id[__float_as_uint(bp.w)] : 0.0f) : -1.0f);
     if (kPlane) match_id[i] = __float_as_uint(bp.w);
     // (the walked partner's certificate, for the next iteration's grid pass: icp_grid_kernel)
     if (match_cert) match_cert[i] = (cert_by_id && __float_as_int(bp.w) >= 0) ? cert_by_id[__float_as_uint(bp.w)] : 0.0f;
@@ -406,9 +408,10 @@ __global__ __launch_bounds__(kIcpGridBlock) void icp_grid_kernel(
       // strict sums: the float64 tile sums (guesses only) are formed by icp_corr_kernel's workgroups while others
       // of them still walk; until the walk's answer arrives the target stands with the best point the grid has
       // seen -- usually the answer -- instead of last iteration's pair (none at all in a Fit's first iteration)
+      // (w: a pair without a certificate, until the walk writes it with its certificate)
       if (!kSums && match_caller) {
         const bool seen = __float_as_int(best.w) >= 0;
-        match_caller[orig_of[i]] = make_float4(best.x, best.y, best.z, seen ? best_d : -1.0f);
+        match_caller[orig_of[i]] = make_float4(best.x, best.y, best.z, seen ? 0.0f : -1.0f);
       }
     } else {
       const bool found = __float_as_int(best.w) >= 0;
@@ -418,7 +421,13 @@ __global__ __launch_bounds__(kIcpGridBlock) void icp_grid_kernel(
       else match[i] = bp;
       // strict sums add the pairs' terms in the CALLER's target order: the pair goes there as well (a
       // 16-byte scatter here, +6 us at C4, instead of a gather through pos_of in the terms kernel, 10 us)
-      if (!kSums && match_caller && !(kept && caller_has_pairs)) match_caller[orig_of[i]] = bp;  // (a kept pair is there, and its reader forms the distance from the points: strict_terms.h, pair_terms)
+      // (in the caller's order w is the partner's CERTIFICATE -- 0: none, -1: no pair -- what a certified summary
+      // kernel tests the next pair against: strict.hip, CertifiedTerms; the terms' reader forms the distance from the
+      // points, strict_terms.h, pair_terms, and looks at w >= 0 only)
+      if (!kSums && match_caller && !(kept && caller_has_pairs)) {
+        const float c = kept ? pm_cert : ((use_cert && v == GRID_FOUND && found) ? grid.cert[__float_as_uint(best.w)] : 0.0f);
+        match_caller[orig_of[i]] = make_float4(bp.x, bp.y, bp.z, found ? c : -1.0f);  // (a kept pair is there already)
+      }
       if (kPlane && !kept) match_id[i] = __float_as_uint(best.w);
       if (found && kSums) {  // correspondence.go:27-29
         if (kPlane) accumulate_plane_terms(acc, x, y, z, bp, normals[kept ? match_id[i] : __float_as_uint(best.w)]);
@@ -654,6 +663,7 @@ struct pcgx_icp_session {
                              // `iter`, which set_pose may start anywhere
   bool spec_walk = true;     // the leftover walk is not launched behind a grid pass from a Fit's second Evaluate on (enqueue_corr)
   bool spec_pending = false; // ... and steps enqueued that way have not been looked at yet (settle())
+  bool certify_next = false; // enqueue_corr left the step's correspondence to the summary kernel (CertifiedTerms): enqueue_strict
   hipStream_t spec_stream = nullptr;  // ... on this stream (entry points without a stream argument settle there)
   hipStream_t used[4] = {nullptr, nullptr, nullptr, nullptr};  // the streams work on this session's buffers was enqueued on
   int n_used = 0;                                               // (5: more than four -- pcgx_icp_session_free waits for the device)
@@ -738,6 +748,7 @@ static pcgx_status reset_state(pcgx_icp_session *s, hipStream_t st) {
   if (s->spec_pending) {  // (steps enqueued without the leftover walk and never looked at: whatever they left in the lists)
     s->spec_pending = false;
     if (s->d_walk_count) PCGX_HIP_TRY(hipMemsetAsync(s->d_walk_count, 0, (size_t)s->grid * sizeof(uint32_t), st));
+    PCGX_TRY(strict_reset(s->strict_buf, st));  // (and a certified summary launch that met `done` 2 midway: its slot counters)
   }
   if (s->shard_failed || s->steps_sharded > 0) {  // (a sharded Fit may have ended inside a launch: its counters)
     PCGX_TRY(strict_reset(s->strict_buf, st));
@@ -1071,6 +1082,7 @@ static pcgx_status enqueue_corr(pcgx_icp_session *s, hipStream_t st, bool may_sp
   // a deletion made after the session was created: from now on the reference's patched tree is walked
   // (the same handle's Nearest / Range already do), without hints from earlier iterations
   if (!s->patched && s->base->n_deleted > 0) s->patched = true;
+  s->certify_next = false;
   PCGX_TRY(general_prepare(s, st));
   const bool caller_had_pairs = s->caller_order_fresh;  // the pass before this one left every pair in the caller's order too
   s->caller_order_fresh = false;
@@ -1127,6 +1139,15 @@ static pcgx_status enqueue_corr(pcgx_icp_session *s, hipStream_t st, bool may_sp
     s->spec_pending = true;
     s->spec_stream = st;
   }
+  // From a Fit's K-th Evaluate on (PCGX_ICP_FUSED_FROM, 0: never) not even the grid pass runs: 98.5 % of the targets
+  // keep their partner from the third iteration on, and the summary kernel reads every target and its partner anyway --
+  // it tests the certificates and searches the rest itself (strict.hip, strict_sum_kernel<., ., true>).  The same
+  // speculation as no_walk: a target the grid cannot answer ends the step with `done` 2, settle() enqueues it again.
+  // (K = 2: 0.0673 ms a C4 step against 0.0680 with K = 3, where iteration 2 still runs the grid pass: DESIGN 3.1)
+  static const int fused_from = icp_knob("PCGX_ICP_FUSED_FROM", 2, 0, 1 << 30);
+  s->certify_next = no_walk && fused_from > 0 && s->host_iter >= fused_from && cert != nullptr && caller_had_pairs &&
+                    s->caller_order_fresh && strict_work(s->strict_buf, s->kp)->exchange;
+  if (s->certify_next) return PCGX_OK;  // (nothing in front of the summary kernel)
   if (grid) {
     ProfScope prof_grid(PCGX_PROF_ICP_GRID, st);
     const unsigned gb = (unsigned)((s->nt + kIcpGridBlock - 1) / kIcpGridBlock);
@@ -1190,7 +1211,22 @@ static pcgx_status enqueue_strict(pcgx_icp_session *s, hipStream_t st) {
       PCGX_TRY(strict_create(s->nt, s->d_xyz, s->d_xyz + s->nt, s->d_xyz + 2 * s->nt, (const uint32_t *)s->d_pos_of,
                              &s->strict_buf, st));
     const bool first_iter = s->host_iter++ == 0;
-    if (s->caller_order_fresh)  // pairs already in the caller's order: no gather through pos_of
+    if (s->certify_next) {  // the step's correspondence in the summary kernel (enqueue_corr)
+      s->certify_next = false;
+      static const int force_search = icp_knob("PCGX_TEST_ICP_FUSED_SEARCH", 0, 0, 1 << 30);
+      static const int force_grid_walk = icp_knob("PCGX_TEST_ICP_FUSED_GRID_WALK", 0, 0, 1 << 30);
+      CertifiedTerms C;
+      C.grid = s->base->grid;
+      C.max_dist_sq = s->kp.max_dist_sq;
+      C.match_caller = s->d_match_caller;
+      C.match = s->d_match;
+      C.match_cert = s->d_match_cert;
+      C.pos_of = s->d_pos_of;
+      C.test_force_walk = force_search;
+      C.test_force_grid_walk = force_grid_walk;
+      PCGX_TRY(strict_enqueue(s->strict_buf, (const float4 *)s->d_match_caller, (const uint32_t *)nullptr, s->d_state,
+                              s->d_sums, s->kp, kFuseUpdate, false, first_iter, st, &C));
+    } else if (s->caller_order_fresh)  // pairs already in the caller's order: no gather through pos_of
       PCGX_TRY(strict_enqueue(s->strict_buf, (const float4 *)s->d_match_caller, (const uint32_t *)nullptr, s->d_state,
                               s->d_sums, s->kp, kFuseUpdate, s->tile_sums_fresh, first_iter, st));
     else
@@ -1227,6 +1263,9 @@ static pcgx_status settle(pcgx_icp_session *s, hipStream_t st) {
   const int32_t zero = 0;
   PCGX_HIP_TRY(hipMemcpyAsync(&s->d_state->done, &zero, sizeof zero, hipMemcpyHostToDevice, st));
   PCGX_HIP_TRY(hipMemsetAsync(s->d_walk_count, 0, (size_t)s->grid * sizeof(uint32_t), st));
+  // (a certified summary launch that met `done` 2 midway: its workgroups already past their look at `done` took job
+  // slots and set arrival bits, which the chain kernel -- gone at once -- did not zero)
+  PCGX_TRY(strict_reset(s->strict_buf, st));
   s->host_iter = h.num_iteration;
   for (int32_t k = 0; k < missing; k++) {
     PCGX_TRY(enqueue_corr(s, st, false));

@@ -421,6 +421,7 @@ __device__ __forceinline__ void icp_update_step(IcpState *__restrict__ state, co
 // strict.hip: the evaluator's sequential float32 sums (evaluator.go:122-145), bit for bit, in parallel
 struct StrictBuffers;
 struct StrictWork;
+struct CertifiedTerms;  // strict_terms.h
 pcgx_status strict_create(int64_t nt, const float *tx, const float *ty, const float *tz, const uint32_t *pos_of,
                           StrictBuffers **out, hipStream_t st);
 void strict_destroy(StrictBuffers *b);
@@ -431,7 +432,7 @@ const StrictWork *strict_work(StrictBuffers *b, const IcpKernelParams &kp);
 // first_iter: (as far as the host can tell) the first Evaluate of a Fit -- the repair pass runs (strict.hip)
 pcgx_status strict_enqueue(StrictBuffers *b, const float4 *match, const uint32_t *pos_of, IcpState *state,
                            double *sums10, const IcpKernelParams &kp, bool fuse_update, bool have_tile_sums, bool first_iter,
-                           hipStream_t st);
+                           hipStream_t st, const struct CertifiedTerms *certify = nullptr);
 pcgx_status strict_read_debug(StrictBuffers *b, unsigned long long out[64], hipStream_t st);
 // strict_check.hip: the same sums by one wave, term after term (the on-device cross-check; set_strict 2)
 pcgx_status strict_check_enqueue(const float *d_xyz, int64_t nt, int64_t nt_pad, const float4 *match, const uint32_t *pos_of,

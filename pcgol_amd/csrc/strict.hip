@@ -22,6 +22,7 @@
 // Nothing here is approximate: a record is applied only when its interval proves the result.
 #include <stddef.h>
 
+#include "knn_grid.h"
 #include "strict_terms.h"
 
 namespace pcgx {
@@ -432,13 +433,72 @@ enum { JOB_CROSSING = 1, JOB_NOWINDOW = 2 };
 // guesses depend on it.  No rank waits for anything that depends on ANOTHER rank's wait: the totals leave a rank
 // without row_base in them, so the ranks' launches do not chain up.
 constexpr long long kExchangeTicks = 200000;  // s_memrealtime runs at 100 MHz
-template <bool kExchange, bool kSharded = false>
+// kCertify's searches (strict_sum_kernel): the tile's targets whose certificate did not hold, a lane each.  What
+// icp_grid_kernel does for such a target, with the same operands: the bound is the DistSq to last iteration's partner
+// (+inf before the first one), the new pair goes to both orders and its partner's certificate along (session order:
+// what a later grid pass reads; caller order: in w, what the next certified step reads).  The pair's terms replace the
+// target's (-0.0f, no pair) in the staged tile.
+__device__ __forceinline__ void certified_search(const CertifiedTerms &C, const TermSrc &S, const IcpState *state, const StrictWork &W,
+                                                 int64_t tile, const uint16_t *list, int nl, float4 *terms /* [kStrictRows][kTile / 4] */,
+                                                 int *np_more) {
+  TermSrc S0 = S;
+  S0.project = false;  // (the targets below are moved already)
+  for (int j = threadIdx.x; j < nl; j += kSumBlock) {
+    const int q = list[j];
+    const int64_t c = tile * kTile + q;
+    float x = W.xyz_caller[3 * c], y = W.xyz_caller[3 * c + 1], z = W.xyz_caller[3 * c + 2];
+    float ub = __builtin_inff();
+    if (S.project) {
+      float px, py, pz;
+      mat4_transform(S.m, x, y, z, px, py, pz);
+      x = px; y = py; z = pz;
+      const float4 pm = C.match_caller[c];
+      const float dx = pm.x - x, dy = pm.y - y, dz = pm.z - z;
+      const float dm = (dx * dx + dy * dy) + dz * dz;
+      if (pm.w >= 0.0f && dm == dm) ub = dm;
+    }
+    float4 best = make_float4(0.0f, 0.0f, 0.0f, __int_as_float(-1));
+    float best_d = C.max_dist_sq;
+    GridVerdict v = grid_nearest(C.grid, x, y, z, C.max_dist_sq, ub, best, best_d);
+    if (C.test_force_grid_walk && c % C.test_force_grid_walk == 0) v = GRID_WALK;  // (tests)
+    if (v == GRID_WALK) {  // the records stay as they are; the step is enqueued again with the walk (icp.hip, settle)
+      if (atomicCAS(&const_cast<IcpState *>(state)->done, 0, 2) == 0) atomicAdd(&W.dbg[47], 1ull << 32);
+      continue;
+    }
+    const bool found = __float_as_int(best.w) >= 0;
+    const float cert = (v == GRID_FOUND && found) ? C.grid.cert[__float_as_uint(best.w)] : 0.0f;
+    const uint32_t pos = C.pos_of[c];
+    C.match[pos] = make_float4(best.x, best.y, best.z, found ? best_d : -1.0f);
+    C.match_cert[pos] = cert;
+    C.match_caller[c] = make_float4(best.x, best.y, best.z, found ? cert : -1.0f);
+    if (found) {
+      float t[kStrictRows];
+      (void)pair_terms(S0, x, y, z, make_float4(best.x, best.y, best.z, best_d), t);
+      const int l = q / kLeaf, vq = (q % kLeaf) / 4, cc = q % 4;
+#pragma unroll
+      for (int k = 0; k < kStrictRows; k++) reinterpret_cast<float *>(&terms[k * (kTile / 4) + tile_quad(l, vq)])[cc] = t[k];
+      atomicAdd(np_more, 1);
+    }
+  }
+}
+
+// kCertify (CertifiedTerms, strict_terms.h; one GPU, with kExchange): this launch is also the step's correspondence pass.
+// A target keeps last iteration's partner when the pair's DistSq is below the partner's certificate (icp_grid_kernel's
+// test, verbatim); the others -- two or so a tile from a Fit's third iteration on -- go on an LDS list, and after the
+// tile's terms are staged the workgroup's first lanes search them with icp_grid_kernel's grid_nearest call (the same
+// bound: the same answer), write the new pairs in both orders and put their terms in place.  A search the grid cannot
+// certify (GRID_WALK) sets `done` 2, as the grid pass without the walk does: the host enqueues the step again (settle()).
+template <bool kExchange, bool kSharded = false, bool kCertify = false>
 __global__ __launch_bounds__(kSumBlock) __attribute__((amdgpu_waves_per_eu(4, 4))) void strict_sum_kernel(
-    const float4 *__restrict__ match, const uint32_t *__restrict__ pos_of, const IcpState *__restrict__ state, StrictWork W) {
+    const float4 *__restrict__ match, const uint32_t *__restrict__ pos_of, const IcpState *__restrict__ state, StrictWork W,
+    CertifiedTerms C = CertifiedTerms()) {
   __shared__ float4 s_terms[kStrictRows][kTile / 4];
   __shared__ int s_np[kSumWaves];
   __shared__ double s_tot[16];
+  __shared__ uint16_t s_list[kCertify ? kTile : 1];  // kCertify: the tile's targets (index in the tile) to search for
+  __shared__ int s_nlist, s_np_more;
   static_assert(!kSharded || kExchange, "the ring form rides on the exchange");
+  static_assert(!kCertify || (kExchange && !kSharded), "the certified terms: one GPU, with the exchange");
   const int done = state->done;  // (looked at behind phase 1, whose loads it would only hold up: nothing is written before)
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int64_t tile = blockIdx.x;
@@ -453,11 +513,33 @@ __global__ __launch_bounds__(kSumBlock) __attribute__((amdgpu_waves_per_eu(4, 4)
     const int l = threadIdx.x >> 3, v = threadIdx.x & 7;
     float4 bp[4];
     float tx[4], ty[4], tz[4];
-    load_quad(S, tile * kTile + (int64_t)l * kLeaf + 4 * v, bp, tx, ty, tz);
+    const int64_t i0 = tile * kTile + (int64_t)l * kLeaf + 4 * v;
+    load_quad(S, i0, bp, tx, ty, tz);
+    if (kCertify) {
+      if (threadIdx.x == 0) s_nlist = s_np_more = 0;
+      __syncthreads();
+    }
     float t[4][kStrictRows];
     int np = 0;
 #pragma unroll
-    for (int c = 0; c < 4; c++) np += pair_terms(S, tx[c], ty[c], tz[c], bp[c], t[c]) ? 1 : 0;
+    for (int c = 0; c < 4; c++) {
+      if (kCertify) {
+        // icp_grid_kernel's test: the moved target's DistSq to last iteration's partner (pair_terms forms the same
+        // floats again) below the partner's certificate, which match_caller carries in w
+        float x = tx[c], y = ty[c], z = tz[c];
+        if (S.project) mat4_transform(S.m, tx[c], ty[c], tz[c], x, y, z);
+        const float dx = bp[c].x - x, dy = bp[c].y - y, dz = bp[c].z - z;
+        const float dm = (dx * dx + dy * dy) + dz * dz;
+        bool kept = S.project && bp[c].w >= 0.0f && dm < bp[c].w && dm < C.max_dist_sq;
+        if ((C.test_force_walk && (i0 + c) % C.test_force_walk == 0) || (C.test_force_grid_walk && (i0 + c) % C.test_force_grid_walk == 0))
+          kept = false;  // (tests: searched below, and with the second knob, handed back as GRID_WALK)
+        if (!kept && i0 + c < W.nt) {
+          s_list[atomicAdd(&s_nlist, 1)] = (uint16_t)(l * kLeaf + 4 * v + c);
+          bp[c].w = -1.0f;  // (its terms: searched for below; until then none)
+        }
+      }
+      np += pair_terms(S, tx[c], ty[c], tz[c], bp[c], t[c]) ? 1 : 0;
+    }
 #pragma unroll
     for (int k = 0; k < kStrictRows; k++) s_terms[k][tile_quad(l, v)] = make_float4(t[0][k], t[1][k], t[2][k], t[3][k]);
 #pragma unroll
@@ -466,8 +548,19 @@ __global__ __launch_bounds__(kSumBlock) __attribute__((amdgpu_waves_per_eu(4, 4)
   }
   __syncthreads();
   if (done) return;  // uniform
+  if (kCertify) {
+    const int nl = s_nlist;  // uniform
+    if (nl > 0) {
+      certified_search(C, make_term_src(match, pos_of, state, W), state, W, tile, s_list, nl, &s_terms[0][0], &s_np_more);
+      __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+      if (tile == 0) atomicAdd(&W.dbg[47], 1ull);  // (fused steps; replayed ones in the high word: certified_search)
+      if (nl > 0) atomicAdd(&W.dbg[59], (unsigned long long)nl);
+    }
+  }
   if (threadIdx.x == 0) {
-    int np = 0;
+    int np = kCertify ? s_np_more : 0;
     for (int w = 0; w < kSumWaves; w++) np += s_np[w];
     W.tile_pairs[tile] = (uint32_t)np;
   }
@@ -2637,7 +2730,7 @@ static void launch_chain(const StrictWork &W, const float4 *match, const uint32_
 
 pcgx_status strict_enqueue(StrictBuffers *b, const float4 *match, const uint32_t *pos_of, IcpState *state,
                            double *sums10, const IcpKernelParams &kp, bool fuse_update, bool have_tile_sums, bool first_iter,
-                           hipStream_t st) {
+                           hipStream_t st, const CertifiedTerms *certify) {
   (void)strict_work(b, kp);
   const StrictWork &W = next_epoch(b);
   if (!have_tile_sums && !W.exchange) {
@@ -2647,7 +2740,12 @@ pcgx_status strict_enqueue(StrictBuffers *b, const float4 *match, const uint32_t
   }
   {
     ProfScope prof(PCGX_PROF_STRICT_SUM, st);
-    if (W.exchange)
+    if (certify && W.exchange && !pos_of)  // (the step's correspondence as well: no grid pass in front, icp.hip)
+      hipLaunchKernelGGL((strict_sum_kernel<true, false, true>), dim3((unsigned)W.ntiles), dim3(kSumBlock), 0, st, match,
+                         pos_of, (const IcpState *)state, W, *certify);
+    else if (certify)
+      return fail(PCGX_E_INVALID, "strict sums: the certified terms need the exchange and the pairs in the caller's order");
+    else if (W.exchange)
       hipLaunchKernelGGL(strict_sum_kernel<true>, dim3((unsigned)W.ntiles), dim3(kSumBlock), 0, st, match, pos_of,
                          (const IcpState *)state, W);
     else

@@ -97,7 +97,8 @@ struct StrictWork {
   uint32_t *cand;               // [naux][kCand]: the tile carried out from kCand start states (cand_offset)
   unsigned int *aux_count;      // [kAuxShards] x 32 words: slots handed out this iteration, per shard (zeroed by the chain kernel)
   unsigned int *done_rows;      // rows of the chain kernel that have finished (ticket of the fused update)
-  unsigned long long *dbg;      // [64] counters (measurement aid)
+  unsigned long long *dbg;      // [64] counters (measurement aid; [47]: certified steps, those that met `done` 2 in the high
+                                // word; [59]: targets searched inside them -- CertifiedTerms)
   unsigned long long *stamps;   // [ntiles][8] wall-clock stamps of the summary kernel's workgroups (measurement aid)
   int64_t nt, ntiles;
   int32_t naux;
@@ -143,6 +144,21 @@ struct StrictWork {
   int32_t spec_depth; // a walker with at least this many walks in front of it walks ahead of its wait (strict_chain_kernel<., kSpec>)
   int32_t selfcheck;  // bit 0: every step of the chain walk is re-derived term by term and compared (dbg[12..15]);
                       // 1: PCGX_STRICT_TRACE stamps; 2: no candidate tables; 3: wall-clock columns of the counters
+};
+
+// The certified-terms form of a step (strict_sum_kernel<., ., true>; icp.hip, enqueue_corr): no grid pass in front of
+// the summary kernel.  Its phase 1 reads every target and last iteration's partner in the caller's order anyway; a pair
+// whose DistSq is below the partner's certificate (match_caller[c].w) is this iteration's pair again, the others are
+// searched right there with the grid pass's own grid_nearest call and written back in both orders.
+struct CertifiedTerms {
+  GridView grid;
+  float max_dist_sq;
+  float4 *match_caller;      // [nt] caller order: {partner, certificate (0: none)}, w = -1: no pair (the summary's `match`)
+  float4 *match;             // [nt] session order: {partner, DistSq} (icp.hip, d_match)
+  float *match_cert;         // [nt] session order: the partner's certificate (d_match_cert)
+  const uint32_t *pos_of;    // [nt] caller's index -> session position
+  int32_t test_force_walk;   // tests: every k-th target (caller index) is searched although its certificate holds
+  int32_t test_force_grid_walk;  // tests: ... and its search ends in GRID_WALK (the step is replayed with the walk)
 };
 
 // ---- the ring (a target spread over ranks, strict_enqueue_ring) -------------------------------------------------
