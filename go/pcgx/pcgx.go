@@ -1019,3 +1019,133 @@ func FitSharded(base *KDTree, tile pc.Vec3RandomAccessor, e *Evaluator, u *icp.G
 	}
 	return trans, stat, status(rc)
 }
+
+// ------------------------------------------------- sample consensus plane detection
+
+// SACPlane is voxelGridSurfaceModelCoefficients (pc/sac/surface.go:191-200); its layout is pcgx_sac_plane's.
+type SACPlane struct {
+	Origin, V1, V2 mat.Vec3
+	L1, L2         float32
+	Norm           mat.Vec3
+	D              float32
+}
+
+func (c *SACPlane) cptr() *C.pcgx_sac_plane { return (*C.pcgx_sac_plane)(unsafe.Pointer(c)) }
+
+// SACPlaneModel is pc/sac's voxelGridSurfaceModel (surface.go:9-34) on the device: the cloud's xyz, the grid's
+// occupied voxels and bucket lengths, vg.MinMax() and Resolution() copied at creation.
+type SACPlaneModel struct {
+	h *C.pcgx_sac_plane_model
+	n int
+}
+
+// NewSACPlaneModel copies ra and the buckets of g into library-owned device memory.
+func NewSACPlaneModel(g *BucketGrid, ra pc.Vec3RandomAccessor) (*SACPlaneModel, error) {
+	runtime.LockOSThread() // the error text is thread-local on the C side: call and pcgx_last_error on one OS thread
+	defer runtime.UnlockOSThread()
+	defer runtime.KeepAlive(g)
+	xyz := packVec3(ra)
+	var data unsafe.Pointer
+	if len(xyz) > 0 {
+		data = unsafe.Pointer(&xyz[0])
+	}
+	m := &SACPlaneModel{n: ra.Len()}
+	rc := C.pcgx_sac_plane_model_create(g.h, data, C.int64_t(ra.Len()), 12, 0, 0, &m.h)
+	runtime.KeepAlive(xyz)
+	if err := status(rc); err != nil {
+		return nil, err
+	}
+	runtime.SetFinalizer(m, func(m *SACPlaneModel) { m.Close() })
+	return m, nil
+}
+
+// Close releases the model.
+func (m *SACPlaneModel) Close() {
+	runtime.LockOSThread()
+	defer runtime.UnlockOSThread()
+	defer runtime.KeepAlive(m)
+	if m.h != nil {
+		C.pcgx_sac_plane_model_free(m.h)
+		m.h = nil
+	}
+}
+
+// Len is ra.Len() of the model's cloud.
+func (m *SACPlaneModel) Len() int { return m.n }
+
+// SACResult is one Compute over pre-drawn ids: the first hypothesis of the largest score above 0 (sac.go:49),
+// and every hypothesis' Fit flag, coefficients and Evaluate().
+type SACResult struct {
+	Found     bool
+	Best      int
+	BestScore int
+	BestCoeff SACPlane
+	OK        []bool
+	Coeff     []SACPlane
+	Score     []int
+}
+
+// Compute fits and evaluates len(ids)/3 hypotheses in one device call.  An id outside [0, Len()) is
+// ErrOutOfRange (the reference panics).
+func (m *SACPlaneModel) Compute(ids []int) (*SACResult, error) {
+	runtime.LockOSThread()
+	defer runtime.UnlockOSThread()
+	defer runtime.KeepAlive(m)
+	if len(ids)%3 != 0 {
+		return nil, errors.New("pcgx: three ids per hypothesis")
+	}
+	n := len(ids) / 3
+	ids64 := make([]int64, len(ids)+1)
+	for i, v := range ids {
+		ids64[i] = int64(v)
+	}
+	ok := make([]int32, n+1)
+	coeff := make([]SACPlane, n+1)
+	score := make([]int64, n+1)
+	var found C.int32_t
+	var best, bestScore C.int64_t
+	r := &SACResult{}
+	rc := C.pcgx_sac_plane_compute(m.h, (*C.int64_t)(unsafe.Pointer(&ids64[0])), C.int64_t(n), &found, &best, &bestScore,
+		r.BestCoeff.cptr(), (*C.int32_t)(unsafe.Pointer(&ok[0])), coeff[0].cptr(), (*C.int64_t)(unsafe.Pointer(&score[0])))
+	runtime.KeepAlive(ids64)
+	runtime.KeepAlive(ok)
+	runtime.KeepAlive(coeff)
+	runtime.KeepAlive(score)
+	if err := status(rc); err != nil {
+		return nil, err
+	}
+	r.Found, r.Best, r.BestScore = found != 0, int(best), int(bestScore)
+	r.OK = make([]bool, n)
+	r.Score = make([]int, n)
+	for i := 0; i < n; i++ {
+		r.OK[i] = ok[i] != 0
+		r.Score[i] = int(score[i])
+	}
+	r.Coeff = coeff[:n]
+	return r, nil
+}
+
+// Inliers is Inliers(d) (surface.go:222-235) of c over the model's cloud, ids ascending.
+func (m *SACPlaneModel) Inliers(c *SACPlane, d float32) []int {
+	runtime.LockOSThread()
+	defer runtime.UnlockOSThread()
+	defer runtime.KeepAlive(m)
+	var cnt C.int64_t
+	if C.pcgx_sac_plane_inliers(m.h, c.cptr(), C.float(d), nil, 0, &cnt) != C.PCGX_OK || cnt <= 0 {
+		return []int{}
+	}
+	ids := make([]int64, int(cnt))
+	C.pcgx_sac_plane_inliers(m.h, c.cptr(), C.float(d), (*C.int64_t)(unsafe.Pointer(&ids[0])), cnt, &cnt)
+	runtime.KeepAlive(ids)
+	return idsToInt(ids[:int(cnt)])
+}
+
+// IsIn is IsIn(p, d) (surface.go:237-240).
+func (m *SACPlaneModel) IsIn(c *SACPlane, p mat.Vec3, d float32) bool {
+	runtime.LockOSThread()
+	defer runtime.UnlockOSThread()
+	defer runtime.KeepAlive(m)
+	var in C.int32_t
+	C.pcgx_sac_plane_is_in(m.h, c.cptr(), (*C.float)(unsafe.Pointer(&p[0])), C.float(d), &in)
+	return in != 0
+}

@@ -618,6 +618,45 @@ PCGX_API pcgx_status pcgx_region_growing_segment(const pcgx_kdtree *t, const uin
 PCGX_API pcgx_status pcgx_region_growing_segment_bfs(const pcgx_kdtree *t, const uint32_t *labels, const float p[3],
                                                      float max_range, int64_t *out, int64_t cap, int64_t *count);
 
+/* ------------------------------------------------ sample consensus plane detection
+ * replaces pc/sac (sac.go:33-59 SAC.Compute, surface.go:36-240 the voxel-grid plane model, Fit / Evaluate /
+ * Inliers / IsIn) over a bucket voxel grid.  Neither Fit nor Evaluate draws random numbers: the caller's sampler
+ * draws the 3n ids of n hypotheses first, in the order sac.go:40-43 draws them, and ONE call fits and evaluates
+ * them all on the device -- the same hypotheses give the reference's result bit for bit (float32 arithmetic left
+ * to right, no contraction).
+ * Model creation copies what the model reads into library-owned device memory before it returns: the cloud's xyz
+ * (data: host records, or device records with on_device = 1; stride / xyz_off as pcgx_bucket_grid_build), the
+ * grid's occupied voxels and their bucket lengths, vg.MinMax() and Resolution().  The caller's buffers and the
+ * grid may change or go afterwards. */
+typedef struct pcgx_sac_plane_model pcgx_sac_plane_model;
+/* voxelGridSurfaceModelCoefficients (surface.go:191-200) */
+typedef struct {
+  float origin[3], v1[3], v2[3];
+  float l1, l2;
+  float norm[3];
+  float d;
+} pcgx_sac_plane;
+PCGX_API pcgx_status pcgx_sac_plane_model_create(const pcgx_bucket_grid *g, const void *data, int64_t n, int32_t stride,
+                                                 int32_t xyz_off, int32_t on_device, pcgx_sac_plane_model **out);
+PCGX_API pcgx_status pcgx_sac_plane_model_free(pcgx_sac_plane_model *m);
+/* Compute(n) over the pre-drawn ids[3n] (Fit(ids) alone is n = 1).  *found = 0 when no hypothesis scores above 0
+ * (then *best = -1, *best_score = 0 and best_coeff is not written); else the FIRST hypothesis of the largest
+ * score (sac.go:49: e > bestE).  ok[n], coeff[n] (zero where Fit failed) and score[n] (Evaluate(), 0 where Fit
+ * failed) may each be NULL.  An id outside [0, n_points) is PCGX_E_OUT_OF_RANGE (the reference panics), n < 0 or
+ * a NULL argument PCGX_E_INVALID; nothing is written then.  A lattice with more than 8192 values along one of its
+ * two axes (the serial a / b accumulators, surface.go:206-207) is PCGX_E_TOO_LARGE, nothing written. */
+PCGX_API pcgx_status pcgx_sac_plane_compute(pcgx_sac_plane_model *m, const int64_t *ids, int64_t n, int32_t *found,
+                                            int64_t *best, int64_t *best_score, pcgx_sac_plane *best_coeff,
+                                            int32_t *ok, pcgx_sac_plane *coeff, int64_t *score);
+/* Inliers(d) (surface.go:222-235): every point of the model's cloud, ids ascending, with
+ * -d < norm . (p - vgMin) - c->d < d (points outside the grid included).  *count = result length; the first
+ * min(count, cap) ids are written. */
+PCGX_API pcgx_status pcgx_sac_plane_inliers(pcgx_sac_plane_model *m, const pcgx_sac_plane *c, float d, int64_t *out,
+                                            int64_t cap, int64_t *count);
+/* IsIn(p, d) (surface.go:237-240), on the host */
+PCGX_API pcgx_status pcgx_sac_plane_is_in(const pcgx_sac_plane_model *m, const pcgx_sac_plane *c, const float p[3], float d,
+                                          int32_t *in);
+
 /* ---------------------------------------------------------------- PCD files
  * replaces pc.UnmarshalHeader / pc.Unmarshal / pc.Marshal (pc/io.go:24-45,47-230,232-285) with a
  * device-resident output: the records of an ascii / binary / binary_compressed file land in HBM

@@ -123,6 +123,11 @@ class PcdHeader(C.Structure):  # pcgx_pcd_header
                 ("stride", C.c_int64), ("data_offset", C.c_int64)]
 
 
+class SacPlane(C.Structure):  # pcgx_sac_plane (surface.go:191-200)
+    _fields_ = [("origin", C.c_float * 3), ("v1", C.c_float * 3), ("v2", C.c_float * 3), ("l1", C.c_float),
+                ("l2", C.c_float), ("norm", C.c_float * 3), ("d", C.c_float)]
+
+
 class IcpStat(C.Structure):
     _fields_ = [("evaluated", IcpEvaluated), ("num_iteration", C.c_int32)]
 
@@ -237,6 +242,12 @@ SIGNATURES = {
     "pcgx_icp_plane_finish_evaluate": (_i32, [_vp, _i32, C.POINTER(IcpEvaluated), _vp]),
     "pcgx_icp_gauss_newton_update": (_i32, [C.POINTER(IcpParams), _f32, C.POINTER(_i32), _vp, _vp, _vp,
                                             C.POINTER(_i32)]),
+    "pcgx_sac_plane_model_create": (_i32, [_vp, _vp, _i64, _i32, _i32, _i32, C.POINTER(_vp)]),
+    "pcgx_sac_plane_model_free": (_i32, [_vp]),
+    "pcgx_sac_plane_compute": (_i32, [_vp, _vp, _i64, C.POINTER(_i32), C.POINTER(_i64), C.POINTER(_i64),
+                                      C.POINTER(SacPlane), _vp, _vp, _vp]),
+    "pcgx_sac_plane_inliers": (_i32, [_vp, C.POINTER(SacPlane), _f32, _vp, _i64, C.POINTER(_i64)]),
+    "pcgx_sac_plane_is_in": (_i32, [_vp, C.POINTER(SacPlane), _vp, _f32, C.POINTER(_i32)]),
 }
 
 _lib = None

@@ -25,6 +25,7 @@
 #include <unordered_set>
 #include <vector>
 
+#include "bucket_grid.h"
 #include "knn_grid.h"
 #include "range_walk.h"
 
@@ -76,13 +77,7 @@ __global__ __launch_bounds__(256) void uf_flatten_kernel(uint32_t *__restrict__ 
 }
 
 // ------------------------------------------------------------------ bucket grid
-struct GridParams {
-  float origin[3];
-  float resolution_inv;
-  int64_t size[3];
-  int64_t len;
-};
-
+// (GridParams, grid_addr, lower_bound_u32 and the tile compaction: bucket_grid.h)
 __device__ __forceinline__ float ld_f32_unaligned(const uint8_t *p) {
   float v;
   __builtin_memcpy(&v, p, 4);
@@ -97,71 +92,26 @@ __global__ __launch_bounds__(256) void grid_key_kernel(const uint8_t *__restrict
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (i >= n) return;
   const uint8_t *rec = data + i * stride + off;
-  int64_t v[3];
-  bool ok = true;
-#pragma unroll
-  for (int k = 0; k < 3; k++) {
-    const float pos = ld_f32_unaligned(rec + 4 * k) - gp.origin[k];
-    const float f = pos * gp.resolution_inv + 0.5f;
-    // NaN or beyond int64: Go's conversion is implementation defined; such a point is outside
-    ok = ok && (f == f) && f > -9.0e18f && f < 9.0e18f;
-    v[k] = ok ? (int64_t)f : -1;
-    ok = ok && v[k] >= 0 && v[k] < gp.size[k];
-  }
-  const uint32_t a = ok ? (uint32_t)(v[0] + (v[1] + v[2] * gp.size[1]) * gp.size[0]) : (uint32_t)gp.len;
+  int64_t addr, v[3];
+  const bool ok = grid_addr(gp, ld_f32_unaligned(rec), ld_f32_unaligned(rec + 4), ld_f32_unaligned(rec + 8), &addr, v);
+  const uint32_t a = ok ? (uint32_t)addr : (uint32_t)gp.len;
   key[i] = a;
   key_orig[i] = a;
   idx[i] = (uint32_t)i;
 }
 
-// Run heads of the sorted keys: head_rank via block scan (one block per 2048 keys) in two launches.
-constexpr int kRunTile = 2048;
-
+// Run heads of the sorted keys: head_rank via block scan (one block per kRunTile keys) in two launches.
 __device__ __forceinline__ bool run_head(const uint32_t *__restrict__ k, int64_t j) { return j == 0 || k[j] != k[j - 1]; }
 
 __global__ __launch_bounds__(256) void run_count_kernel(const uint32_t *__restrict__ k, int64_t n,
                                                         uint32_t *__restrict__ tile_count) {
-  __shared__ uint32_t ws[4];
-  const int64_t base = (int64_t)blockIdx.x * kRunTile;
-  uint32_t c = 0;
-  for (int r = 0; r < kRunTile / 256; r++) {
-    const int64_t j = base + r * 256 + threadIdx.x;
-    if (j < n && run_head(k, j)) c++;
-  }
-  for (int o = 32; o > 0; o >>= 1) c += __shfl_down(c, o);
-  if ((threadIdx.x & 63) == 0) ws[threadIdx.x >> 6] = c;
-  __syncthreads();
-  if (threadIdx.x == 0) tile_count[blockIdx.x] = ws[0] + ws[1] + ws[2] + ws[3];
+  tile_flag_count(n, [=](int64_t j) { return run_head(k, j); }, tile_count);
 }
 
 // exclusive scan of the tile counts by one block; total -> *total
 __global__ __launch_bounds__(1024) void run_scan_kernel(uint32_t *__restrict__ tile_count, int ntiles,
                                                         uint32_t *__restrict__ total) {
-  __shared__ uint32_t ws[16];
-  __shared__ uint32_t carry_s;
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  if (threadIdx.x == 0) carry_s = 0;
-  __syncthreads();
-  for (int start = 0; start < ntiles; start += 1024) {
-    const int i = start + threadIdx.x;
-    const uint32_t v = i < ntiles ? tile_count[i] : 0u;
-    uint32_t inc = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-      const uint32_t t = __shfl_up(inc, o);
-      if (lane >= o) inc += t;
-    }
-    if (lane == 63) ws[wave] = inc;
-    __syncthreads();
-    uint32_t wbase = 0;
-    for (int w = 0; w < wave; w++) wbase += ws[w];
-    const uint32_t carry = carry_s;
-    if (i < ntiles) tile_count[i] = carry + wbase + inc - v;
-    __syncthreads();
-    if (threadIdx.x == 1023) carry_s = carry + wbase + inc;
-    __syncthreads();
-  }
-  if (threadIdx.x == 0) *total = carry_s;
+  tile_scan(tile_count, ntiles, total);
 }
 
 // run r: run_key[r] = its key, run_start[r] = first sorted position (run_start[runs] = n is set by the host)
@@ -169,39 +119,10 @@ __global__ __launch_bounds__(256) void run_write_kernel(const uint32_t *__restri
                                                         const uint32_t *__restrict__ tile_offset,
                                                         uint32_t *__restrict__ run_key,
                                                         uint32_t *__restrict__ run_start) {
-  __shared__ uint32_t ws[4];
-  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
-  const int64_t base = (int64_t)blockIdx.x * kRunTile;
-  uint32_t running = tile_offset[blockIdx.x];
-  const uint64_t lt_mask = lane == 0 ? 0ull : (~0ull >> (64 - lane));
-  for (int r = 0; r < kRunTile / 256; r++) {
-    const int64_t j = base + r * 256 + threadIdx.x;
-    const bool head = j < n && run_head(k, j);
-    const uint64_t bal = __ballot(head);
-    if (lane == 0) ws[wave] = (uint32_t)__popcll(bal);
-    __syncthreads();
-    uint32_t wbase = 0, round_total = 0;
-    for (int w = 0; w < 4; w++) {
-      if (w < wave) wbase += ws[w];
-      round_total += ws[w];
-    }
-    if (head) {
-      const uint32_t slot = running + wbase + (uint32_t)__popcll(bal & lt_mask);
-      run_key[slot] = k[j];
-      run_start[slot] = (uint32_t)j;
-    }
-    running += round_total;
-    __syncthreads();
-  }
-}
-
-__device__ __forceinline__ int64_t lower_bound_u32(const uint32_t *__restrict__ a, int64_t n, uint32_t v) {
-  int64_t lo = 0, hi = n;
-  while (lo < hi) {
-    const int64_t mid = (lo + hi) >> 1;
-    if (a[mid] < v) lo = mid + 1; else hi = mid;
-  }
-  return lo;
+  tile_flag_write(n, [=](int64_t j) { return run_head(k, j); }, tile_offset, [=](uint32_t slot, int64_t j) {
+    run_key[slot] = k[j];
+    run_start[slot] = (uint32_t)j;
+  });
 }
 
 // Flood-fill connectivity (segmentation/voxelgrid/voxelgrid.go:13-25,62-70): an occupied voxel is
@@ -356,18 +277,6 @@ __global__ __launch_bounds__(256) void uf_jump_kernel(uint32_t *__restrict__ par
 
 using namespace pcgx;
 
-struct pcgx_bucket_grid {
-  int64_t n = 0;  // points offered (Add(point i, i) for i in [0, n))
-  float resolution = 0.0f;
-  GridParams gp;
-  // host copies of the CSR buckets (downloaded once): occupied voxels ascending
-  std::vector<uint32_t> cell_addr, cell_start, idx_sorted, point_key;
-  std::vector<int32_t> cell_of_addr;  // lazily (segment_bfs, grids up to 2^27 voxels): address -> voxel, -1 empty
-  std::vector<uint32_t> cell_comp;  // lazily: smallest voxel address of each voxel's component
-  bool have_comp = false;
-  int64_t n_in = 0;
-};
-
 static pcgx_status grid_params(float resolution, const int64_t size[3], const float origin[3], GridParams &gp) {
   if (!(resolution > 0.0f)) return fail(PCGX_E_INVALID, "bucket grid: resolution must be > 0");
   double len = 1.0;
@@ -493,18 +402,9 @@ extern "C" pcgx_status pcgx_bucket_grid_counts(const pcgx_bucket_grid *g, int64_
   return PCGX_OK;
 }
 
-// VoxelGrid.Addr (voxelgrid.go:64-79), host arithmetic identical to grid_key_kernel
+// VoxelGrid.Addr (voxelgrid.go:64-79) on the host: grid_addr, the arithmetic of grid_key_kernel
 static bool grid_addr_host(const GridParams &gp, const float p[3], int64_t *addr, int64_t xyz[3]) {
-  for (int k = 0; k < 3; k++) {
-    const float pos = p[k] - gp.origin[k];
-    const float f = pos * gp.resolution_inv + 0.5f;
-    if (!(f == f) || !(f > -9.0e18f) || !(f < 9.0e18f)) return false;
-    const int64_t v = (int64_t)f;
-    if (v < 0 || v >= gp.size[k]) return false;
-    xyz[k] = v;
-  }
-  *addr = xyz[0] + (xyz[1] + xyz[2] * gp.size[1]) * gp.size[0];
-  return true;
+  return grid_addr(gp, p[0], p[1], p[2], addr, xyz);
 }
 
 extern "C" pcgx_status pcgx_bucket_grid_addr(const pcgx_bucket_grid *g, const float p[3], int64_t *addr, int32_t *ok) {

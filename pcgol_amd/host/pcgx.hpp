@@ -9,6 +9,7 @@
 //   pcgx::PointToPointICP   <- icp.PointToPointICPGradient{Evaluator, UpdaterFactory}
 //   pcgx::BucketVoxelGrid   <- pc/storage/voxelgrid.VoxelGrid + pc/segmentation/voxelgrid (Segment)
 //   pcgx::RegionGrowing     <- pc/segmentation/regiongrowing.RegionGrowing
+//   pcgx::sac::SAC          <- pc/sac.SAC over NewVoxelGridSurfaceModel (the plane model of a BucketVoxelGrid)
 //   pcgx::PointToPlaneICP   <- (extension, no counterpart in the reference) the same Fit shape with
 //                              the point-to-plane evaluator / Gauss-Newton updater, HasHessian() == true
 //   pcgx::Comm              <- (no counterpart: the reference is one process) the exchange of the
@@ -19,6 +20,7 @@
 #include <initializer_list>
 #include <memory>
 #include <cstring>
+#include <random>
 #include <stdexcept>
 #include <string>
 #include <vector>
@@ -203,6 +205,7 @@ class BucketVoxelGrid {
     if (cnt > 0) check(pcgx_bucket_grid_segment_bfs(h_, p.data(), out.data(), cnt, &cnt));
     return out;
   }
+  const pcgx_bucket_grid *handle() const { return h_; }
 
  private:
   pcgx_bucket_grid *h_ = nullptr;
@@ -467,5 +470,123 @@ struct PointToPointICPGradient {  // icp.go:18-67
   }
 };
 }  // namespace icp
+
+// pc/sac (sac.go, randomsample.go, surface.go).  Compute(n) draws the 3n ids from the Sampler first, in the
+// reference's order, and fits and evaluates every hypothesis in one device call (include/pcgx.h).
+namespace sac {
+
+struct Sampler {  // sac.go:7-9
+  virtual ~Sampler() = default;
+  virtual int64_t Sample() = 0;
+};
+
+// randomsample.go:7-12: uniform ids in [0, n) (std::mt19937_64; Go's math/rand sequence is Go's own)
+class RandomSampler : public Sampler {
+ public:
+  explicit RandomSampler(int64_t n, uint64_t seed = std::random_device{}()) : rng_(seed), dist_(0, n - 1) {}
+  int64_t Sample() override { return dist_(rng_); }
+
+ private:
+  std::mt19937_64 rng_;
+  std::uniform_int_distribution<int64_t> dist_;
+};
+inline std::unique_ptr<Sampler> NewRandomSampler(int64_t n) { return std::unique_ptr<Sampler>(new RandomSampler(n)); }
+
+class VoxelGridSurfaceModel;
+using ModelHandle = std::shared_ptr<pcgx_sac_plane_model>;
+
+// voxelGridSurfaceModelCoefficients (surface.go:191-240)
+class Coefficients {
+ public:
+  Coefficients(ModelHandle m, const pcgx_sac_plane &c, int64_t score) : m_(std::move(m)), c_(c), score_(score) {}
+  int64_t Evaluate() const { return score_; }  // computed by the call that fitted these coefficients
+  std::vector<int64_t> Inliers(float d) const {
+    int64_t cnt = 0;
+    check(pcgx_sac_plane_inliers(m_.get(), &c_, d, nullptr, 0, &cnt));
+    std::vector<int64_t> out((size_t)cnt);
+    if (cnt > 0) check(pcgx_sac_plane_inliers(m_.get(), &c_, d, out.data(), cnt, &cnt));
+    return out;
+  }
+  bool IsIn(const Vec3 &p, float d) const {
+    int32_t in = 0;
+    check(pcgx_sac_plane_is_in(m_.get(), &c_, p.data(), d, &in));
+    return in != 0;
+  }
+  const pcgx_sac_plane &plane() const { return c_; }
+
+ private:
+  ModelHandle m_;
+  pcgx_sac_plane c_;
+  int64_t score_;
+};
+
+// voxelGridSurfaceModel (surface.go:9-34): copies the cloud and the grid's buckets at construction
+class VoxelGridSurfaceModel {
+ public:
+  VoxelGridSurfaceModel(const BucketVoxelGrid &vg, const CloudView &ra, bool on_device = false) {
+    pcgx_sac_plane_model *h = nullptr;
+    check(pcgx_sac_plane_model_create(vg.handle(), ra.data, ra.points, ra.stride, ra.xyz_offset, on_device ? 1 : 0, &h));
+    h_ = ModelHandle(h, [](pcgx_sac_plane_model *p) { pcgx_sac_plane_model_free(p); });
+  }
+  std::pair<int, int> NumRange() const { return {3, 3}; }
+  struct Result {
+    bool found = false;
+    int64_t best = -1, best_score = 0;
+    std::unique_ptr<Coefficients> best_coeff;
+    std::vector<int32_t> ok;
+    std::vector<pcgx_sac_plane> coeff;
+    std::vector<int64_t> score;
+  };
+  // Fit + Evaluate of ids.size() / 3 hypotheses
+  Result Compute(const std::vector<int64_t> &ids) const {
+    if (ids.size() % 3) throw Error(PCGX_E_INVALID, "three ids per hypothesis");
+    const int64_t n = (int64_t)ids.size() / 3;
+    Result r;
+    r.ok.resize((size_t)n);
+    r.coeff.resize((size_t)n);
+    r.score.resize((size_t)n);
+    int32_t found = 0;
+    pcgx_sac_plane bc{};
+    check(pcgx_sac_plane_compute(h_.get(), ids.data(), n, &found, &r.best, &r.best_score, &bc, r.ok.data(),
+                                 r.coeff.data(), r.score.data()));
+    r.found = found != 0;
+    if (r.found) r.best_coeff.reset(new Coefficients(h_, bc, r.best_score));
+    return r;
+  }
+  // surface.go:36-181: nullptr when the three points give no plane
+  std::unique_ptr<Coefficients> Fit(const std::vector<int64_t> &ids) const {
+    if (ids.size() != 3) return nullptr;
+    Result r = Compute(ids);
+    if (!r.ok[0]) return nullptr;
+    return std::unique_ptr<Coefficients>(new Coefficients(h_, r.coeff[0], r.score[0]));
+  }
+
+ private:
+  ModelHandle h_;
+};
+
+class SAC {  // sac.go:23-63
+ public:
+  SAC(Sampler &s, const VoxelGridSurfaceModel &m) : sampler_(&s), model_(&m) {}
+  // false keeps the previous Coefficients()
+  bool Compute(int n) {
+    std::vector<int64_t> ids;
+    ids.reserve((size_t)(n > 0 ? n : 0) * 3);
+    for (int i = 0; i < n; i++)
+      for (int j = 0; j < model_->NumRange().first; j++) ids.push_back(sampler_->Sample());
+    auto r = model_->Compute(ids);
+    if (!r.found) return false;
+    best_ = std::move(r.best_coeff);
+    return true;
+  }
+  const sac::Coefficients *Coefficients() const { return best_.get(); }  // nullptr before the first success
+
+ private:
+  Sampler *sampler_;
+  const VoxelGridSurfaceModel *model_;
+  std::unique_ptr<sac::Coefficients> best_;
+};
+
+}  // namespace sac
 
 }  // namespace pcgx
