@@ -487,6 +487,11 @@ PCGX_API pcgx_status pcgx_icp_session_step(pcgx_icp_session *s, void *stream);
  *      kernels are resident at once and only the walkers wait, each for
  *      one word from the rank before it (csrc/strict.hip, strict_enqueue_ring).  Elsewhere (ranks on several nodes,
  *      PCGX_SHARD_RING=0): 2 + world collectives of <= 16 x world doubles per iteration.  Same bits either way.
+ *      Several sessions on ONE communicator: allowed, stepped in any interleaving (A's step k, then B's step k, or
+ *      one Fit after the other), as long as every rank makes its sharded calls on that communicator in the same
+ *      order.  Each session's Fit is then its own, bit for bit: a ring word's tag names the communicator's step,
+ *      not the session's.  A session's first step since it was made or reset begins a Fit on the communicator.  A
+ *      rank that fails a step aborts the ring for every session on the communicator until one of them begins a Fit.
  *  PCGX_SUMS_F64_TREE  partials -> ONE all-reduce of the 10 (plane: 30) float64 sums -> update: faster, and off the
  *      reference by the reference's own rounding noise (1.6e-5 on the transform at 1M pairs).
  * Every collective also carries the ranks' error flag: a rank whose step fails keeps calling the collectives with its

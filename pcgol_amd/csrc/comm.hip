@@ -102,6 +102,7 @@ struct pcgx_comm {
   void *ring_map = nullptr;  // a mapping this communicator owns (shared memory); nullptr: somebody else's block
   size_t ring_bytes = 0;
   uint32_t ring_fit = 0;  // Fits begun on this communicator (comm_ring_new_fit; every rank counts alike): the upper bits of a word's tag
+  int32_t ring_steps = 0; // ring steps taken on this communicator under ring_fit, by ANY session (comm_ring_step): the lower bits
   // The inboxes' DATA words in DEVICE memory (ring_setup_device, collective, behind the host block): every rank's
   // inbox lives in its own GPU's memory and is mapped by the others -- hipIpcOpenMemHandle between processes, the
   // plain pointer (+ hipDeviceEnablePeerAccess) between the device slots of one process.  A store into a peer's inbox
@@ -427,15 +428,25 @@ static void ring_ensure(pcgx_comm *c) {  // collective on first use
 
 // A Fit begins on the communicator: every rank calls this ONCE per Fit, at the same point of its call sequence (the
 // first sharded step of a session since it was made or reset; pcgx_icp_fit_sharded, also on a rank that can go no
-// further).  A word's tag is {Fit number, step + 1} (ring_tag): what an earlier Fit left in the inboxes -- data or
-// abort words, or what a laggard of that Fit still writes -- carries another Fit's number and is nobody's business;
-// and a rank that STOPS stepping in the middle of a Fit (its caller saw an error) is in step with the others again at
-// the next Fit, which a count of steps taken would not be.  The owner wipes its own abort word if an earlier Fit's.
-// (kRingTagStepBits, strict_terms.h: steps 0 .. 4094 of a Fit ride the ring; beyond: the collective form)
-static uint32_t ring_tag(uint32_t fit, int32_t step) { return (fit & 0xfffffu) << kRingTagStepBits | (uint32_t)(step + 1); }
+// further).  A word's tag is {Fit number, the communicator's step count + 1} (ring_tag): what an earlier Fit left in
+// the inboxes -- data or abort words, or what a laggard of that Fit still writes -- carries another Fit's number and is
+// nobody's business; and a rank that STOPS stepping in the middle of a Fit (its caller saw an error) is in step with
+// the others again at the next Fit, which a count of steps alone would not be.  The owner wipes its own abort word if
+// an earlier Fit's.
+// The step count is the COMMUNICATOR's, not the session's: two sessions stepped in turn on one communicator (A's
+// step k, then B's step k) would otherwise tag their words alike, and a walker of B's step could take A's word, still
+// in the inbox slot, for its own while the rank in front of it is late -- wrong sums, no error.  Every rank counts
+// alike, since the ranks make their sharded steps in the same order.  When the 12-bit field would wrap
+// (kRingTagStepBits, strict_terms.h) the Fit number moves on instead.  (A session's own steps 0 .. 4094 of a Fit ride
+// the ring; beyond: the collective form, as before.)
+static uint32_t ring_tag(uint32_t fit, int32_t count) { return (fit & 0xfffffu) << kRingTagStepBits | (uint32_t)(count + 1); }
+static void ring_next_fit(pcgx_comm *c) {
+  if (++c->ring_fit == 0u || (c->ring_fit & 0xfffffu) == 0u) c->ring_fit = 1u;
+  c->ring_steps = 0;
+}
 void comm_ring_new_fit(pcgx_comm *c) {
   ring_ensure(c);
-  if (++c->ring_fit == 0u || (c->ring_fit & 0xfffffu) == 0u) c->ring_fit = 1u;
+  ring_next_fit(c);
   if (!c->ring_host) return;
   const RingLayout RL{c->world};
   unsigned long long *w = c->ring_host + (size_t)c->rank * c->ring_words + RL.abort();
@@ -460,7 +471,8 @@ bool comm_ring_step(pcgx_comm *c, int32_t step, RingView *out) {
   out->words_per_rank = c->ring_words;
   out->rank = c->rank;
   out->world = c->world;
-  out->epoch = ring_tag(c->ring_fit, step);
+  if (c->ring_steps + 1 >= (1 << kRingTagStepBits)) ring_next_fit(c);  // (the step field would wrap)
+  out->epoch = ring_tag(c->ring_fit, c->ring_steps++);
   out->kind = c->ring_kind;
   {
     static const long long knob = getenv("PCGX_RING_GUESS_WAIT_US") ? atoll(getenv("PCGX_RING_GUESS_WAIT_US")) * 100 : 0;  // (tests)

@@ -451,7 +451,7 @@ struct RingView {
   unsigned long long *const *tab = nullptr;  // device memory: [world] every rank's inbox (data words) as this device addresses it
   unsigned long long *mine = nullptr;        // tab[rank]
   int32_t words_per_rank = 0, rank = 0, world = 1;
-  uint32_t epoch = 0;                   // this step's tag: {the communicator's Fit number, step + 1} (comm.hip, ring_tag; every rank counts alike)
+  uint32_t epoch = 0;                   // this step's tag: {the communicator's Fit number, its step count + 1} (comm.hip, ring_tag; every rank counts alike)
   int32_t kind = 0;                     // 1: the data words in host-coherent memory; 2: in the ranks' device memory
   long long guess_ticks = 0;            // bound of the waits only guesses depend on (strict_terms.h, kRingGuessTicks*)
 };

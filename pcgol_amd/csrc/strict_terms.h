@@ -127,7 +127,8 @@ struct StrictWork {
   // host-coherent memory that all GPUs of the node write and poll directly (RingLayout below); a word is a 32-bit
   // payload under a 32-bit tag -- the communicator's step count, `ring_epoch` -- so it says by itself whether it
   // is this step's: no flags, no fences, no resets.  ring == nullptr: one GPU, or the collective form above.
-  // (a word's tag, `ring_epoch` for this step: {the communicator's Fit number, step + 1}, kRingTagStepBits for the step)
+  // (a word's tag, `ring_epoch` for this step: {the communicator's Fit number, its step count + 1}, kRingTagStepBits for
+  // the count: the communicator's ring steps, whatever session took them)
   unsigned long long *ring;   // the ranks' ABORT words: rank k's at ring + k * ring_words + RingLayout::abort(), in the
   int32_t ring_words;         // host-coherent block every host can write (comm.hip); != nullptr: the ring form
   // the DATA words of the inboxes: ring_tab[k] = rank k's inbox as THIS device addresses it -- the rank's own GPU's
@@ -185,7 +186,7 @@ struct RingLayout {
 // that is late by milliseconds costs the others those milliseconds, where giving up after 2 ms cost them the slow paths
 // of hundreds of tiles with guesses off: 37 ms a step, round 5's rehearsals).  Ranks that SHARE a device (tests and
 // rehearsals on the one-GPU box) keep the short bound: there a waiting launch may hold the places the awaited one needs.
-constexpr int kRingTagStepBits = 12;                    // a word's tag: {Fit number (20 bits), step + 1 (12 bits)}, comm.hip ring_tag
+constexpr int kRingTagStepBits = 12;                    // a word's tag: {Fit number (20 bits), the communicator's step count + 1 (12 bits)}, comm.hip ring_tag
 constexpr long long kRingGuessTicks = 200000;          // 2 ms
 constexpr long long kRingGuessTicksApart = 20000000;   // 200 ms
 constexpr long long kRingWalkTicks = 1000000000;  // 10 s: waits for the state a walk starts from (there is no going on without it)

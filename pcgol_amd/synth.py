@@ -73,6 +73,26 @@ def c4_icp(n=1_000_000, width=10.0, base_seed=2, perm_seed=5):
                 max_iteration=20)
 
 
+def chunked_icp(n_base=1_000_000, n_target=4_500_000, width=10.0, base_seed=2, draw_seed=31, jitter=0.002,
+                far_every=100):
+    """A target several times the base's size, for Fits whose ranks hold more than one chunk of the chain
+    kernel (1 048 576 targets) each: target = T * (base points drawn with replacement + a seeded uniform jitter
+    of +-jitter per coordinate), with every far_every-th point of the order (about 1 %) a far one (+50 on every
+    axis: no partner within MaxDist).  n_target points exactly; MaxDist 0.5, MinPairs 6, Weight 0.3,
+    Threshold -1, MaxIteration 4."""
+    base = uniform_cloud(n_base, width, base_seed)
+    rng = np.random.Generator(np.random.PCG64(draw_seed))
+    n_far = n_target // far_every
+    m = n_target - n_far
+    pts = base[rng.integers(0, n_base, size=m)]
+    pts = pts + rng.uniform(-jitter, jitter, size=(m, 3)).astype(np.float32)
+    near = transform_points(icp_pose(), pts)
+    far = near[:n_far] + np.float32(50.0)
+    target = np.insert(near, np.arange(n_far) * (m // n_far), far, axis=0)
+    return dict(base=base, target=np.ascontiguousarray(target, dtype=np.float32), max_dist=0.5, min_pairs=6,
+                weight=np.full(6, 0.3, np.float32), threshold=np.full(6, -1.0, np.float32), max_iteration=4)
+
+
 def surface_cloud(n, width, seed):
     """Points on the smooth surface z = h(x, y) over [0, width)^2 with their analytic unit
     normals (input of the point-to-plane extension; the uniform cube has no surface).
@@ -161,6 +181,24 @@ def c5_tile(base, rank, world=8, width=40.0, order_seed=23, chunk=8_000_000):
     t = np.concatenate(parts)
     order = np.random.Generator(np.random.PCG64(order_seed + rank)).permutation(len(t))
     return np.ascontiguousarray(t[order])
+
+
+def c5_tiles(base, world=8, width=40.0, order_seed=23, chunk=8_000_000):
+    """[c5_tile(base, r, world, width, order_seed, chunk) for r in range(world)] in one pass over the base."""
+    pose = icp_pose()
+    parts = [[] for _ in range(world)]
+    for s in range(0, len(base), chunk):
+        t = transform_points(pose, base[s:s + chunk])
+        cell = spatial_cell(t, world, (0, 0, 0), (width,) * 3)
+        for r in range(world):
+            parts[r].append(t[cell == r])
+    out = []
+    for r in range(world):
+        t = np.concatenate(parts[r])
+        parts[r] = None
+        order = np.random.Generator(np.random.PCG64(order_seed + r)).permutation(len(t))
+        out.append(np.ascontiguousarray(t[order]))
+    return out
 
 
 def uniform_cloud_chunked(n, width, seed, chunk=8_000_000):

@@ -17,6 +17,14 @@ and octant 0 of its target (synth.c5_tile) -- condensed into digests the GPU sui
             device's parallel sums to (before round 5 that test compared them with the device's own one-wave chain)
 
 Run from the repo root:  python tests/golden/make_c5_digest.py   (about 20 min, 1 core, 5 GB)
+
+Mode "octants" writes tests/golden/c5_octants_digest.json instead: C5 as worded, the target of all
+eight ranks.  The oracle runs the three-iteration Fit (the tile Fit's config) of the concatenation of
+synth.c5_tile(base, r, 8) for r = 0..7 in rank order -- what eight ranks hold and what a sharded Fit
+with the reference's sums must reproduce bit for bit (tests/test_gpu_sharded_chunks.py):
+
+  python tests/golden/make_c5_digest.py octants   (25 min, 1 core, 5 GB: the tree 8 min, the Fit 17; the run times
+                                                   are recorded in the file, "generator_seconds")
 """
 import json
 import os
@@ -81,5 +89,40 @@ def main():
     print("done", time.time() - t0)
 
 
+def octants():
+    t0 = time.time()
+    base = synth.uniform_cloud_chunked(NB, WIDTH, 2)
+    tiles = [synth.c5_tile(base, r, 8, WIDTH) for r in range(8)]
+    sizes = [len(t) for t in tiles]
+    target = np.concatenate(tiles)
+    del tiles
+    print("clouds", len(base), sizes, time.time() - t0, flush=True)
+    tree = O.KDTree(base)
+    t_tree = time.time() - t0
+    print("oracle tree built", t_tree, flush=True)
+    w, th = np.full(6, 0.3, np.float32), np.full(6, -1.0, np.float32)
+    ft = O.icp_fit(tree, target, 0.5, 6, w, th, 3, sums_mode=0)
+    t_all = time.time() - t0
+    print("octants fit", ft["num_iteration"], t_all, flush=True)
+    out = {"_about": "the CPU oracle's three-iteration Fit (MaxIteration 3, Threshold -1, MaxDist 0.5, MinPairs 6, "
+                     "Weight 0.3, the reference's float32 sums) of config C5's whole target: the concatenation of "
+                     "synth.c5_tile(base, r, 8) for r = 0..7 in rank order, against the 64M-point base; "
+                     "generator: python tests/golden/make_c5_digest.py octants",
+           "n_base": NB, "width": WIDTH, "max_dist": 0.5, "min_pairs": 6, "weight": 0.3, "threshold": -1.0,
+           "max_iteration": 3, "octant_sizes": sizes,
+           "fit3_num_iteration": int(ft["num_iteration"]),
+           "fit3_trans_bits": [int(v) for v in np.asarray(ft["trans"], np.float32).ravel().view(np.uint32)],
+           "fit3_value_bits": int(np.float32(ft["value"]).view(np.uint32)),
+           "fit3_gradient_bits": [int(v) for v in np.asarray(ft["gradient"], np.float32).view(np.uint32)],
+           "fit3_dist_rms_bits": int(np.float32(ft["dist_rms"]).view(np.uint32)),
+           "generator_seconds": {"tree": round(t_tree), "total": round(t_all)}}
+    with open(os.path.join(ROOT, "tests", "golden", "c5_octants_digest.json"), "w") as f:
+        json.dump(out, f, indent=1)
+    print("done", time.time() - t0)
+
+
 if __name__ == "__main__":
-    main()
+    if sys.argv[1:] == ["octants"]:
+        octants()
+    else:
+        main()

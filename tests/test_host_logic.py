@@ -40,6 +40,23 @@ def test_synth_pose_matches_oracle():
     assert np.array_equal(synth.transform_points(m, pts), O.mat4_transform(m, pts))
 
 
+def test_c5_tiles_in_one_pass_equal_c5_tile():
+    base = synth.uniform_cloud_chunked(300_000, 40.0, 2, chunk=70_000)
+    tiles = synth.c5_tiles(base, 8, 40.0, chunk=70_000)
+    for r in range(8):
+        assert np.array_equal(tiles[r], synth.c5_tile(base, r, 8, 40.0, chunk=70_000))
+    assert sum(len(t) for t in tiles) == len(base)
+
+
+def test_chunked_icp_layout():
+    c = synth.chunked_icp(n_base=20_000, n_target=90_000, width=2.7)
+    t = c["target"]
+    assert t.shape == (90_000, 3) and t.dtype == np.float32 and np.array_equal(t, synth.chunked_icp(20_000, 90_000, 2.7)["target"])
+    far = t.min(axis=1) > 40.0
+    assert far.sum() == 900 and np.all(np.flatnonzero(far) == np.arange(900) * 100)   # 1 %, spread through the order
+    assert t[~far].max() < 2.7 + 0.1 and t[~far].min() > -0.1
+
+
 @pytest.mark.parametrize("world", [1, 2, 3, 8])
 def test_spatial_tiles_partition(world):
     pts = synth.uniform_cloud(10007, 10.0, 4)
