@@ -282,6 +282,50 @@ func (k *KDTree) NearestBatch(q []mat.Vec3, maxRange float32) ([]storage.Neighbo
 	return out, nil
 }
 
+// Normals estimates a unit surface normal for every point of the tree from its radius neighbourhood
+// (extension: no reference parity; include/pcgx.h, pcgx_kdtree_normals).  The result is in the tree's id
+// order: the base normals of the point-to-plane extension.  A degenerate point (fewer than minNeighbors
+// neighbours, or all of them at one place) gets a zero normal and a NaN curvature.
+func (k *KDTree) Normals(radius float32, viewpoint mat.Vec3, minNeighbors int) (normals []mat.Vec3, curvature []float32, counts []int32, err error) {
+	return k.NormalsAt(nil, radius, viewpoint, minNeighbors)
+}
+
+// NormalsAt is Normals for arbitrary query points; q == nil takes the tree's own points.
+func (k *KDTree) NormalsAt(q []mat.Vec3, radius float32, viewpoint mat.Vec3, minNeighbors int) ([]mat.Vec3, []float32, []int32, error) {
+	runtime.LockOSThread() // the error text is thread-local on the C side: call and pcgx_last_error on one OS thread
+	defer runtime.UnlockOSThread()
+	defer runtime.KeepAlive(k) // the finalizer must not free the handle while a call is in flight
+	var qp *C.float
+	n := len(q)
+	if q == nil {
+		var ln C.int64_t
+		if err := status(C.pcgx_kdtree_len(k.t.h, &ln)); err != nil {
+			return nil, nil, nil, err
+		}
+		n = int(ln)
+	} else if n > 0 {
+		qp = (*C.float)(unsafe.Pointer(&q[0]))
+	}
+	normals := make([]mat.Vec3, n)
+	curvature := make([]float32, n)
+	counts := make([]int32, n)
+	if n == 0 {
+		return normals, curvature, counts, nil
+	}
+	vp := viewpoint
+	rc := C.pcgx_kdtree_normals(k.t.h, qp, C.int64_t(n), C.float(radius), (*C.float)(unsafe.Pointer(&vp[0])),
+		C.int32_t(minNeighbors), (*C.float)(unsafe.Pointer(&normals[0])), (*C.float)(unsafe.Pointer(&curvature[0])),
+		(*C.int32_t)(unsafe.Pointer(&counts[0])))
+	runtime.KeepAlive(q)
+	runtime.KeepAlive(normals)
+	runtime.KeepAlive(curvature)
+	runtime.KeepAlive(counts)
+	if err := status(rc); err != nil {
+		return nil, nil, nil, err
+	}
+	return normals, curvature, counts, nil
+}
+
 // Nearest keeps storage.Search working for single points (one tiny batch).
 func (k *KDTree) Nearest(p mat.Vec3, maxRange float32) storage.Neighbor {
 	atomic.AddInt64(&singlePointCalls, 1)

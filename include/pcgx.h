@@ -731,6 +731,35 @@ PCGX_API pcgx_status pcgx_icp_gauss_newton_update(const pcgx_icp_params *p, floa
                                                   const float gradient[6], const float hessian36[36],
                                                   float trans16[16], int32_t *converged);
 
+/* ------------------------------------------- surface normals (extension: no reference parity)
+ * NOT in the reference: pcgol has no normal estimation.  The normals of the point-to-plane extension above, from
+ * KD-tree radius neighbourhoods.  For query q, radius r, viewpoint v (NULL: the origin) and min_neighbors (below 3
+ * counts as 3):
+ *   N(q)  = the points p of the tree with DistSq(p, q) < r*r (the reference's float32 expression): exactly the set
+ *           pcgx_kdtree_range_count counts, with or without a grid, after DeletePoint too; a tree point counts itself;
+ *   count = |N(q)| (exact);
+ *   count < min_neighbors, or all of N(q) coincide: normal (0, 0, 0), curvature NaN;
+ *   else, in float64 with d = p - q: C = sum d d^T / count - mean mean^T (mean = sum d / count), eigenvalues
+ *   l0 <= l1 <= l2; normal = unit eigenvector of l0, negated if normal . (v - q) < 0, rounded to float32;
+ *   curvature = max(l0, 0) / (l0 + l1 + l2) (PCL's surface variation).
+ * q == NULL: the tree's own points (deleted ones included), nq must equal Len(); the output is in the tree's id
+ * order, i.e. exactly the base_normals pcgx_icp_plane_session_create / pcgx_icp_plane_fit take.  curvature and
+ * counts may be NULL.  A radius that is not finite and > 0, q == NULL with nq != Len() or normals == NULL with
+ * nq > 0 is PCGX_E_INVALID.  Always computed on the device.
+ * Fed to a plane session: a degenerate point's zero normal gives its pairs r = 0 and J = 0, but they still count in
+ * the pair count and in sum w.  pcgx_icp_plane_session_create reads device normals asynchronously on its stream:
+ * the buffer must stay alive until the session's first synchronising call.
+ * Cost is the sum over the queries of the records in the cells (or tree nodes) their radius covers, as for Range:
+ * a radius far above the point spacing, or thousands of coincident queries, is paid for in full. */
+PCGX_API pcgx_status pcgx_kdtree_normals(const pcgx_kdtree *t, const float *q, int64_t nq, float radius,
+                                         const float viewpoint[3], int32_t min_neighbors,
+                                         float *normals /* [3nq] */, float *curvature /* [nq] */,
+                                         int32_t *counts /* [nq] */);
+/* Same, every array device resident, enqueued on `stream` (NULL: the library's); returns without waiting. */
+PCGX_API pcgx_status pcgx_kdtree_normals_dev(const pcgx_kdtree *t, const float *d_q, int64_t nq, float radius,
+                                             const float viewpoint[3], int32_t min_neighbors, float *d_normals,
+                                             float *d_curvature, int32_t *d_counts, void *stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -248,6 +248,8 @@ SIGNATURES = {
                                       C.POINTER(SacPlane), _vp, _vp, _vp]),
     "pcgx_sac_plane_inliers": (_i32, [_vp, C.POINTER(SacPlane), _f32, _vp, _i64, C.POINTER(_i64)]),
     "pcgx_sac_plane_is_in": (_i32, [_vp, C.POINTER(SacPlane), _vp, _f32, C.POINTER(_i32)]),
+    "pcgx_kdtree_normals": (_i32, [_vp, _vp, _i64, _f32, _vp, _i32, _vp, _vp, _vp]),
+    "pcgx_kdtree_normals_dev": (_i32, [_vp, _vp, _i64, _f32, _vp, _i32, _vp, _vp, _vp, _vp]),
 }
 
 _lib = None

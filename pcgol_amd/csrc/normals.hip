@@ -1,0 +1,417 @@
+// normals.hip -- surface normals from KD-tree radius neighbourhoods (extension: no reference parity).
+//
+// pcgol has no normal estimation; this is the input the point-to-plane extension (icp.hip, kPlane) needs for a cloud
+// that is not synthetic.  For a query q (float32), radius r, viewpoint v (include/pcgx.h, pcgx_kdtree_normals):
+//   N(q)   = every point p of the tree with DistSq(p, q) < r*r -- the reference's float32 expression, exactly the set
+//            pcgx_kdtree_range_count counts (range.hip) on every kind of handle;
+//   count  = |N(q)|; below max(min_neighbors, 3), or when all of N(q) coincide: normal 0, curvature NaN;
+//   else, in float64 with d = p - q (centred on the query: small cancellation), mean = sum d / count,
+//          C = sum d d^T / count - mean mean^T, eigenvalues l0 <= l1 <= l2:
+//          normal = unit eigenvector of l0 turned towards v, curvature = max(l0, 0) / (l0 + l1 + l2).
+// Nothing is materialised: each lane enumerates its query's neighbours exactly as the range kernels do and keeps
+// count, sum d (3), the upper triangle of sum d d^T (6) and the box of the neighbours (6 floats: "all coincide" is
+// exact, whatever the summation rounds) in registers, then solves the 3 x 3 eigenproblem in the same kernel by
+// cyclic Jacobi in double.  Three ways to enumerate, as pcgx_kdtree_range_count takes them:
+//   grid  (range_on_grid): the cells grid_cover names, rows of >= kNormFatRow records scanned by the whole wave;
+//   walk  (no grid, PCGX_RANGE_WALK=1): range_walk_nodes over the implicit tree;
+//   xwalk (a handle that has seen DeletePoint): the patched tree's walk of knn_xwalk.h.
+// Queries: the caller's (Morton-ordered from kNormPresortMin on), or the tree's own points (q == NULL) in the grid's
+// cell order, where neighbouring lanes read the same cells; results are written at the query's index / point id.
+#include <math.h>
+#include <stdlib.h>
+
+#include "knn_grid.h"
+#include "knn_xwalk.h"
+#include "range_walk.h"
+
+namespace pcgx {
+
+constexpr int kNormBlock = kRangeWalkBlock;     // one wave per workgroup: the walks' LDS frame stacks are [level][64]
+constexpr int64_t kNormPresortMin = 16384;      // caller batches from this size on run in Morton order (as Range's)
+constexpr uint32_t kNormFatRow = 4096u;         // a row of at least this many records is scanned by the whole wave
+constexpr int kJacobiSweeps = 8;                // upper bound; a sweep that finds nothing to rotate ends the solve
+
+enum NormSrc { kNormGrid = 0, kNormWalk = 1, kNormXWalk = 2 };
+
+// where the queries come from: own[pos] ({x, y, z, bits(id)}: the tree's own points in cell order), else q[perm[pos]]
+struct NormQuery {
+  const float *q;
+  const int32_t *perm;
+  const float4 *own;
+  int64_t nq;
+};
+
+struct NormOut {
+  float *normals;    // [3 nq]
+  float *curvature;  // [nq] or nullptr
+  int32_t *counts;   // [nq] or nullptr
+  float vx, vy, vz;  // viewpoint
+  int32_t min_nb;    // >= 3
+};
+
+// The moments of one neighbourhood, centred on the query.
+struct NormAcc {
+  double sx, sy, sz, sxx, sxy, sxz, syy, syz, szz;
+  int32_t n;
+  float lox, loy, loz, hix, hiy, hiz;  // box of the neighbours: empty box <=> all coincide (or none)
+
+  __device__ __forceinline__ void clear() {
+    sx = sy = sz = sxx = sxy = sxz = syy = syz = szz = 0.0;
+    n = 0;
+    lox = loy = loz = __builtin_inff();
+    hix = hiy = hiz = -__builtin_inff();
+  }
+  __device__ __forceinline__ void add(const float px, const float py, const float pz, const float qx, const float qy,
+                                      const float qz) {
+    const double dx = (double)px - (double)qx, dy = (double)py - (double)qy, dz = (double)pz - (double)qz;
+    sx += dx;
+    sy += dy;
+    sz += dz;
+    sxx = fma(dx, dx, sxx);
+    sxy = fma(dx, dy, sxy);
+    sxz = fma(dx, dz, sxz);
+    syy = fma(dy, dy, syy);
+    syz = fma(dy, dz, syz);
+    szz = fma(dz, dz, szz);
+    n++;
+    lox = fminf(lox, px);
+    loy = fminf(loy, py);
+    loz = fminf(loz, pz);
+    hix = fmaxf(hix, px);
+    hiy = fmaxf(hiy, py);
+    hiz = fmaxf(hiz, pz);
+  }
+  // the whole wave's partials into every lane (all 64 lanes must be here)
+  __device__ __forceinline__ void wave_sum() {
+#pragma unroll
+    for (int m = 1; m < 64; m <<= 1) {
+      sx += __shfl_xor(sx, m);
+      sy += __shfl_xor(sy, m);
+      sz += __shfl_xor(sz, m);
+      sxx += __shfl_xor(sxx, m);
+      sxy += __shfl_xor(sxy, m);
+      sxz += __shfl_xor(sxz, m);
+      syy += __shfl_xor(syy, m);
+      syz += __shfl_xor(syz, m);
+      szz += __shfl_xor(szz, m);
+      n += __shfl_xor(n, m);
+      lox = fminf(lox, __shfl_xor(lox, m));
+      loy = fminf(loy, __shfl_xor(loy, m));
+      loz = fminf(loz, __shfl_xor(loz, m));
+      hix = fmaxf(hix, __shfl_xor(hix, m));
+      hiy = fmaxf(hiy, __shfl_xor(hiy, m));
+      hiz = fmaxf(hiz, __shfl_xor(hiz, m));
+    }
+  }
+  __device__ __forceinline__ void merge(const NormAcc &o) {
+    sx += o.sx; sy += o.sy; sz += o.sz;
+    sxx += o.sxx; sxy += o.sxy; sxz += o.sxz; syy += o.syy; syz += o.syz; szz += o.szz;
+    n += o.n;
+    lox = fminf(lox, o.lox); loy = fminf(loy, o.loy); loz = fminf(loz, o.loz);
+    hix = fmaxf(hix, o.hix); hiy = fmaxf(hiy, o.hiy); hiz = fmaxf(hiz, o.hiz);
+  }
+};
+
+// One Jacobi rotation in the (p, q) plane of the symmetric A (Numerical Recipes' form); V collects the rotations.
+// Every index is a compile-time constant: A and V stay in registers.
+template <int p, int q>
+__device__ __forceinline__ void jacobi_rotate(double (&A)[3][3], double (&V)[3][3]) {
+  constexpr int r = 3 - p - q;
+  const double apq = A[p][q];
+  if (apq == 0.0) return;
+  // (theta^2 overflows for an apq below 1e-154 of the diagonal gap: t = 0, the rotation only drops apq)
+  const double theta = (A[q][q] - A[p][p]) / (2.0 * apq);
+  const double t = (theta >= 0.0 ? 1.0 : -1.0) / (fabs(theta) + sqrt(fma(theta, theta, 1.0)));
+  const double c = 1.0 / sqrt(fma(t, t, 1.0)), s = t * c;
+  A[p][p] -= t * apq;
+  A[q][q] += t * apq;
+  A[p][q] = A[q][p] = 0.0;
+  const double arp = A[r][p], arq = A[r][q];
+  A[r][p] = A[p][r] = c * arp - s * arq;
+  A[r][q] = A[q][r] = s * arp + c * arq;
+#pragma unroll
+  for (int k = 0; k < 3; k++) {
+    const double vkp = V[k][p], vkq = V[k][q];
+    V[k][p] = c * vkp - s * vkq;
+    V[k][q] = s * vkp + c * vkq;
+  }
+}
+
+// count, moments -> normal, curvature of query i (the contract in the file's head)
+__device__ __forceinline__ void normals_finish(const NormAcc &a, const float qx, const float qy, const float qz,
+                                               const NormOut &O, const int64_t i) {
+  float nx = 0.0f, ny = 0.0f, nz = 0.0f, cv = __builtin_nanf("");
+  const bool spread = !(a.lox == a.hix && a.loy == a.hiy && a.loz == a.hiz);
+  if (a.n >= O.min_nb && spread) {
+    const double inv = 1.0 / (double)a.n;
+    const double mx = a.sx * inv, my = a.sy * inv, mz = a.sz * inv;
+    double A[3][3], V[3][3];
+    A[0][0] = a.sxx * inv - mx * mx;
+    A[0][1] = a.sxy * inv - mx * my;
+    A[0][2] = a.sxz * inv - mx * mz;
+    A[1][1] = a.syy * inv - my * my;
+    A[1][2] = a.syz * inv - my * mz;
+    A[2][2] = a.szz * inv - mz * mz;
+    const double tr = A[0][0] + A[1][1] + A[2][2];
+    if (tr > 0.0) {
+      // scaled to unit trace: nothing under- or overflows in the rotations, eigenvectors and l0 / sum l unchanged
+      const double sc = 1.0 / tr;
+      A[0][0] *= sc; A[0][1] *= sc; A[0][2] *= sc; A[1][1] *= sc; A[1][2] *= sc; A[2][2] *= sc;
+      A[1][0] = A[0][1]; A[2][0] = A[0][2]; A[2][1] = A[1][2];
+#pragma unroll
+      for (int r = 0; r < 3; r++)
+#pragma unroll
+        for (int c = 0; c < 3; c++) V[r][c] = r == c ? 1.0 : 0.0;
+      for (int sweep = 0; sweep < kJacobiSweeps; sweep++) {
+        // an off-diagonal element below 1e-18 of the (unit) trace moves the l0 eigenvector by 1e-18 / (l1 - l0)
+        if (fabs(A[0][1]) < 1e-18) A[0][1] = A[1][0] = 0.0;
+        if (fabs(A[0][2]) < 1e-18) A[0][2] = A[2][0] = 0.0;
+        if (fabs(A[1][2]) < 1e-18) A[1][2] = A[2][1] = 0.0;
+        if (A[0][1] == 0.0 && A[0][2] == 0.0 && A[1][2] == 0.0) break;
+        jacobi_rotate<0, 1>(A, V);
+        jacobi_rotate<0, 2>(A, V);
+        jacobi_rotate<1, 2>(A, V);
+      }
+      const double e0 = A[0][0], e1 = A[1][1], e2 = A[2][2];
+      const int k = (e0 <= e1 && e0 <= e2) ? 0 : (e1 <= e2 ? 1 : 2);
+      const double l0 = k == 0 ? e0 : (k == 1 ? e1 : e2);
+      double ux = k == 0 ? V[0][0] : (k == 1 ? V[0][1] : V[0][2]);
+      double uy = k == 0 ? V[1][0] : (k == 1 ? V[1][1] : V[1][2]);
+      double uz = k == 0 ? V[2][0] : (k == 1 ? V[2][1] : V[2][2]);
+      const double len = sqrt(ux * ux + uy * uy + uz * uz);
+      ux /= len;
+      uy /= len;
+      uz /= len;
+      const double dot = ux * ((double)O.vx - (double)qx) + uy * ((double)O.vy - (double)qy) + uz * ((double)O.vz - (double)qz);
+      if (dot < 0.0) {
+        ux = -ux;
+        uy = -uy;
+        uz = -uz;
+      }
+      nx = (float)ux;
+      ny = (float)uy;
+      nz = (float)uz;
+      cv = (float)(fmax(l0, 0.0) / (e0 + e1 + e2));
+    }
+  }
+  O.normals[3 * i] = nx;
+  O.normals[3 * i + 1] = ny;
+  O.normals[3 * i + 2] = nz;
+  if (O.curvature) O.curvature[i] = cv;
+  if (O.counts) O.counts[i] = a.n;
+}
+
+// The tree's own points by id, out of the BFS slots (a handle without a grid, q == NULL)
+__global__ __launch_bounds__(256) void normals_own_points_kernel(TreeView tv, float *__restrict__ xyz) {
+  const uint32_t b = blockIdx.x * 256u + threadIdx.x;
+  if (b < 1u || b >= (1u << tv.depth)) return;
+  const uint32_t size = node_size(b, 31 - __clz((int)b), (uint32_t)tv.n + 1u);
+  if (size < 1u || size > (uint32_t)tv.n) return;  // no such node
+  const float4 nd = node_at(tv.nodes, b);
+  const uint32_t id = __float_as_uint(nd.w);
+  if (id >= (uint32_t)tv.n) return;
+  xyz[3 * (size_t)id] = nd.x;
+  xyz[3 * (size_t)id + 1] = nd.y;
+  xyz[3 * (size_t)id + 2] = nd.z;
+}
+
+template <int kSrc>
+__global__ __launch_bounds__(kNormBlock) void normals_kernel(GridView g, TreeView tv, XTreeView xv, NormQuery Q,
+                                                             float bound, NormOut O, int64_t guard) {
+  extern __shared__ uint32_t s_stack[];
+  const uint32_t n_tiles = (uint32_t)((Q.nq + kNormBlock - 1) / kNormBlock);
+  const int64_t pos = (int64_t)xcd_tile(blockIdx.x, n_tiles) * kNormBlock + threadIdx.x;
+  // (the grid path keeps every lane of the wave to the end: the fat rows are scanned and summed by all 64)
+  const bool live = pos < Q.nq;
+  if (kSrc != kNormGrid && !live) return;
+  int64_t i = 0;
+  float qx = 0.0f, qy = 0.0f, qz = 0.0f;
+  if (live) {
+    if (Q.own) {
+      const float4 r = Q.own[pos];
+      i = (int64_t)__float_as_uint(r.w);
+      qx = r.x; qy = r.y; qz = r.z;
+    } else {
+      i = Q.perm ? (int64_t)Q.perm[pos] : pos;
+      qx = Q.q[3 * i]; qy = Q.q[3 * i + 1]; qz = Q.q[3 * i + 2];
+    }
+  }
+  NormAcc acc;
+  acc.clear();
+  auto take = [&](const float4 &p) {
+    const float dx = p.x - qx, dy = p.y - qy, dz = p.z - qz;
+    const float d = (dx * dx + dy * dy) + dz * dz;  // the reference's expression (mat/vec3.go:18-20,38-40)
+    if (d < bound) acc.add(p.x, p.y, p.z, qx, qy, qz);  // kdtree.go:166,178
+  };
+  if constexpr (kSrc == kNormGrid) {
+    GridBox box = grid_cover(g, qx, qy, qz, bound);
+    if (!live) box.z1 = box.z0 - 1;
+    uint32_t fat_f0 = 0u, fat_e0 = 0u, fat_f1 = 0u, fat_e1 = 0u;
+    int nfat = 0;
+    for (int z = box.z0; z <= box.z1; z++) {
+      for (int y = box.y0; y <= box.y1; y++) {
+        const uint32_t row = ((uint32_t)z * (uint32_t)g.ny + (uint32_t)y) * (uint32_t)g.nx;
+        uint32_t f = g.start[row + (uint32_t)box.x0];
+        const uint32_t e = g.start[row + (uint32_t)box.x1 + 1u];
+        if (e > f && e - f >= kNormFatRow && nfat < 2) {  // (a third one is this lane's own work)
+          if (nfat == 0) { fat_f0 = f; fat_e0 = e; }
+          else { fat_f1 = f; fat_e1 = e; }
+          nfat++;
+          continue;
+        }
+        for (; f + 4u <= e; f += 4u) {  // four records in flight
+          const float4 p0 = g.pts[f], p1 = g.pts[f + 1u], p2 = g.pts[f + 2u], p3 = g.pts[f + 3u];
+          take(p0); take(p1); take(p2); take(p3);
+        }
+        for (; f < e; f++) take(g.pts[f]);
+      }
+    }
+    // A row of thousands of records (one site of the cloud taken thousands of times) is the whole wave's work:
+    // every lane takes every 64th record of the owner's row, the partial moments are summed over the wave.
+    if (__ballot(nfat > 0) != 0ull) {
+      const int lane = (int)(threadIdx.x & 63u);
+      for (int k = 0; k < 2; k++) {
+        unsigned long long owners = __ballot(nfat > k);
+        while (owners != 0ull) {  // uniform
+          const int owner = __builtin_ctzll(owners);
+          owners &= owners - 1ull;
+          const float ox = __shfl(qx, owner), oy = __shfl(qy, owner), oz = __shfl(qz, owner);
+          const uint32_t rf = __shfl(k == 0 ? fat_f0 : fat_f1, owner), re = __shfl(k == 0 ? fat_e0 : fat_e1, owner);
+          NormAcc part;
+          part.clear();
+          for (uint32_t r = rf + (uint32_t)lane; r < re; r += 64u) {
+            const float4 p = g.pts[r];
+            const float dx = p.x - ox, dy = p.y - oy, dz = p.z - oz;
+            const float d = (dx * dx + dy * dy) + dz * dz;
+            if (d < bound) part.add(p.x, p.y, p.z, ox, oy, oz);
+          }
+          part.wave_sum();
+          if (lane == owner) acc.merge(part);
+        }
+      }
+    }
+    if (!live) return;
+  } else if constexpr (kSrc == kNormWalk) {
+    range_walk_nodes(tv, s_stack + threadIdx.x, kNormBlock, qx, qy, qz, bound, [&](const float4 &nd, float) {
+      acc.add(nd.x, nd.y, nd.z, qx, qy, qz);  // (range_walk_nodes reports only DistSq < bound)
+    });
+  } else {
+    auto hit = [&](const float4 &nd, float) {
+      take(nd);
+      return true;
+    };
+    xwalk(xv, s_stack + threadIdx.x, kNormBlock, qx, qy, qz, guard, [&]() { return bound; }, hit, hit);
+  }
+  normals_finish(acc, qx, qy, qz, O, i);
+}
+
+}  // namespace pcgx
+
+using namespace pcgx;
+
+namespace {
+
+pcgx_status normals_check(const char *fn, const pcgx_kdtree *t, const float *q, int64_t nq, float radius,
+                          const float *normals) {
+  if (!t || nq < 0) return fail(PCGX_E_INVALID, "%s: bad argument", fn);
+  if (!(radius > 0.0f) || !(radius < __builtin_inff())) return fail(PCGX_E_INVALID, "%s: radius must be finite and > 0", fn);
+  if (!q && nq != t->n) return fail(PCGX_E_INVALID, "%s: q == NULL takes the tree's own points: nq must equal Len()", fn);
+  if (nq > 0 && !normals) return fail(PCGX_E_INVALID, "%s: NULL normals", fn);
+  return PCGX_OK;
+}
+
+// everything device resident; temporaries from ctx().arena
+pcgx_status normals_enqueue(const pcgx_kdtree *t, const float *d_q, int64_t nq, float radius, const float viewpoint[3],
+                            int32_t min_neighbors, float *d_normals, float *d_curvature, int32_t *d_counts,
+                            hipStream_t st) {
+  Arena &ar = ctx().arena;
+  PCGX_TRY(ar.begin(st));
+  const pcgx_kdtree *outer = t;
+  const bool patched = outer->n_deleted > 0;  // the reference's patched tree (knn_explicit.hip), as range_count walks it
+  XTreeView xv{};
+  if (patched) PCGX_TRY(xtree_view(outer, &xv, st));
+  const TreeView tv = t->view();
+  NormQuery Q{d_q, nullptr, nullptr, nq};
+  if (!d_q) {  // the tree's own points, Len() of them, deleted ones included
+    if (outer->grid_ok) {
+      Q.own = outer->grid.pts;  // cell order
+    } else {
+      float *xyz = nullptr;
+      if (patched) {
+        xyz = outer->d_xsrc;  // by id (xtree_view made it)
+      } else {
+        PCGX_TRY(ar.alloc_n((size_t)nq * 3, &xyz));
+        const unsigned slots = 1u << tv.depth;
+        hipLaunchKernelGGL(normals_own_points_kernel, dim3((slots + 255u) / 256u), dim3(256), 0, st, tv, xyz);
+        PCGX_HIP_TRY(hipGetLastError());
+      }
+      Q.q = xyz;
+    }
+  }
+  if (!Q.own && nq >= kNormPresortMin) {
+    int32_t *perm = nullptr;
+    PCGX_TRY(ar.alloc_n((size_t)nq, &perm));
+    PCGX_TRY(morton_order(Q.q, nq, outer->bbox_lo, outer->bbox_hi, perm, st));
+    Q.perm = perm;
+  }
+  NormOut O{d_normals, d_curvature, d_counts, 0.0f, 0.0f, 0.0f, min_neighbors < 3 ? 3 : min_neighbors};
+  if (viewpoint) {
+    O.vx = viewpoint[0];
+    O.vy = viewpoint[1];
+    O.vz = viewpoint[2];
+  }
+  const float bound = radius * radius;
+  const dim3 grid(xcd_grid((unsigned)((nq + kNormBlock - 1) / kNormBlock))), block(kNormBlock);
+  const int64_t guard = 4 * outer->n + 8;
+  if (patched) {
+    const size_t lds = (size_t)(xv.depth > 0 ? xv.depth : 1) * kNormBlock * sizeof(uint32_t);
+    hipLaunchKernelGGL(normals_kernel<kNormXWalk>, grid, block, lds, st, GridView{}, tv, xv, Q, bound, O, guard);
+  } else if (range_on_grid(t)) {
+    hipLaunchKernelGGL(normals_kernel<kNormGrid>, grid, block, 0, st, t->grid, tv, xv, Q, bound, O, guard);
+  } else {
+    hipLaunchKernelGGL(normals_kernel<kNormWalk>, grid, block, walk_stack_bytes(tv, kNormBlock), st, GridView{}, tv, xv, Q,
+                       bound, O, guard);
+  }
+  PCGX_HIP_TRY(hipGetLastError());
+  return PCGX_OK;
+}
+
+}  // namespace
+
+extern "C" pcgx_status pcgx_kdtree_normals_dev(const pcgx_kdtree *t, const float *d_q, int64_t nq, float radius,
+                                               const float viewpoint[3], int32_t min_neighbors, float *d_normals,
+                                               float *d_curvature, int32_t *d_counts, void *stream) {
+  PCGX_API_LOCK();
+  PCGX_TRY(normals_check("pcgx_kdtree_normals_dev", t, d_q, nq, radius, d_normals));
+  if (nq == 0) return PCGX_OK;
+  PCGX_TRY(ensure_init());
+  return normals_enqueue(t, d_q, nq, radius, viewpoint, min_neighbors, d_normals, d_curvature, d_counts,
+                         pick_stream(stream));
+}
+
+extern "C" pcgx_status pcgx_kdtree_normals(const pcgx_kdtree *t, const float *q, int64_t nq, float radius,
+                                           const float viewpoint[3], int32_t min_neighbors, float *normals,
+                                           float *curvature, int32_t *counts) {
+  PCGX_API_CALL();
+  PCGX_TRY(normals_check("pcgx_kdtree_normals", t, q, nq, radius, normals));
+  if (nq == 0) return PCGX_OK;
+  PCGX_TRY(ensure_init());
+  // always on the device, a single query too: the moments and the solve are the kernel's, not a host restatement
+  hipStream_t st = ctx().stream;
+  Arena &ha = ctx().host_arena;
+  PCGX_TRY(ha.begin(st));
+  float *d_q = nullptr, *d_n = nullptr, *d_c = nullptr;
+  int32_t *d_k = nullptr;
+  if (q) {
+    PCGX_TRY(ha.alloc_n((size_t)nq * 3, &d_q));
+    PCGX_TRY(staged_upload(d_q, q, (size_t)nq * 12, st));
+  }
+  PCGX_TRY(ha.alloc_n((size_t)nq * 3, &d_n));
+  if (curvature) PCGX_TRY(ha.alloc_n((size_t)nq, &d_c));
+  if (counts) PCGX_TRY(ha.alloc_n((size_t)nq, &d_k));
+  PCGX_TRY(pcgx_kdtree_normals_dev(t, d_q, nq, radius, viewpoint, min_neighbors, d_n, d_c, d_k, st));
+  PCGX_TRY(staged_download(normals, d_n, (size_t)nq * 12, st));
+  if (curvature) PCGX_TRY(staged_download(curvature, d_c, (size_t)nq * 4, st));
+  if (counts) PCGX_TRY(staged_download(counts, d_k, (size_t)nq * 4, st));
+  return PCGX_OK;
+}

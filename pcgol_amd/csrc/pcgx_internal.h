@@ -329,6 +329,8 @@ pcgx_status minmax_to_host(const void *d_data, int64_t n, int32_t stride, int32_
 // [lo, hi]).  Uses the arena.
 pcgx_status morton_order(const float *d_q, int64_t n, const float lo[3], const float hi[3], int32_t *d_perm,
                          hipStream_t st);
+// range.hip: Range / range-count batches take the handle's grid (else the tree walk); PCGX_RANGE_WALK=1 forces the walk
+bool range_on_grid(const pcgx_kdtree *t);
 
 
 // icp.hip / strict.hip

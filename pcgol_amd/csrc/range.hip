@@ -304,7 +304,7 @@ __global__ __launch_bounds__(256) void range_widen_check_kernel(const uint32_t *
 
 namespace pcgx {
 // PCGX_RANGE_WALK=1: the tree walk even where the handle has a grid (measurements, tests of the walk)
-static bool range_on_grid(const pcgx_kdtree *t) {
+bool range_on_grid(const pcgx_kdtree *t) {
   const char *e = getenv("PCGX_RANGE_WALK");  // (read per call: the tests switch between the two)
   return t->grid_ok && !(e && *e && *e != '0');
 }

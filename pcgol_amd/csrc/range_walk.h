@@ -6,8 +6,9 @@
 //   unwind: skip the pivot and the far side if fp*fp > maxRange^2        (:173-177)
 //           hit the pivot if dsq < maxRange^2                            (:178-181)
 //           recurse into the other child                                 (:182-195)
-// Hits are reported in the reference's discovery order.  Used by range.hip (KDTree.Range) and
-// segment.hip (region growing: the same neighbourhoods feed a union-find).
+// Hits are reported in the reference's discovery order.  Used by range.hip (KDTree.Range),
+// segment.hip (region growing: the same neighbourhoods feed a union-find) and normals.hip (the
+// neighbourhood moments of normal estimation).
 #pragma once
 #include "knn_walk.h"
 
@@ -16,11 +17,11 @@ namespace pcgx {
 constexpr int kRangeWalkBlock = 64;  // threads per block of a kernel using range_walk
 
 // stk: this lane's frame column in LDS ([level][stk_stride], walk_stack_bytes(tv, block)).
-// on_hit(id, dist_sq) is called for every point with dist_sq < bound, in discovery order.
+// on_node(node {x, y, z, bits(id)}, dist_sq) is called for every point with dist_sq < bound, in discovery order.
 template <class Hit>
-__device__ __forceinline__ void range_walk(const TreeView &tv, uint32_t *__restrict__ stk, const int stk_stride,
-                                           const float qx, const float qy, const float qz, const float bound,
-                                           Hit &&on_hit) {
+__device__ __forceinline__ void range_walk_nodes(const TreeView &tv, uint32_t *__restrict__ stk, const int stk_stride,
+                                                 const float qx, const float qy, const float qz, const float bound,
+                                                 Hit &&on_node) {
   const uint32_t np1 = (uint32_t)tv.n + 1u;
   uint32_t b = 1;
   int32_t n = tv.n, sp = 0;
@@ -68,8 +69,17 @@ __device__ __forceinline__ void range_walk(const TreeView &tv, uint32_t *__restr
         desc = true;
       }
     }
-    if (hit) on_hit(__float_as_int(nd.w), d);
+    if (hit) on_node(nd, d);
   }
+}
+
+// The same with on_hit(id, dist_sq).
+template <class Hit>
+__device__ __forceinline__ void range_walk(const TreeView &tv, uint32_t *__restrict__ stk, const int stk_stride,
+                                           const float qx, const float qy, const float qz, const float bound,
+                                           Hit &&on_hit) {
+  range_walk_nodes(tv, stk, stk_stride, qx, qy, qz, bound,
+                   [&](const float4 &nd, float d) { on_hit(__float_as_int(nd.w), d); });
 }
 
 }  // namespace pcgx

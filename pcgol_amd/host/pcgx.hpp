@@ -144,6 +144,26 @@ class KDTree {  // pc/storage/kdtree/kdtree.go:14-23
     check(rc);
   }
   int32_t MaxDepth() const { int32_t d; check(pcgx_kdtree_max_depth(h_.get(), &d)); return d; }
+  // Surface normals from radius neighbourhoods (extension: no reference parity; include/pcgx.h,
+  // pcgx_kdtree_normals).  An empty `queries` takes the tree's own points: the result is in id order, the
+  // baseNormals PointToPlaneICP::Fit takes.  Degenerate points: normal {0, 0, 0}, curvature NaN.
+  struct NormalsResult {
+    std::vector<Vec3> normals;
+    std::vector<float> curvature;
+    std::vector<int32_t> counts;
+  };
+  NormalsResult Normals(float radius, const Vec3 &viewpoint = Vec3{0.0f, 0.0f, 0.0f}, int32_t minNeighbors = 3,
+                        const std::vector<Vec3> &queries = {}) const {
+    const bool own = queries.empty();
+    const int64_t n = own ? Len() : (int64_t)queries.size();
+    NormalsResult r;
+    r.normals.resize((size_t)n);
+    r.curvature.resize((size_t)n);
+    r.counts.resize((size_t)n);
+    check(pcgx_kdtree_normals(h_.get(), own ? nullptr : queries[0].data(), n, radius, viewpoint.data(), minNeighbors,
+                              n ? r.normals[0].data() : nullptr, r.curvature.data(), r.counts.data()));
+    return r;
+  }
   const pcgx_kdtree *handle() const { return h_.get(); }
 
  private:

@@ -214,8 +214,8 @@ class IcpSession:
     def __init__(self, base, target, MaxDist, MinPairs=0, Weight=None, Threshold=None, MaxIteration=0,
                  d_sums10=0, target_on_device=False, nt=None, BaseNormals=None, Damping=0.0, WeightFn=None,
                  SumsMode=SumsReference):
-        """BaseNormals (unit normals per base point, id order; a device address when
-        target_on_device) selects the point-to-plane / Gauss-Newton extension: the exchange
+        """BaseNormals (unit normals per base point, id order; a device address or a tensor when
+        target_on_device, e.g. KDTree.NormalsDev's output) selects the point-to-plane / Gauss-Newton extension: the exchange
         vector then has 30 doubles (d_sums10 must point to 30).  SumsMode: PCGX_SUMS_* (default: the
         reference's sequential float32 sums; a session stepped through an exchange forms float64 sums)."""
         w = np.zeros(6, np.float32) if Weight is None else Weight
@@ -234,7 +234,10 @@ class IcpSession:
         sums = L.ptr(int(d_sums10)) if d_sums10 else None
         if self.plane:
             if target_on_device:
-                nptr = L.ptr(int(BaseNormals))
+                # (a device buffer: an address, or an object with data_ptr() -- held here, because session
+                # creation reads the normals asynchronously, after this call has returned)
+                self._n = BaseNormals
+                nptr = L.ptr(int(BaseNormals.data_ptr()) if hasattr(BaseNormals, "data_ptr") else int(BaseNormals))
             else:
                 self._n = L.f32c(BaseNormals).reshape(-1, 3)
                 if len(self._n) != base.Len():

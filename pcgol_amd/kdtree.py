@@ -1,5 +1,6 @@
 """pc/storage/kdtree mirror: KDTree on the GPU behind the storage.Search shape
-(pc/storage/search.go:13-17): Vec3At / Len / Nearest, plus batched NearestBatch."""
+(pc/storage/search.go:13-17): Vec3At / Len / Nearest, plus batched NearestBatch, and surface
+normals (Normals, an extension with no reference counterpart)."""
 import ctypes as C
 
 import numpy as np
@@ -138,6 +139,36 @@ class KDTree:
         dsq = np.empty(total, np.float32)
         L.check(L.lib().pcgx_kdtree_range_fill(self._h, L.ptr(q), n, maxRange, L.ptr(offs), L.ptr(ids), L.ptr(dsq)))
         return offs, ids, dsq
+
+    # -- extension (no reference parity): surface normals for the point-to-plane evaluator
+    def Normals(self, radius, Viewpoint=(0.0, 0.0, 0.0), MinNeighbors=3, Queries=None):
+        """Unit normal of the radius neighbourhood (DistSq < radius^2, Range's set) of every query ->
+        (normals (n,3) float32, curvature (n,) float32, counts (n,) int32).  Queries None: the tree's own
+        points, in id order (the BaseNormals of PointToPlaneEvaluator).  Fewer than max(MinNeighbors, 3)
+        neighbours, or all of them at one place: normal 0, curvature NaN (include/pcgx.h)."""
+        q = None if Queries is None else L.f32c(Queries).reshape(-1, 3)
+        n = self.Len() if q is None else len(q)
+        vp = L.f32c(Viewpoint).reshape(3)
+        normals = np.empty((n, 3), np.float32)
+        curvature = np.empty(n, np.float32)
+        counts = np.empty(n, np.int32)
+        L.check(L.lib().pcgx_kdtree_normals(self._h, L.ptr(q), n, float(radius), L.ptr(vp), int(MinNeighbors),
+                                            L.ptr(normals), L.ptr(curvature), L.ptr(counts)))
+        return normals, curvature, counts
+
+    def NormalsDev(self, radius, d_normals, d_curvature=0, d_counts=0, d_q=0, nq=None, Viewpoint=(0.0, 0.0, 0.0),
+                   MinNeighbors=3, stream=0):
+        """Device-resident Normals: raw device addresses (e.g. torch .data_ptr()); d_q 0 takes the tree's own
+        points (nq = Len()).  Enqueued on `stream`, returns without waiting."""
+        if nq is None:
+            if d_q:
+                raise ValueError("nq is required with d_q")
+            nq = self.Len()
+        vp = L.f32c(Viewpoint).reshape(3)
+        L.check(L.lib().pcgx_kdtree_normals_dev(
+            self._h, L.ptr(int(d_q)) if d_q else None, int(nq), float(radius), L.ptr(vp), int(MinNeighbors),
+            L.ptr(int(d_normals)), L.ptr(int(d_curvature)) if d_curvature else None,
+            L.ptr(int(d_counts)) if d_counts else None, L.ptr(stream) if stream else None))
 
     def NearestBatchDev(self, d_q, nq, maxRange, d_ids, d_dsq, presort=True, stream=0):
         """Device-resident variant: raw device addresses (e.g. torch .data_ptr())."""
