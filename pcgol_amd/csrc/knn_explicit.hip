@@ -62,38 +62,6 @@ __global__ __launch_bounds__(kXBlock) void xnearest_kernel(XTreeView xv, const f
   out_dsq[i] = best_d;
 }
 
-// same contract as range_kernel (range.hip)
-template <bool kFill>
-__global__ __launch_bounds__(kXBlock) void xrange_kernel(XTreeView xv, const float *__restrict__ q,
-                                                         const int32_t *__restrict__ perm, int64_t nq, float bound,
-                                                         int64_t *__restrict__ counts,
-                                                         const int64_t *__restrict__ offsets, int64_t total,
-                                                         int32_t *__restrict__ out_id, uint32_t *__restrict__ out_key,
-                                                         uint32_t *__restrict__ out_query, int64_t guard) {
-  extern __shared__ uint32_t s_stack[];
-  const int64_t pos = (int64_t)blockIdx.x * kXBlock + threadIdx.x;
-  if (pos >= nq) return;
-  const int64_t i = perm ? (int64_t)perm[pos] : pos;
-  const float qx = q[3 * i], qy = q[3 * i + 1], qz = q[3 * i + 2];
-  int64_t found = 0;
-  const int64_t out0 = kFill ? offsets[i] : 0;
-  const int64_t cap = kFill ? offsets[i + 1] - out0 : 0;
-  const bool slice_ok = kFill && out0 >= 0 && cap >= 0 && out0 + cap <= total;
-  auto hit = [&](const float4 &nd, float d) {
-    if (d < bound) {  // kdtree.go:166-169,178-181
-      if (kFill && slice_ok && found < cap) {
-        out_id[out0 + found] = __float_as_int(nd.w);
-        out_key[out0 + found] = __float_as_uint(d);
-        out_query[out0 + found] = (uint32_t)i;
-      }
-      ++found;
-    }
-    return true;
-  };
-  xwalk(xv, s_stack + threadIdx.x, kXBlock, qx, qy, qz, guard, [&]() { return bound; }, hit, hit);
-  if (!kFill) counts[i] = found;
-}
-
 // The device copy out of the host mirror as it is ({id, child0, child1, dim} per node, uploaded in one piece) and the
 // cloud's points by id (uploaded once per handle): node k's point record and links.  (The host used to put both arrays
 // together point by point and copy them from pageable memory: 8-14 ms per refresh at 1M nodes.)
@@ -529,25 +497,6 @@ pcgx_status xtree_launch_nearest(const pcgx_kdtree *t, const float *d_q, const i
   return PCGX_OK;
 }
 
-pcgx_status xtree_launch_range(const pcgx_kdtree *t, bool fill, const float *d_q, const int32_t *d_perm, int64_t nq,
-                               float bound, int64_t *d_counts, const int64_t *d_offsets, int64_t total, int32_t *d_id,
-                               uint32_t *d_key, uint32_t *d_query, hipStream_t st) {
-  if (nq == 0) return PCGX_OK;
-  XTreeView xv;
-  PCGX_TRY(xtree_view(t, &xv, st));
-  const size_t lds = (size_t)(xv.depth > 0 ? xv.depth : 1) * kXBlock * sizeof(uint32_t);
-  const unsigned blocks = (unsigned)((nq + kXBlock - 1) / kXBlock);
-  const int64_t guard = 4 * t->n + 8;
-  if (fill)
-    hipLaunchKernelGGL(xrange_kernel<true>, dim3(blocks), dim3(kXBlock), lds, st, xv, d_q, d_perm, nq, bound, d_counts,
-                       d_offsets, total, d_id, d_key, d_query, guard);
-  else
-    hipLaunchKernelGGL(xrange_kernel<false>, dim3(blocks), dim3(kXBlock), lds, st, xv, d_q, d_perm, nq, bound, d_counts,
-                       d_offsets, total, d_id, d_key, d_query, guard);
-  PCGX_HIP_TRY(hipGetLastError());
-  return PCGX_OK;
-}
-
 // ---- a few points at a time: the same walk on the host -------------------------------------------------------------
 // storage.Search.Nearest / Range for ONE point (pc/storage/search.go:13-17; callers that loop: correspondence.go:25-36,
 // regiongrowing.go:26,47) used to be a blocking GPU call each -- upload, launch, two PCIe round trips: 57-74 us against
@@ -573,8 +522,7 @@ inline void host_xwalk(const pcgx_kdtree *t, const float qv[3], Bound &&bound, L
       const pcgx_kdtree::XNode &nd = X[cur];
       const float *p = P + 3 * (size_t)nd.id;
       if (nd.c0 < 0 && nd.c1 < 0) {
-        const float dx = p[0] - qv[0], dy = p[1] - qv[1], dz = p[2] - qv[2];
-        if (!on_leaf(nd.id, (dx * dx + dy * dy) + dz * dz)) return;
+        if (!on_leaf(nd.id, ref_dist_sq(p[0], p[1], p[2], qv[0], qv[1], qv[2]))) return;
         desc = false;
         continue;
       }
@@ -590,8 +538,7 @@ inline void host_xwalk(const pcgx_kdtree *t, const float qv[3], Bound &&bound, L
       const float *p = P + 3 * (size_t)nd.id;
       const float fp = qv[nd.dim] - p[nd.dim];  // p[dim] - pivot[dim]
       if (fp * fp > bound()) continue;           // kdtree.go:111-115 / :173-177
-      const float dx = p[0] - qv[0], dy = p[1] - qv[1], dz = p[2] - qv[2];
-      if (!on_pivot(nd.id, (dx * dx + dy * dy) + dz * dz)) return;
+      if (!on_pivot(nd.id, ref_dist_sq(p[0], p[1], p[2], qv[0], qv[1], qv[2]))) return;
       const int32_t other = side ? nd.c0 : nd.c1;  // the child that is not on the stack (:124-132)
       if (other >= 0) {
         cur = other;

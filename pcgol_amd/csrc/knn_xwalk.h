@@ -3,6 +3,7 @@
 // (rangeImpl), :199-222 (searchLeafNode).
 #pragma once
 #include "knn_walk.h"
+#include "range_enum.h"
 
 namespace pcgx {
 
@@ -31,8 +32,7 @@ __device__ __forceinline__ void xwalk(const XTreeView &xv, uint32_t *__restrict_
       const int4 lk = xv.links[cur];
       const float4 nd = xv.pts[cur];
       if (lk.x < 0 && lk.y < 0) {  // no children: the leaf of this descent
-        const float dx = nd.x - qx, dy = nd.y - qy, dz = nd.z - qz;
-        if (!on_leaf(nd, (dx * dx + dy * dy) + dz * dz)) return;
+        if (!on_leaf(nd, ref_dist_sq(nd.x, nd.y, nd.z, qx, qy, qz))) return;
         desc = false;
         continue;
       }
@@ -51,8 +51,7 @@ __device__ __forceinline__ void xwalk(const XTreeView &xv, uint32_t *__restrict_
       const float4 nd = xv.pts[n];
       const float fp = sel3(lk.z, qx, qy, qz) - sel3(lk.z, nd.x, nd.y, nd.z);  // p[dim] - pivot[dim]
       if (fp * fp > bound()) continue;  // kdtree.go:111-115 / :173-177
-      const float dx = nd.x - qx, dy = nd.y - qy, dz = nd.z - qz;
-      if (!on_pivot(nd, (dx * dx + dy * dy) + dz * dz)) return;
+      if (!on_pivot(nd, ref_dist_sq(nd.x, nd.y, nd.z, qx, qy, qz))) return;
       const int32_t other = side ? lk.x : lk.y;  // the child that is not on the stack (:124-132)
       if (other >= 0) {
         cur = other;

@@ -11,10 +11,10 @@
 // Nothing is materialised: each lane enumerates its query's neighbours exactly as the range kernels do and keeps
 // count, sum d (3), the upper triangle of sum d d^T (6) and the box of the neighbours (6 floats: "all coincide" is
 // exact, whatever the summation rounds) in registers, then solves the 3 x 3 eigenproblem in the same kernel by
-// cyclic Jacobi in double.  Three ways to enumerate, as pcgx_kdtree_range_count takes them:
-//   grid  (range_on_grid): the cells grid_cover names, rows of >= kNormFatRow records scanned by the whole wave;
-//   walk  (no grid, PCGX_RANGE_WALK=1): range_walk_nodes over the implicit tree;
-//   xwalk (a handle that has seen DeletePoint): the patched tree's walk of knn_xwalk.h.
+// cyclic Jacobi in double.  Three ways to enumerate, as pcgx_kdtree_range_count takes them (range_source, range_enum.h):
+//   grid  (kRangeGrid): grid_radius_scan over the cells grid_cover names, fat rows scanned by the whole wave;
+//   walk  (kRangeWalk: no grid, PCGX_RANGE_WALK=1): range_walk_nodes over the implicit tree;
+//   xwalk (kRangeXWalk: a handle that has seen DeletePoint): the patched tree's walk of knn_xwalk.h.
 // Queries: the caller's (Morton-ordered from kNormPresortMin on), or the tree's own points (q == NULL) in the grid's
 // cell order, where neighbouring lanes read the same cells; results are written at the query's index / point id.
 #include <math.h>
@@ -28,10 +28,7 @@ namespace pcgx {
 
 constexpr int kNormBlock = kRangeWalkBlock;     // one wave per workgroup: the walks' LDS frame stacks are [level][64]
 constexpr int64_t kNormPresortMin = 16384;      // caller batches from this size on run in Morton order (as Range's)
-constexpr uint32_t kNormFatRow = 4096u;         // a row of at least this many records is scanned by the whole wave
 constexpr int kJacobiSweeps = 8;                // upper bound; a sweep that finds nothing to rotate ends the solve
-
-enum NormSrc { kNormGrid = 0, kNormWalk = 1, kNormXWalk = 2 };
 
 // where the queries come from: own[pos] ({x, y, z, bits(id)}: the tree's own points in cell order), else q[perm[pos]]
 struct NormQuery {
@@ -223,7 +220,7 @@ __global__ __launch_bounds__(kNormBlock) void normals_kernel(GridView g, TreeVie
   const int64_t pos = (int64_t)xcd_tile(blockIdx.x, n_tiles) * kNormBlock + threadIdx.x;
   // (the grid path keeps every lane of the wave to the end: the fat rows are scanned and summed by all 64)
   const bool live = pos < Q.nq;
-  if (kSrc != kNormGrid && !live) return;
+  if (kSrc != kRangeGrid && !live) return;
   int64_t i = 0;
   float qx = 0.0f, qy = 0.0f, qz = 0.0f;
   if (live) {
@@ -239,59 +236,24 @@ __global__ __launch_bounds__(kNormBlock) void normals_kernel(GridView g, TreeVie
   NormAcc acc;
   acc.clear();
   auto take = [&](const float4 &p) {
-    const float dx = p.x - qx, dy = p.y - qy, dz = p.z - qz;
-    const float d = (dx * dx + dy * dy) + dz * dz;  // the reference's expression (mat/vec3.go:18-20,38-40)
-    if (d < bound) acc.add(p.x, p.y, p.z, qx, qy, qz);  // kdtree.go:166,178
+    if (ref_dist_sq(p.x, p.y, p.z, qx, qy, qz) < bound) acc.add(p.x, p.y, p.z, qx, qy, qz);  // kdtree.go:166,178
   };
-  if constexpr (kSrc == kNormGrid) {
-    GridBox box = grid_cover(g, qx, qy, qz, bound);
-    if (!live) box.z1 = box.z0 - 1;
-    uint32_t fat_f0 = 0u, fat_e0 = 0u, fat_f1 = 0u, fat_e1 = 0u;
-    int nfat = 0;
-    for (int z = box.z0; z <= box.z1; z++) {
-      for (int y = box.y0; y <= box.y1; y++) {
-        const uint32_t row = ((uint32_t)z * (uint32_t)g.ny + (uint32_t)y) * (uint32_t)g.nx;
-        uint32_t f = g.start[row + (uint32_t)box.x0];
-        const uint32_t e = g.start[row + (uint32_t)box.x1 + 1u];
-        if (e > f && e - f >= kNormFatRow && nfat < 2) {  // (a third one is this lane's own work)
-          if (nfat == 0) { fat_f0 = f; fat_e0 = e; }
-          else { fat_f1 = f; fat_e1 = e; }
-          nfat++;
-          continue;
-        }
-        for (; f + 4u <= e; f += 4u) {  // four records in flight
-          const float4 p0 = g.pts[f], p1 = g.pts[f + 1u], p2 = g.pts[f + 2u], p3 = g.pts[f + 3u];
-          take(p0); take(p1); take(p2); take(p3);
-        }
-        for (; f < e; f++) take(g.pts[f]);
+  if constexpr (kSrc == kRangeGrid) {
+    // a fat row (one site of the cloud taken thousands of times) is the whole wave's work: every lane takes every 64th
+    // record of the owner's row, the partial moments are summed over the wave
+    const int lane = (int)(threadIdx.x & 63u);
+    grid_radius_scan(g, qx, qy, qz, bound, live, take, [&](int owner, uint32_t rf, uint32_t re, float ox, float oy, float oz) {
+      NormAcc part;
+      part.clear();
+      for (uint32_t r = rf + (uint32_t)lane; r < re; r += 64u) {
+        const float4 p = g.pts[r];
+        if (ref_dist_sq(p.x, p.y, p.z, ox, oy, oz) < bound) part.add(p.x, p.y, p.z, ox, oy, oz);
       }
-    }
-    // A row of thousands of records (one site of the cloud taken thousands of times) is the whole wave's work:
-    // every lane takes every 64th record of the owner's row, the partial moments are summed over the wave.
-    if (__ballot(nfat > 0) != 0ull) {
-      const int lane = (int)(threadIdx.x & 63u);
-      for (int k = 0; k < 2; k++) {
-        unsigned long long owners = __ballot(nfat > k);
-        while (owners != 0ull) {  // uniform
-          const int owner = __builtin_ctzll(owners);
-          owners &= owners - 1ull;
-          const float ox = __shfl(qx, owner), oy = __shfl(qy, owner), oz = __shfl(qz, owner);
-          const uint32_t rf = __shfl(k == 0 ? fat_f0 : fat_f1, owner), re = __shfl(k == 0 ? fat_e0 : fat_e1, owner);
-          NormAcc part;
-          part.clear();
-          for (uint32_t r = rf + (uint32_t)lane; r < re; r += 64u) {
-            const float4 p = g.pts[r];
-            const float dx = p.x - ox, dy = p.y - oy, dz = p.z - oz;
-            const float d = (dx * dx + dy * dy) + dz * dz;
-            if (d < bound) part.add(p.x, p.y, p.z, ox, oy, oz);
-          }
-          part.wave_sum();
-          if (lane == owner) acc.merge(part);
-        }
-      }
-    }
+      part.wave_sum();
+      if (lane == owner) acc.merge(part);
+    });
     if (!live) return;
-  } else if constexpr (kSrc == kNormWalk) {
+  } else if constexpr (kSrc == kRangeWalk) {
     range_walk_nodes(tv, s_stack + threadIdx.x, kNormBlock, qx, qy, qz, bound, [&](const float4 &nd, float) {
       acc.add(nd.x, nd.y, nd.z, qx, qy, qz);  // (range_walk_nodes reports only DistSq < bound)
     });
@@ -326,19 +288,18 @@ pcgx_status normals_enqueue(const pcgx_kdtree *t, const float *d_q, int64_t nq, 
                             hipStream_t st) {
   Arena &ar = ctx().arena;
   PCGX_TRY(ar.begin(st));
-  const pcgx_kdtree *outer = t;
-  const bool patched = outer->n_deleted > 0;  // the reference's patched tree (knn_explicit.hip), as range_count walks it
+  const RangeSrc src = range_source(t);  // as pcgx_kdtree_range_count takes it
   XTreeView xv{};
-  if (patched) PCGX_TRY(xtree_view(outer, &xv, st));
+  if (src == kRangeXWalk) PCGX_TRY(xtree_view(t, &xv, st));
   const TreeView tv = t->view();
   NormQuery Q{d_q, nullptr, nullptr, nq};
   if (!d_q) {  // the tree's own points, Len() of them, deleted ones included
-    if (outer->grid_ok) {
-      Q.own = outer->grid.pts;  // cell order
+    if (t->grid_ok) {
+      Q.own = t->grid.pts;  // cell order
     } else {
       float *xyz = nullptr;
-      if (patched) {
-        xyz = outer->d_xsrc;  // by id (xtree_view made it)
+      if (src == kRangeXWalk) {
+        xyz = t->d_xsrc;  // by id (xtree_view made it)
       } else {
         PCGX_TRY(ar.alloc_n((size_t)nq * 3, &xyz));
         const unsigned slots = 1u << tv.depth;
@@ -351,7 +312,7 @@ pcgx_status normals_enqueue(const pcgx_kdtree *t, const float *d_q, int64_t nq, 
   if (!Q.own && nq >= kNormPresortMin) {
     int32_t *perm = nullptr;
     PCGX_TRY(ar.alloc_n((size_t)nq, &perm));
-    PCGX_TRY(morton_order(Q.q, nq, outer->bbox_lo, outer->bbox_hi, perm, st));
+    PCGX_TRY(morton_order(Q.q, nq, t->bbox_lo, t->bbox_hi, perm, st));
     Q.perm = perm;
   }
   NormOut O{d_normals, d_curvature, d_counts, 0.0f, 0.0f, 0.0f, min_neighbors < 3 ? 3 : min_neighbors};
@@ -362,14 +323,14 @@ pcgx_status normals_enqueue(const pcgx_kdtree *t, const float *d_q, int64_t nq, 
   }
   const float bound = radius * radius;
   const dim3 grid(xcd_grid((unsigned)((nq + kNormBlock - 1) / kNormBlock))), block(kNormBlock);
-  const int64_t guard = 4 * outer->n + 8;
-  if (patched) {
+  const int64_t guard = 4 * t->n + 8;
+  if (src == kRangeXWalk) {
     const size_t lds = (size_t)(xv.depth > 0 ? xv.depth : 1) * kNormBlock * sizeof(uint32_t);
-    hipLaunchKernelGGL(normals_kernel<kNormXWalk>, grid, block, lds, st, GridView{}, tv, xv, Q, bound, O, guard);
-  } else if (range_on_grid(t)) {
-    hipLaunchKernelGGL(normals_kernel<kNormGrid>, grid, block, 0, st, t->grid, tv, xv, Q, bound, O, guard);
+    hipLaunchKernelGGL(normals_kernel<kRangeXWalk>, grid, block, lds, st, GridView{}, tv, xv, Q, bound, O, guard);
+  } else if (src == kRangeGrid) {
+    hipLaunchKernelGGL(normals_kernel<kRangeGrid>, grid, block, 0, st, t->grid, tv, xv, Q, bound, O, guard);
   } else {
-    hipLaunchKernelGGL(normals_kernel<kNormWalk>, grid, block, walk_stack_bytes(tv, kNormBlock), st, GridView{}, tv, xv, Q,
+    hipLaunchKernelGGL(normals_kernel<kRangeWalk>, grid, block, walk_stack_bytes(tv, kNormBlock), st, GridView{}, tv, xv, Q,
                        bound, O, guard);
   }
   PCGX_HIP_TRY(hipGetLastError());

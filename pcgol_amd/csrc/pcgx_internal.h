@@ -256,9 +256,6 @@ bool xtree_host_range(const pcgx_kdtree *t, const float *q, int64_t nq, float ma
                       int64_t *ids, float *dist_sq);
 pcgx_status xtree_launch_nearest(const pcgx_kdtree *t, const float *d_q, const int32_t *d_perm, int64_t nq,
                                  float max_range_sq, float min_dist_sq, int32_t *d_ids, float *d_dsq, hipStream_t st);
-pcgx_status xtree_launch_range(const pcgx_kdtree *t, bool fill, const float *d_q, const int32_t *d_perm, int64_t nq,
-                               float bound, int64_t *d_counts, const int64_t *d_offsets, int64_t total, int32_t *d_id,
-                               uint32_t *d_key, uint32_t *d_query, hipStream_t st);
 namespace pcgx {
 
 // knn.hip
@@ -329,9 +326,6 @@ pcgx_status minmax_to_host(const void *d_data, int64_t n, int32_t stride, int32_
 // [lo, hi]).  Uses the arena.
 pcgx_status morton_order(const float *d_q, int64_t n, const float lo[3], const float hi[3], int32_t *d_perm,
                          hipStream_t st);
-// range.hip: Range / range-count batches take the handle's grid (else the tree walk); PCGX_RANGE_WALK=1 forces the walk
-bool range_on_grid(const pcgx_kdtree *t);
-
 
 // icp.hip / strict.hip
 // Loop state kept in device memory so that a whole Fit can be enqueued without

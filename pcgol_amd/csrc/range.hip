@@ -17,6 +17,8 @@
 // fetches per query.  The ORDER the walk would have found them in matters only among equal DistSq of one query;
 // those runs are put into it afterwards (range_tie_*_kernel: the walk is an in-order traversal that takes the
 // query's side of every node first, so a point's place in it follows from its node's BFS index).
+// Which of the three enumerations a handle takes -- the grid, the implicit tree's walk (no grid, or
+// PCGX_RANGE_WALK=1), the patched tree's walk after DeletePoint (knn_explicit.hip) -- is range_source's (range_enum.h).
 //
 // Two entry points because the result length is data dependent: pcgx_kdtree_range_count
 // (walk, count) and pcgx_kdtree_range_fill (walk again, write at the caller's offsets, then
@@ -28,7 +30,7 @@
 #include <mutex>
 #include <vector>
 
-#include "knn_grid.h"
+#include "knn_xwalk.h"
 #include "range_walk.h"
 
 namespace pcgx {
@@ -38,22 +40,22 @@ constexpr int64_t kRangePresortMin = 16384;  // batches from this size on are wa
 
 // kFill == false: counts[i] = number of neighbours.  kFill == true: neighbours of query i are
 // written from offsets[i] in discovery order: {point id, DistSq bits, query index}.
-template <bool kFill>
-__global__ __launch_bounds__(kRangeBlock) void range_kernel(TreeView tv, const float *__restrict__ q,
-                                                            const int32_t *__restrict__ perm, int64_t nq,
-                                                            float bound, int64_t *__restrict__ counts,
-                                                            const int64_t *__restrict__ offsets, int64_t total,
-                                                            int32_t *__restrict__ out_id,
-                                                            uint32_t *__restrict__ out_key,
-                                                            uint32_t *__restrict__ out_query) {
+// kSrc == kRangeWalk: the walk of the implicit tree (range_walk.h); kRangeXWalk: the walk of the patched tree of a
+// handle that has seen DeletePoint (knn_xwalk.h, at most `guard` steps), 256 lanes a block, in launch order.
+template <int kSrc, bool kFill>
+__global__ __launch_bounds__(kSrc == kRangeXWalk ? kXBlock : kRangeBlock) void range_kernel(
+    TreeView tv, XTreeView xv, const float *__restrict__ q, const int32_t *__restrict__ perm, int64_t nq, float bound,
+    int64_t *__restrict__ counts, const int64_t *__restrict__ offsets, int64_t total, int32_t *__restrict__ out_id,
+    uint32_t *__restrict__ out_key, uint32_t *__restrict__ out_query, int64_t guard) {
   extern __shared__ uint32_t s_stack[];
-  // launch positions are in Morton order when `perm` is given: an XCD takes a contiguous eighth of
+  constexpr int kBlock = kSrc == kRangeXWalk ? kXBlock : kRangeBlock;
+  // launch positions are in Morton order when `perm` is given: on the implicit tree an XCD takes a contiguous eighth of
   // them, so its L2 holds that region's part of the tree (pcgx_internal.h, xcd_tile).  (Two queries
   // per lane with their walks interleaved -- two node fetches in flight -- measured 1.4x SLOWER at
   // 200k queries: half as many waves, each with twice the instructions; the walk is bound by how
   // fast one wave issues its dependent instructions, and there are too few waves as it is.)
-  const uint32_t n_tiles = (uint32_t)((nq + kRangeBlock - 1) / kRangeBlock);
-  const int64_t pos = (int64_t)xcd_tile(blockIdx.x, n_tiles) * kRangeBlock + threadIdx.x;
+  const uint32_t tile = kSrc == kRangeWalk ? xcd_tile(blockIdx.x, (uint32_t)((nq + kBlock - 1) / kBlock)) : blockIdx.x;
+  const int64_t pos = (int64_t)tile * kBlock + threadIdx.x;
   if (pos >= nq) return;
   // perm (optional): launch position -> query index (Morton order: the lanes of a wave walk
   // neighbouring sub-trees); everything is written at the query's own index
@@ -64,18 +66,28 @@ __global__ __launch_bounds__(kRangeBlock) void range_kernel(TreeView tv, const f
   const int64_t out0 = kFill ? offsets[i] : 0;
   const int64_t cap = kFill ? offsets[i + 1] - out0 : 0;
   const bool slice_ok = kFill && out0 >= 0 && cap >= 0 && out0 + cap <= total;
-  range_walk(tv, s_stack + threadIdx.x, kRangeBlock, qx, qy, qz, bound, [&](int32_t id, float d) {
+  auto hit = [&](const float4 &nd, float d) {
     if (kFill && slice_ok && found < cap) {
-      out_id[out0 + found] = id;
+      out_id[out0 + found] = __float_as_int(nd.w);
       out_key[out0 + found] = __float_as_uint(d);  // d >= 0: the bit pattern orders like the value
       out_query[out0 + found] = (uint32_t)i;
     }
     ++found;
-  });
+  };
+  if constexpr (kSrc == kRangeWalk) {
+    range_walk_nodes(tv, s_stack + threadIdx.x, kBlock, qx, qy, qz, bound, hit);
+  } else {
+    auto visit = [&](const float4 &nd, float d) {
+      if (d < bound) hit(nd, d);  // kdtree.go:166-169,178-181
+      return true;
+    };
+    xwalk(xv, s_stack + threadIdx.x, kBlock, qx, qy, qz, guard, [&]() { return bound; }, visit, visit);
+  }
   if (!kFill) counts[i] = found;
 }
 
-// The same on the grid: every point of the cells grid_cover names, row by row.  Hits in cell order.
+// The same on the grid: every point of the cells grid_cover names, row by row.  Hits in cell order; the order among
+// equal DistSq of a query is made afterwards (range_tie_*_kernel), everything else is sorted by DistSq.
 template <bool kFill>
 __global__ __launch_bounds__(kRangeBlock) void range_grid_kernel(GridView g, const float *__restrict__ q,
                                                                  const int32_t *__restrict__ perm, int64_t nq, float bound,
@@ -84,76 +96,45 @@ __global__ __launch_bounds__(kRangeBlock) void range_grid_kernel(GridView g, con
                                                                  uint4 *__restrict__ out_rec) {
   const uint32_t n_tiles = (uint32_t)((nq + kRangeBlock - 1) / kRangeBlock);
   const int64_t pos = (int64_t)xcd_tile(blockIdx.x, n_tiles) * kRangeBlock + threadIdx.x;
-  if (pos >= nq) return;
-  const int64_t i = perm ? (int64_t)perm[pos] : pos;
-  const float qx = q[3 * i], qy = q[3 * i + 1], qz = q[3 * i + 2];
-  int64_t found = 0;
-  const int64_t out0 = kFill ? offsets[i] : 0;
-  const int64_t cap = kFill ? offsets[i + 1] - out0 : 0;
-  const bool slice_ok = kFill && out0 >= 0 && cap >= 0 && out0 + cap <= total;
-  auto take = [&](const float4 &p) {
-    const float dx = p.x - qx, dy = p.y - qy, dz = p.z - qz;
-    const float d = (dx * dx + dy * dy) + dz * dz;  // the reference's expression (mat/vec3.go:18-20,38-40)
-    if (d < bound) {  // kdtree.go:166,178
-      // one 16-byte store per neighbour (every lane writes into a slice of its own: three 4-byte stores into
-      // three arrays made the fill 2.3x the count); range_split_kernel spreads them afterwards, coalesced
-      if (kFill && slice_ok && found < cap)
-        out_rec[out0 + found] = make_uint4(__float_as_uint(p.w), __float_as_uint(d), (uint32_t)i, 0u);
-      ++found;
-    }
-  };
-  // (a NaN bound or query: the box is some cell or other and no distance compares below the bound, as in the walk)
-  const GridBox box = grid_cover(g, qx, qy, qz, bound);
-  // A row of thousands of records (one site of the cloud taken a hundred thousand times) is not one lane's work -- 25 ms
-  // of dependent loop for 100k records, twice: the lane notes up to two such rows and the WAVE scans them together
-  // below.  The order hits are found in is free here: among equal DistSq of a query it is made afterwards
-  // (range_tie_*_kernel), everything else is sorted by DistSq.
-  constexpr uint32_t kFatRow = 4096u;
-  uint32_t fat_f0 = 0u, fat_e0 = 0u, fat_f1 = 0u, fat_e1 = 0u;
-  int nfat = 0;
-  for (int z = box.z0; z <= box.z1; z++) {
-    for (int y = box.y0; y <= box.y1; y++) {
-      const uint32_t row = ((uint32_t)z * (uint32_t)g.ny + (uint32_t)y) * (uint32_t)g.nx;
-      uint32_t f = g.start[row + (uint32_t)box.x0];
-      const uint32_t e = g.start[row + (uint32_t)box.x1 + 1u];
-      if (e - f >= kFatRow && e > f && nfat < 2) {
-        if (nfat == 0) { fat_f0 = f; fat_e0 = e; }
-        else { fat_f1 = f; fat_e1 = e; }
-        nfat++;
-        continue;
-      }
-      for (; f + 4u <= e; f += 4u) {  // four records in flight
-        const float4 p0 = g.pts[f], p1 = g.pts[f + 1u], p2 = g.pts[f + 2u], p3 = g.pts[f + 3u];
-        take(p0); take(p1); take(p2); take(p3);
-      }
-      for (; f < e; f++) take(g.pts[f]);
-    }
+  const bool live = pos < nq;  // (every lane of the wave stays to the end: the fat rows are scanned by all 64)
+  int64_t i = 0;
+  float qx = 0.0f, qy = 0.0f, qz = 0.0f;
+  if (live) {
+    i = perm ? (int64_t)perm[pos] : pos;
+    qx = q[3 * i]; qy = q[3 * i + 1]; qz = q[3 * i + 2];
   }
-  if (__ballot(nfat > 0) != 0ull) {  // (the lanes that are still here: those with a query)
-    const int lane = (int)(threadIdx.x & 63u);
-    const unsigned long long act = __ballot(true), below = act & ((1ull << lane) - 1ull);
-    const uint32_t nact = (uint32_t)__popcll(act), myrank = (uint32_t)__popcll(below);
-    for (int k = 0; k < 2; k++) {
-      unsigned long long owners = __ballot(nfat > k);
-      while (owners != 0ull) {  // uniform
-        const int owner = __builtin_ctzll(owners);
-        owners &= owners - 1ull;
-        const float ox = __shfl(qx, owner), oy = __shfl(qy, owner), oz = __shfl(qz, owner);
-        const uint32_t rf = __shfl(k == 0 ? fat_f0 : fat_f1, owner), re = __shfl(k == 0 ? fat_e0 : fat_e1, owner);
+  int64_t found = 0;
+  const int64_t out0 = kFill && live ? offsets[i] : 0;
+  const int64_t cap = kFill && live ? offsets[i + 1] - out0 : 0;
+  const bool slice_ok = kFill && live && out0 >= 0 && cap >= 0 && out0 + cap <= total;
+  const int lane = (int)(threadIdx.x & 63u);
+  grid_radius_scan(
+      g, qx, qy, qz, bound, live,
+      [&](const float4 &p) {
+        const float d = ref_dist_sq(p.x, p.y, p.z, qx, qy, qz);
+        if (d < bound) {  // kdtree.go:166,178
+          // one 16-byte store per neighbour (every lane writes into a slice of its own: three 4-byte stores into
+          // three arrays made the fill 2.3x the count); range_split_kernel spreads them afterwards, coalesced
+          if (kFill && slice_ok && found < cap)
+            out_rec[out0 + found] = make_uint4(__float_as_uint(p.w), __float_as_uint(d), (uint32_t)i, 0u);
+          ++found;
+        }
+      },
+      [&](int owner, uint32_t rf, uint32_t re, float ox, float oy, float oz) {
+        // 64 records at a time; a hit's slot is the owner's count so far plus the hits of the lanes below it
         const long long o_out0 = __shfl((long long)out0, owner), o_cap = __shfl((long long)cap, owner),
                         o_found = __shfl((long long)found, owner);
         const int o_ok = __shfl(slice_ok ? 1 : 0, owner);
         const uint32_t o_i = __shfl((uint32_t)i, owner);
         long long add = 0;
-        for (uint32_t r0 = rf; r0 < re; r0 += nact) {  // uniform
-          const uint32_t r = r0 + myrank;
+        for (uint32_t r0 = rf; r0 < re; r0 += 64u) {  // uniform
+          const uint32_t r = r0 + (uint32_t)lane;
           bool hit = false;
           float4 p = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
           float d = 0.0f;
           if (r < re) {
             p = g.pts[r];
-            const float dx = p.x - ox, dy = p.y - oy, dz = p.z - oz;
-            d = (dx * dx + dy * dy) + dz * dz;
+            d = ref_dist_sq(p.x, p.y, p.z, ox, oy, oz);
             hit = d < bound;
           }
           const unsigned long long hb = __ballot(hit);
@@ -164,10 +145,8 @@ __global__ __launch_bounds__(kRangeBlock) void range_grid_kernel(GridView g, con
           add += (long long)__popcll(hb);
         }
         if (lane == owner) found += (int64_t)add;
-      }
-    }
-  }
-  if (!kFill) counts[i] = found;
+      });
+  if (live && !kFill) counts[i] = found;
 }
 
 // {id, DistSq bits, query} records -> the three arrays the sort works on (a slot no query wrote keeps the
@@ -303,12 +282,6 @@ __global__ __launch_bounds__(256) void range_widen_check_kernel(const uint32_t *
 }  // namespace pcgx
 
 namespace pcgx {
-// PCGX_RANGE_WALK=1: the tree walk even where the handle has a grid (measurements, tests of the walk)
-bool range_on_grid(const pcgx_kdtree *t) {
-  const char *e = getenv("PCGX_RANGE_WALK");  // (read per call: the tests switch between the two)
-  return t->grid_ok && !(e && *e && *e != '0');
-}
-
 static pcgx_status range_inverse_map(const pcgx_kdtree *tc, const uint32_t **out, hipStream_t st) {
   pcgx_kdtree *t = const_cast<pcgx_kdtree *>(tc);  // made once per handle, on first use
   std::lock_guard<std::mutex> lock(t->mu);
@@ -332,6 +305,51 @@ static pcgx_status range_inverse_map(const pcgx_kdtree *tc, const uint32_t **out
   *out = t->d_inv;
   return PCGX_OK;
 }
+
+// The neighbours of the nq device queries d_q (perm: launch position -> query, or none) by the kernel of src.
+// kFill == false: their number into counts.  kFill == true: {id, DistSq bits, query} in discovery order at the caller's
+// offsets, into slots poisoned first (id 0xffffffff, DistSq and query 0): offsets that leave a slot unwritten are caught
+// behind the sort, and on the grid already by range_split_kernel (into *bad).
+template <bool kFill>
+static pcgx_status range_launch(const pcgx_kdtree *t, RangeSrc src, const float *d_q, const int32_t *perm, int64_t nq,
+                                float bound, int64_t *counts, const int64_t *offsets, int64_t total, int32_t *out_id,
+                                uint32_t *out_key, uint32_t *out_query, int32_t *bad, hipStream_t st) {
+  const dim3 tiles(xcd_grid((unsigned)((nq + kRangeBlock - 1) / kRangeBlock)));
+  if (src == kRangeGrid) {
+    uint4 *rec = nullptr;
+    if (kFill) {
+      PCGX_TRY(ctx().arena.alloc_n((size_t)total, &rec));
+      PCGX_HIP_TRY(hipMemsetAsync(rec, 0xFF, (size_t)total * 16, st));
+    }
+    hipLaunchKernelGGL(range_grid_kernel<kFill>, tiles, dim3(kRangeBlock), 0, st, t->grid, d_q, perm, nq, bound, counts,
+                       offsets, total, rec);
+    if (kFill)
+      hipLaunchKernelGGL(range_split_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (const uint4 *)rec,
+                         total, out_id, out_key, out_query, bad);
+  } else {
+    if (kFill) {
+      PCGX_HIP_TRY(hipMemsetAsync(out_id, 0xFF, (size_t)total * 4, st));
+      PCGX_HIP_TRY(hipMemsetAsync(out_key, 0, (size_t)total * 4, st));
+      PCGX_HIP_TRY(hipMemsetAsync(out_query, 0, (size_t)total * 4, st));
+    }
+    if (src == kRangeWalk) {
+      const TreeView tv = t->view();
+      hipLaunchKernelGGL((range_kernel<kRangeWalk, kFill>), tiles, dim3(kRangeBlock), walk_stack_bytes(tv, kRangeBlock), st,
+                         tv, XTreeView{}, d_q, perm, nq, bound, counts, offsets, total, out_id, out_key, out_query,
+                         (int64_t)0);
+    } else {
+      XTreeView xv;
+      PCGX_TRY(xtree_view(t, &xv, st));
+      const size_t lds = (size_t)(xv.depth > 0 ? xv.depth : 1) * kXBlock * sizeof(uint32_t);
+      const int64_t guard = 4 * t->n + 8;  // a walk takes at most two steps per node
+      hipLaunchKernelGGL((range_kernel<kRangeXWalk, kFill>), dim3((unsigned)((nq + kXBlock - 1) / kXBlock)), dim3(kXBlock),
+                         lds, st, TreeView{}, xv, d_q, perm, nq, bound, counts, offsets, total, out_id, out_key, out_query,
+                         guard);
+    }
+  }
+  PCGX_HIP_TRY(hipGetLastError());
+  return PCGX_OK;
+}
 }  // namespace pcgx
 
 extern "C" pcgx_status pcgx_kdtree_range_count(const pcgx_kdtree *t, const float *q, int64_t nq, float max_range,
@@ -344,10 +362,7 @@ extern "C" pcgx_status pcgx_kdtree_range_count(const pcgx_kdtree *t, const float
     (void)xtree_host_range(t, q, nq, max_range, counts, nullptr, nullptr, nullptr);
     return PCGX_OK;
   }
-  const pcgx_kdtree *outer = t;  // a handle with deletions walks the reference's patched tree (knn_explicit.hip)
-  const bool patched = outer->n_deleted > 0;
-  bool empty = false;
-  if (!patched) PCGX_TRY(resolve_tree(t, &t, &empty));
+  const RangeSrc src = range_source(t);
   hipStream_t st = ctx().stream;
   float *d_q = nullptr;
   int64_t *d_c = nullptr;
@@ -355,26 +370,14 @@ extern "C" pcgx_status pcgx_kdtree_range_count(const pcgx_kdtree *t, const float
   PCGX_TRY(ctx().host_arena.alloc_n((size_t)nq * 3, &d_q));
   PCGX_TRY(ctx().host_arena.alloc_n((size_t)nq, &d_c));
   PCGX_TRY(staged_upload(d_q, q, (size_t)nq * 12, st));
-  const TreeView tv = t->view();
-  const size_t lds = walk_stack_bytes(tv, kRangeBlock);
   int32_t *perm = nullptr;
   if (nq >= kRangePresortMin) {
     PCGX_TRY(ctx().arena.begin(st));
     PCGX_TRY(ctx().arena.alloc_n((size_t)nq, &perm));
     PCGX_TRY(morton_order(d_q, nq, t->bbox_lo, t->bbox_hi, perm, st));
   }
-  if (patched)
-    PCGX_TRY(xtree_launch_range(outer, false, d_q, perm, nq, max_range * max_range, d_c, nullptr, 0, nullptr, nullptr,
-                                nullptr, st));
-  else if (range_on_grid(t))
-    hipLaunchKernelGGL(range_grid_kernel<false>, dim3(xcd_grid((unsigned)((nq + kRangeBlock - 1) / kRangeBlock))), dim3(kRangeBlock),
-                       0, st, t->grid, (const float *)d_q, (const int32_t *)perm, nq, max_range * max_range, d_c, nullptr, 0,
-                       (uint4 *)nullptr);
-  else
-    hipLaunchKernelGGL(range_kernel<false>, dim3(xcd_grid((unsigned)((nq + kRangeBlock - 1) / kRangeBlock))), dim3(kRangeBlock),
-                       lds, st, tv, (const float *)d_q, (const int32_t *)perm, nq, max_range * max_range, d_c, nullptr, 0,
-                       nullptr, nullptr, nullptr);
-  PCGX_HIP_TRY(hipGetLastError());
+  PCGX_TRY(range_launch<false>(t, src, d_q, perm, nq, max_range * max_range, d_c, nullptr, 0, nullptr, nullptr, nullptr,
+                               nullptr, st));
   PCGX_TRY(staged_download(counts, d_c, (size_t)nq * 8, st));
   return PCGX_OK;
 }
@@ -397,16 +400,13 @@ extern "C" pcgx_status pcgx_kdtree_range_fill(const pcgx_kdtree *t, const float 
       return fail(PCGX_E_INVALID, "pcgx_kdtree_range_fill: offsets do not match the neighbour counts");
     return PCGX_OK;
   }
-  const pcgx_kdtree *outer = t;
-  const bool patched = outer->n_deleted > 0;
-  bool empty = false;
-  if (!patched) PCGX_TRY(resolve_tree(t, &t, &empty));
+  const RangeSrc src = range_source(t);
   hipStream_t st = ctx().stream;
   Arena &ar = ctx().arena;
   PCGX_TRY(ar.begin(st));
   float *d_q = nullptr;
   int64_t *d_off = nullptr;
-  int32_t *d_id = nullptr;
+  int32_t *d_id = nullptr, *d_bad = nullptr;
   uint32_t *keys[2] = {nullptr, nullptr}, *vals[2] = {nullptr, nullptr}, *d_query = nullptr, *d_key = nullptr,
            *d_out_id = nullptr, *d_out_key = nullptr;
   void *ws = nullptr;
@@ -422,41 +422,17 @@ extern "C" pcgx_status pcgx_kdtree_range_fill(const pcgx_kdtree *t, const float 
   PCGX_TRY(ar.alloc_n((size_t)total, &d_out_id));
   PCGX_TRY(ar.alloc_n((size_t)total, &d_out_key));
   PCGX_TRY(ar.alloc(radix_sort_workspace_bytes(total), &ws));
+  PCGX_TRY(ar.alloc_n(1, &d_bad));
   PCGX_TRY(staged_upload(d_q, q, (size_t)nq * 12, st));
   PCGX_TRY(staged_upload(d_off, offsets, (size_t)(nq + 1) * 8, st));
-  const bool on_grid = !patched && range_on_grid(t);
-  if (!on_grid) {
-    // Poison the ids so that offsets inconsistent with the counts are caught below.
-    PCGX_HIP_TRY(hipMemsetAsync(d_id, 0xFF, (size_t)total * 4, st));
-    PCGX_HIP_TRY(hipMemsetAsync(d_key, 0, (size_t)total * 4, st));
-    PCGX_HIP_TRY(hipMemsetAsync(d_query, 0, (size_t)total * 4, st));
-  }
-  const TreeView tv = t->view();
-  const size_t lds = walk_stack_bytes(tv, kRangeBlock);
+  PCGX_HIP_TRY(hipMemsetAsync(d_bad, 0, 4, st));
   int32_t *qperm = nullptr;
   if (nq >= kRangePresortMin) {
     PCGX_TRY(ar.alloc_n((size_t)nq, &qperm));
     PCGX_TRY(morton_order(d_q, nq, t->bbox_lo, t->bbox_hi, qperm, st));
   }
-  int32_t *d_bad = nullptr;
-  if (patched)
-    PCGX_TRY(xtree_launch_range(outer, true, d_q, qperm, nq, max_range * max_range, nullptr, d_off, total, d_id, d_key,
-                                d_query, st));
-  else if (on_grid) {
-    uint4 *d_rec = nullptr;
-    PCGX_TRY(ar.alloc_n((size_t)total, &d_rec));
-    PCGX_HIP_TRY(hipMemsetAsync(d_rec, 0xFF, (size_t)total * 16, st));  // (poisoned ids as above)
-    PCGX_TRY(ar.alloc_n(1, &d_bad));
-    PCGX_HIP_TRY(hipMemsetAsync(d_bad, 0, 4, st));
-    hipLaunchKernelGGL(range_grid_kernel<true>, dim3(xcd_grid((unsigned)((nq + kRangeBlock - 1) / kRangeBlock))), dim3(kRangeBlock),
-                       0, st, t->grid, (const float *)d_q, (const int32_t *)qperm, nq, max_range * max_range, nullptr, d_off, total,
-                       d_rec);
-    hipLaunchKernelGGL(range_split_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, st, (const uint4 *)d_rec, total,
-                       d_id, d_key, d_query, d_bad);
-  } else
-    hipLaunchKernelGGL(range_kernel<true>, dim3(xcd_grid((unsigned)((nq + kRangeBlock - 1) / kRangeBlock))), dim3(kRangeBlock),
-                       lds, st, tv, d_q, (const int32_t *)qperm, nq, max_range * max_range, nullptr, d_off, total, d_id,
-                       d_key, d_query);
+  PCGX_TRY(range_launch<true>(t, src, d_q, qperm, nq, max_range * max_range, nullptr, d_off, total, d_id, d_key, d_query,
+                              d_bad, st));
   const unsigned tb = (unsigned)((total + 255) / 256);
   hipLaunchKernelGGL(range_iota_kernel, dim3(tb), dim3(256), 0, st, vals[0], total);
   PCGX_HIP_TRY(hipMemcpyAsync(keys[0], d_key, (size_t)total * 4, hipMemcpyDeviceToDevice, st));
@@ -475,7 +451,8 @@ extern "C" pcgx_status pcgx_kdtree_range_fill(const pcgx_kdtree *t, const float 
                      d_out_id);
   hipLaunchKernelGGL(range_gather_u32_kernel, dim3(tb), dim3(256), 0, st, d_key, perm, total, d_out_key);
   PCGX_HIP_TRY(hipGetLastError());
-  if (on_grid) {  // equal DistSq of one query: into the walk's order (k2[r2]: the query of every sorted slot)
+  if (src == kRangeGrid) {  // equal DistSq of one query: into the walk's order (k2[r2]: the query of every sorted slot)
+    const TreeView tv = t->view();
     const uint32_t *d_inv = nullptr;
     PCGX_TRY(range_inverse_map(t, &d_inv, st));
     unsigned long long *d_place = nullptr;
@@ -486,10 +463,6 @@ extern "C" pcgx_status pcgx_kdtree_range_fill(const pcgx_kdtree *t, const float 
     hipLaunchKernelGGL(range_tie_place_kernel, dim3(tb), dim3(256), 0, st, tv, d_inv, (const float *)d_q, (const uint32_t *)k2[r2],
                        (const uint32_t *)d_out_key, (const uint32_t *)d_out_id, total, d_place, d_long);
     // (into d_id: the discovery-order ids are done with)
-    if (!d_bad) {
-      PCGX_TRY(ar.alloc_n(1, &d_bad));
-      PCGX_HIP_TRY(hipMemsetAsync(d_bad, 0, 4, st));
-    }
     int32_t long_run = 0;
     PCGX_HIP_TRY(hipMemcpyAsync(&long_run, d_long, 4, hipMemcpyDeviceToHost, st));
     PCGX_HIP_TRY(hipStreamSynchronize(st));
@@ -548,10 +521,6 @@ extern "C" pcgx_status pcgx_kdtree_range_fill(const pcgx_kdtree *t, const float 
   // counts) on the device, straight into the caller's slice
   int64_t *d_ids64 = nullptr;
   PCGX_TRY(ar.alloc_n((size_t)total, &d_ids64));
-  if (!d_bad) {
-    PCGX_TRY(ar.alloc_n(1, &d_bad));
-    PCGX_HIP_TRY(hipMemsetAsync(d_bad, 0, 4, st));
-  }
   hipLaunchKernelGGL(range_widen_check_kernel, dim3(tb), dim3(256), 0, st, (const uint32_t *)d_out_id, total, d_ids64, d_bad);
   PCGX_HIP_TRY(hipGetLastError());
   int32_t bad = 0;

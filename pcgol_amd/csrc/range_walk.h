@@ -11,6 +11,7 @@
 // neighbourhood moments of normal estimation).
 #pragma once
 #include "knn_walk.h"
+#include "range_enum.h"
 
 namespace pcgx {
 
@@ -35,8 +36,7 @@ __device__ __forceinline__ void range_walk_nodes(const TreeView &tv, uint32_t *_
       at = fw & 0x07FFFFFFu;
     }
     const float4 nd = node_at(tv.nodes, at);
-    const float dx = nd.x - qx, dy = nd.y - qy, dz = nd.z - qz;
-    const float d = (dx * dx + dy * dy) + dz * dz;
+    const float d = ref_dist_sq(nd.x, nd.y, nd.z, qx, qy, qz);
     const int32_t depth = 31 - __clz((int)at);
     const int dim = depth % 3;
     const float pv = sel3(dim, nd.x, nd.y, nd.z), qv = sel3(dim, qx, qy, qz);

@@ -210,8 +210,7 @@ __global__ __launch_bounds__(256) void rg_grid_kernel(GridView g, int64_t n, con
       e = e < (uint32_t)f0 ? e : (uint32_t)f0;  // each edge from its higher end
       for (; f < e; f++) {
         const float4 p = g.pts[f];
-        const float dx = p.x - me.x, dy = p.y - me.y, dz = p.z - me.z;
-        const float d = (dx * dx + dy * dy) + dz * dz;  // (mat/vec3.go:18-20,38-40, as in the walk)
+        const float d = ref_dist_sq(p.x, p.y, p.z, me.x, me.y, me.z);
         if (!(d < bound) || labels[__float_as_uint(p.w)] != mine) continue;  // regiongrowing.go:43-47
         if (kHookMin) {
           best = f < best ? f : best;
@@ -627,8 +626,7 @@ extern "C" pcgx_status pcgx_region_growing_components(const pcgx_kdtree *t, cons
   hipLaunchKernelGGL(uf_init_kernel, dim3(nb), dim3(256), 0, st, d_parent, n);
   const TreeView tv = t->view();
   const uint32_t slots = 1u << tv.depth;
-  const char *walk_env = getenv("PCGX_RANGE_WALK");  // (as in range.hip: the walk although the handle has a grid)
-  const bool on_grid = t->grid_ok && t->n == n && !(walk_env && *walk_env && *walk_env != '0');
+  const bool on_grid = t->grid_ok && t->n == n && !range_walk_forced();  // (the resolved tree; no patched walk here)
   if (on_grid) {
     uint32_t *d_min = nullptr;
     PCGX_TRY(ar.alloc_n((size_t)n, &d_min));

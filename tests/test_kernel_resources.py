@@ -1,4 +1,4 @@
-"""No kernel of the ICP step (and of the VoxelGrid bucket path) may spill: hipcc's own resource report
+"""No kernel of the ICP step (and of the VoxelGrid bucket path, and of Range's neighbourhood enumeration) may spill: hipcc's own resource report
 (-Rpass-analysis=kernel-resource-usage, tools/kernel_resources.py) for the production instantiations.
 HISTORY.md (3.9) records what spilled dwords cost on this chip (5 us phases became 40 us ones); round 3 shipped
 strict_sum_kernel with 8 bytes of scratch per lane under its occupancy attribute."""
@@ -16,6 +16,8 @@ STEP_KERNELS = {
     "strict.hip": ["strict_sum_kernelILb1E", "strict_sum_kernelILb0E", "strict_job_kernel", "strict_chain_kernelILb0ELb0E",
                    "strict_chain_kernelILb0ELb1E"],
     "icp_small.hip": ["icp_small_fit_kernelILb0E", "icp_small_fit_kernelILb1E"],
+    "range.hip": ["range_grid_kernelILb0E", "range_grid_kernelILb1E", "range_kernelILi1ELb0E", "range_kernelILi1ELb1E",
+                  "range_kernelILi2ELb0E", "range_kernelILi2ELb1E"],
     "voxel_bucket.hip": ["vb_key_hist_kernel", "vb_scatter_kernelILb1ELb0E", "vb_scatter_kernelILb0ELb0E",
                          "vb_bucket_kernelILb0E", "vb_bucket_kernelILb1E"],
 }
