@@ -17,6 +17,8 @@ import (
 // Nearest and Range for ONE point are a blocking GPU call each: code that loops over them (correspondence.go:25-36,
 // regiongrowing.go:26,47) should take the batch seams instead -- NearestBatch / RangeBatch here, or the icp and
 // segmentation types of this tree, which do.  pcgx.SinglePointCalls() counts such calls (tests guard hot loops with it).
+// Extensions with no reference counterpart come with the type: KNearest(p, k, maxRange) []storage.Neighbor (the k
+// nearest points, ties by ID; include/pcgx.h, pcgx_kdtree_knearest), KNearestBatch, Normals.
 type KDTree = pcgx.KDTree
 
 // KDTreeOption is kdtree.KDTreeOption (kdtree.go:31).
@@ -46,3 +48,4 @@ func NewFromPointCloud(pp *pc.PointCloud, opts ...KDTreeOption) (*KDTree, error)
 
 // WithMinDistSq is the option form of the exported field MinDistSq (the reference defines no option of its own).
 func WithMinDistSq(d float32) KDTreeOption { return pcgx.WithMinDistSq(d) }
+

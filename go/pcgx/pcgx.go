@@ -326,6 +326,61 @@ func (k *KDTree) NormalsAt(q []mat.Vec3, radius float32, viewpoint mat.Vec3, min
 	return normals, curvature, counts, nil
 }
 
+// KNearest returns the kk points of the tree with the smallest (DistSq, ID) among those with DistSq < maxRange^2,
+// ascending (extension: no reference parity; include/pcgx.h, pcgx_kdtree_knearest: ties go by ID).  Like Nearest it
+// is one blocking GPU call and panics where the call fails (kk outside [1, 64], a NaN maxRange).
+func (k *KDTree) KNearest(p mat.Vec3, kk int, maxRange float32) []storage.Neighbor {
+	atomic.AddInt64(&singlePointCalls, 1)
+	r, err := k.KNearestBatch([]mat.Vec3{p}, kk, maxRange)
+	if err != nil {
+		panic(err)
+	}
+	return r[0]
+}
+
+// KNearestBatch is KNearest for every query, one row each (at most kk long); q == nil takes the tree's own points,
+// in id order.
+func (k *KDTree) KNearestBatch(q []mat.Vec3, kk int, maxRange float32) ([][]storage.Neighbor, error) {
+	runtime.LockOSThread() // the error text is thread-local on the C side: call and pcgx_last_error on one OS thread
+	defer runtime.UnlockOSThread()
+	defer runtime.KeepAlive(k) // the finalizer must not free the handle while a call is in flight
+	var qp *C.float
+	n := len(q)
+	if q == nil {
+		var ln C.int64_t
+		if err := status(C.pcgx_kdtree_len(k.t.h, &ln)); err != nil {
+			return nil, err
+		}
+		n = int(ln)
+	} else if n > 0 {
+		qp = (*C.float)(unsafe.Pointer(&q[0]))
+	}
+	if n == 0 {
+		return [][]storage.Neighbor{}, nil
+	}
+	if kk < 1 || kk > 64 {
+		return nil, errors.New("pcgx: k must be in [1, 64]")
+	}
+	ids := make([]int64, n*kk)
+	dsq := make([]float32, n*kk)
+	counts := make([]int32, n)
+	rc := C.pcgx_kdtree_knearest(k.t.h, qp, C.int64_t(n), C.int32_t(kk), C.float(maxRange),
+		(*C.int64_t)(unsafe.Pointer(&ids[0])), (*C.float)(unsafe.Pointer(&dsq[0])), (*C.int32_t)(unsafe.Pointer(&counts[0])))
+	runtime.KeepAlive(q)
+	if err := status(rc); err != nil {
+		return nil, err
+	}
+	out := make([][]storage.Neighbor, n)
+	for i := range out {
+		row := make([]storage.Neighbor, counts[i])
+		for s := range row {
+			row[s] = storage.Neighbor{ID: int(ids[i*kk+s]), DistSq: dsq[i*kk+s]}
+		}
+		out[i] = row
+	}
+	return out, nil
+}
+
 // Nearest keeps storage.Search working for single points (one tiny batch).
 func (k *KDTree) Nearest(p mat.Vec3, maxRange float32) storage.Neighbor {
 	atomic.AddInt64(&singlePointCalls, 1)
@@ -422,6 +477,56 @@ func (f *voxelGrid) Filter(pp *pc.PointCloud) (*pc.PointCloud, error) {
 	newPc := &pc.PointCloud{PointCloudHeader: pp.Clone(), Points: int(m), Data: out[:int(m)*stride]}
 	newPc.Width, newPc.Height = int(m), 1
 	return newPc, nil
+}
+
+// ---------------------------------------------- statistical outlier removal (extension)
+
+// SOR is a filter.Filter for statistical outlier removal (no reference counterpart; PCL's
+// StatisticalOutlierRemoval; include/pcgx.h, pcgx_sor_filter): keeps the points whose mean distance to their MeanK
+// nearest other finite points is at most mu + StddevMul * sigma (Negative: the others), records byte for byte in
+// input order.  Non-finite points are dropped in both modes.
+type SOR struct {
+	MeanK     int
+	StddevMul float32
+	Negative  bool
+}
+
+// Filter runs the filter; Stats is the same with the mean distances (by input index, NaN for dropped points) and
+// {mu, sigma, threshold}.
+func (f *SOR) Filter(pp *pc.PointCloud) (*pc.PointCloud, error) {
+	out, _, _, err := f.FilterStats(pp)
+	return out, err
+}
+
+func (f *SOR) FilterStats(pp *pc.PointCloud) (*pc.PointCloud, []float64, [3]float64, error) {
+	runtime.LockOSThread() // the error text is thread-local on the C side: call and pcgx_last_error on one OS thread
+	defer runtime.UnlockOSThread()
+	var stats [3]float64
+	stride, off, err := xyzLayout(pp)
+	if err != nil {
+		return nil, nil, stats, err
+	}
+	n := pp.Points
+	if n == 0 {
+		return nil, nil, stats, errors.New("no point")
+	}
+	out := make([]byte, n*stride)
+	md := make([]float64, n)
+	neg := C.int32_t(0)
+	if f.Negative {
+		neg = 1
+	}
+	var m C.int64_t
+	rc := C.pcgx_sor_filter(unsafe.Pointer(&pp.Data[0]), C.int64_t(n), C.int32_t(stride), C.int32_t(off),
+		C.int32_t(f.MeanK), C.float(f.StddevMul), neg, unsafe.Pointer(&out[0]), &m,
+		(*C.double)(unsafe.Pointer(&md[0])), (*C.double)(unsafe.Pointer(&stats[0])))
+	runtime.KeepAlive(pp)
+	if err := status(rc); err != nil {
+		return nil, nil, stats, err
+	}
+	newPc := &pc.PointCloud{PointCloudHeader: pp.Clone(), Points: int(m), Data: out[:int(m)*stride]}
+	newPc.Width, newPc.Height = int(m), 1
+	return newPc, md, stats, nil
 }
 
 // FilterSharded is this rank's share of Filter(pp) over the ranks of c (SURVEY 8(e)): every rank

@@ -760,6 +760,56 @@ PCGX_API pcgx_status pcgx_kdtree_normals_dev(const pcgx_kdtree *t, const float *
                                              const float viewpoint[3], int32_t min_neighbors, float *d_normals,
                                              float *d_curvature, int32_t *d_counts, void *stream);
 
+/* ------------------------------------------- k nearest neighbours (extension: no reference parity)
+ * NOT in the reference: pcgol's KD-tree answers Nearest (k = 1) and Range (a fixed radius).  For each query i: the k
+ * points p of the tree with the smallest (DistSq(p, q[i]), id) in lexicographic order, among those with
+ * DistSq < max_range^2 (Range's rule, kdtree.go:166,178; DistSq is the reference's float32 expression
+ * (dx*dx + dy*dy) + dz*dz).  Ascending in that order.  counts[i] = how many were found (<= k).  Slots past counts[i]
+ * are {-1, max_range^2}, Nearest's not-found value.
+ * q == NULL: the queries are the tree's own points in id order (nq must equal Len()); each point finds itself at
+ * DistSq 0.  Deleted points are never neighbours.  A deleted point's own row is still computed when q == NULL.
+ * 1 <= k <= 64.  max_range >= 0 or +inf.  Anything else (NaN max_range, NULL ids / dist_sq with nq > 0) is
+ * PCGX_E_INVALID.  Non-finite queries find nothing.
+ * Ties are broken by id, not by visit order, so the result is a function of the cloud alone, whichever way the
+ * device enumerates (grid, tree walk, patched tree after DeletePoint).  Consequences:
+ *   - the result equals the prefix Range(q, max_range)[:k] whenever no two of Range's first k+1 entries have equal
+ *     DistSq; on a tie it can differ, because Range orders ties by the walk's discovery order;
+ *   - k = 1 equals Nearest except on ties and at DistSq == max_range^2 (Nearest's leaf rule admits that one).
+ * Always computed on the device.  The cost is that of the cells (or tree nodes) the k-th distance covers; a heap of
+ * coincident points is scanned by a whole wave for every query that reaches it. */
+PCGX_API pcgx_status pcgx_kdtree_knearest(const pcgx_kdtree *t, const float *q, int64_t nq, int32_t k,
+                                          float max_range, int64_t *ids /* [nq*k] */,
+                                          float *dist_sq /* [nq*k] */, int32_t *counts /* [nq], may be NULL */);
+/* Same, every array device resident (ids int32), enqueued on `stream` (NULL: the library's); returns without
+ * waiting. */
+PCGX_API pcgx_status pcgx_kdtree_knearest_dev(const pcgx_kdtree *t, const float *d_q, int64_t nq, int32_t k,
+                                              float max_range, int32_t *d_ids, float *d_dist_sq,
+                                              int32_t *d_counts, void *stream);
+
+/* ------------------------------------------- statistical outlier removal (extension: no reference parity)
+ * PCL's StatisticalOutlierRemoval / Open3D's remove_statistical_outlier over an AoS cloud (stride / xyz_off as
+ * pcgx_voxel_filter).
+ *   F   = the points whose x, y, z are all finite (the others are dropped and are nobody's neighbour); m = |F|.
+ *   d_i = (1/mean_k) * sum of sqrt((double)DistSq) over the mean_k points of F \ {i} with the smallest
+ *         (DistSq, id) (pcgx_kdtree_knearest's order, ids = positions in F).  The sum is float64 in that order.
+ *         Coincident duplicates of i count; i itself does not.
+ *   mu  = sum d_i / m;  sigma = sqrt(sum (d_i - mu)^2 / (m - 1));  T = mu + std_mul * sigma   (all float64;
+ *         deterministic: the same bits on every call for the same input).
+ *   keep i iff d_i <= T (negative != 0: iff d_i > T).  Output: the kept records, byte for byte, in input order;
+ *   *out_n of them (out_data must hold n*stride bytes).
+ * 1 <= mean_k <= 64 else PCGX_E_INVALID; n == 0 or m <= mean_k -> PCGX_E_NO_POINT; a stride / offset that does not
+ * hold an xyz triple -> PCGX_E_BAD_FIELD.  mean_dist (n doubles by input index, NaN for dropped points) and
+ * stats = {mu, sigma, T} are optional (NULL).  A tree over F is built inside the call (pcgx_kdtree_build). */
+PCGX_API pcgx_status pcgx_sor_filter(const void *data, int64_t n, int32_t stride, int32_t xyz_off, int32_t mean_k,
+                                     float std_mul, int32_t negative, void *out_data, int64_t *out_n,
+                                     double *mean_dist, double stats[3]);
+/* Device resident: d_data, d_out (>= n*stride bytes) and d_mean_dist (may be NULL) are device buffers; out_n and
+ * stats (may be NULL) are host memory.  Returns when everything is done on `stream` (the tree build in between needs
+ * the finite count on the host, and the tree is freed before the call returns). */
+PCGX_API pcgx_status pcgx_sor_filter_dev(const void *d_data, int64_t n, int32_t stride, int32_t xyz_off,
+                                         int32_t mean_k, float std_mul, int32_t negative, void *d_out,
+                                         int64_t *out_n, double *d_mean_dist, double stats[3], void *stream);
+
 #ifdef __cplusplus
 }
 #endif

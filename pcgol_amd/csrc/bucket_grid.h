@@ -119,6 +119,16 @@ __device__ __forceinline__ void tile_flag_write(int64_t n, Flag flag, const uint
   }
 }
 
+// One record of `stride` bytes, byte for byte (VoxelGrid's copy: 4-byte words where stride and both buffers allow)
+__device__ __forceinline__ void copy_record(const uint8_t *__restrict__ src, uint8_t *__restrict__ dst, int32_t stride,
+                                            bool words) {
+  if (words) {
+    for (int b = 0; b < stride; b += 4) *(uint32_t *)(dst + b) = *(const uint32_t *)(src + b);
+  } else {
+    for (int b = 0; b < stride; b++) dst[b] = src[b];
+  }
+}
+
 }  // namespace pcgx
 
 struct pcgx_bucket_grid {

@@ -1,0 +1,466 @@
+// knearest.hip -- k nearest neighbours on a KD-tree handle (extension: no reference counterpart).
+//
+// pcgol answers Nearest (k = 1) and Range (a fixed radius); this is the k closest points, the query statistical outlier
+// removal (sor.hip) is built on.  For query q, 1 <= k <= 64, bound B = max_range^2 (include/pcgx.h, pcgx_kdtree_knearest):
+//   the k points p of the tree with the smallest (DistSq(p, q), id), lexicographic, among those with DistSq < B
+//   (Range's rule; DistSq is the reference's float32 expression ref_dist_sq), ascending.
+// Ties go by id, not by visit order: the answer is a function of the cloud alone, so no source ever has to fall back to
+// another because of a tie, and a brute-force oracle checks it.  Each lane keeps its query's best k as 64-bit keys
+// {bits(DistSq) << 32 | id} -- DistSq >= 0, so the bits order as the floats do and one integer compare is the
+// lexicographic one -- sorted ascending in LDS laid out [slot][lane] (a runtime-indexed register array would go to
+// scratch), inserted by a short insertion sort.  d_k is the k-th DistSq once k are held.  Three sources, as
+// pcgx_kdtree_range_count takes them (range_source, range_enum.h):
+//   grid  (kRangeGrid): the 3 x 3 x 3 cells around the query, then shells; accepted when grid_cover(min(d_k, B)) lies
+//         inside the box scanned (the certificate knn_grid.h uses for k = 1).  A box beyond kGridWide cells of the
+//         query's own cell goes to the implicit-tree walk below, in the same lane.  Rows of kRangeFatRow records and
+//         more (a site of the cloud taken thousands of times) are scanned by the whole wave, the owner inserting what
+//         beats its k-th key.
+//   walk  (kRangeWalk: no grid, PCGX_RANGE_WALK=1): the implicit tree, a side pruned when fromPivotSq > min(d_k, B)
+//         (strict: an equal-DistSq point with a smaller id may lie beyond the plane), re-tested when a frame is popped;
+//   xwalk (kRangeXWalk: a handle that has seen DeletePoint): the patched tree's walk (knn_xwalk.h), same pruning.
+// Non-finite queries find nothing (no DistSq of theirs compares below B).  Queries: the caller's (Morton-ordered from
+// kKnnPresortMin on), or the tree's own points (q == NULL) in the grid's cell order.  SOR mode writes no ids: only the
+// mean of sqrt(DistSq) over the first mean_k entries other than the query's own id, in float64 (sor.hip).
+#include <math.h>
+#include <stdlib.h>
+
+#include "knn_grid.h"
+#include "knn_xwalk.h"
+#include "range_walk.h"
+
+namespace pcgx {
+
+constexpr int kKnnKBlock = kRangeWalkBlock;  // one wave per workgroup: the top-k lists and walk stacks are [.][64] in LDS
+constexpr int64_t kKnnPresortMin = 16384;    // caller batches from this size on run in Morton order (as Range's)
+constexpr int kKnnMaxK = 64;
+
+struct KnnQuery {
+  const float *q;
+  const int32_t *perm;
+  const float4 *own;  // {x, y, z, bits(id)}: the tree's own points in cell order, else nullptr
+  int64_t nq;
+};
+
+struct KnnOut {
+  int32_t *ids;      // [nq * k] (not SOR)
+  float *dsq;        // [nq * k] (not SOR)
+  int32_t *counts;   // [nq] or nullptr
+  double *mean;      // SOR: [nq] by id, compact
+  int32_t mean_k;    // SOR: k - 1
+};
+
+// One lane's best k, ascending, in LDS column `col` (slot s at col[s * 64]).
+struct TopK {
+  uint64_t *col;
+  int k, c;        // capacity, held
+  uint64_t worst;  // the k-th key once k are held, else all ones
+  float mr2;       // max_range^2
+  float lim;       // min(d_k, mr2): a point must have DistSq below it (equal: only with a smaller id)
+
+  __device__ __forceinline__ void init(uint64_t *column, int kk, float b) {
+    col = column;
+    k = kk;
+    c = 0;
+    worst = ~0ull;
+    mr2 = b;
+    lim = b;
+  }
+  __device__ __forceinline__ static uint64_t key_of(float d, uint32_t id) {
+    return ((uint64_t)__float_as_uint(d) << 32) | (uint64_t)id;
+  }
+  // the key of a point that may go in (Range's rule d < max_range^2 first), or all ones
+  __device__ __forceinline__ uint64_t candidate(float d, uint32_t id) const {
+    if (!(d < mr2)) return ~0ull;
+    const uint64_t key = key_of(d, id);
+    return key < worst ? key : ~0ull;
+  }
+  __device__ __forceinline__ void insert_key(uint64_t key) {
+    if (key >= worst) return;
+    int j = c < k ? c : k - 1;
+    while (j > 0) {
+      const uint64_t prev = col[(j - 1) * kKnnKBlock];
+      if (prev <= key) break;
+      col[j * kKnnKBlock] = prev;
+      j--;
+    }
+    col[j * kKnnKBlock] = key;
+    if (c < k) c++;
+    if (c == k) {
+      worst = col[(k - 1) * kKnnKBlock];
+      lim = __uint_as_float((uint32_t)(worst >> 32));
+    }
+  }
+  __device__ __forceinline__ void take(float d, uint32_t id) {
+    const uint64_t key = candidate(d, id);
+    if (key != ~0ull) insert_key(key);
+  }
+  __device__ __forceinline__ void take(const float4 &p, float qx, float qy, float qz) {
+    take(ref_dist_sq(p.x, p.y, p.z, qx, qy, qz), __float_as_uint(p.w));
+  }
+  __device__ __forceinline__ void clear() {
+    c = 0;
+    worst = ~0ull;
+    lim = mr2;
+  }
+};
+
+// Exact k-nearest walk of the implicit tree (range_walk_nodes' order and frame words) with the shrinking bound
+// top.lim: a frame is pushed only if its plane can still pass and tested again when it is popped.  Each node is
+// evaluated at most once: leaves on the way down, inner nodes when their frame is popped.
+__device__ __forceinline__ void knn_walk(const TreeView &tv, uint32_t *__restrict__ stk, const int stk_stride,
+                                         const float qx, const float qy, const float qz, TopK &top) {
+  const uint32_t np1 = (uint32_t)tv.n + 1u;
+  uint32_t b = 1;
+  int32_t n = tv.n, sp = 0;
+  bool desc = true;
+  for (int64_t guard = 2 * (int64_t)tv.n + 2; guard > 0; --guard) {
+    uint32_t at = b, fw = 0;
+    if (!desc) {
+      if (sp == 0) break;
+      fw = stk[(--sp) * stk_stride];
+      at = fw & 0x07FFFFFFu;
+    }
+    const float4 nd = node_at(tv.nodes, at);
+    const int32_t depth = 31 - __clz((int)at);
+    const int dim = depth % 3;
+    const float pv = sel3(dim, nd.x, nd.y, nd.z), qv = sel3(dim, qx, qy, qz);
+    const float fp = qv - pv;
+    if (desc) {
+      if (n == 1) {  // leaf
+        top.take(nd, qx, qy, qz);
+        desc = false;
+      } else {
+        const int32_t half = n >> 1;
+        const bool go_left = n == 2 || pv > qv;
+        if (!(fp * fp > top.lim)) {
+          const uint32_t size_bit = (uint32_t)n - ((np1 >> depth) - 1u);
+          stk[(sp++) * stk_stride] = b | (go_left ? (1u << 27) : 0u) | (size_bit << 31);
+        }
+        b = 2u * b + (go_left ? 0u : 1u);
+        n = go_left ? half : n - half - 1;
+      }
+    } else {
+      if (fp * fp > top.lim) continue;  // the bound shrank since the push: the pivot and the far side are out
+      top.take(nd, qx, qy, qz);
+      const int32_t fn = (int32_t)((np1 >> depth) - 1u + (fw >> 31));
+      if (fn != 2) {
+        const bool went_left = ((fw >> 27) & 1u) != 0u;
+        const int32_t half = fn >> 1;
+        b = 2u * at + (went_left ? 1u : 0u);
+        n = went_left ? fn - half - 1 : half;
+        desc = true;
+      }
+    }
+  }
+}
+
+// The cells of row (z, y) from x0 to x1 (inclusive) as one record range of the grid.
+__device__ __forceinline__ void knn_row(const GridView &g, int z, int y, int x0, int x1, uint32_t &f, uint32_t &e) {
+  const uint32_t row = ((uint32_t)z * (uint32_t)g.ny + (uint32_t)y) * (uint32_t)g.nx;
+  f = g.start[row + (uint32_t)x0];
+  e = g.start[row + (uint32_t)x1 + 1u];
+}
+
+__device__ __forceinline__ bool box_inside(const GridBox &a, const GridBox &b) {  // a within b
+  return a.x0 >= b.x0 && a.x1 <= b.x1 && a.y0 >= b.y0 && a.y1 <= b.y1 && a.z0 >= b.z0 && a.z1 <= b.z1;
+}
+
+// The own points of a handle without a grid by id, out of the BFS slots (q == NULL)
+__global__ __launch_bounds__(256) void knn_own_points_kernel(TreeView tv, float *__restrict__ xyz) {
+  const uint32_t b = blockIdx.x * 256u + threadIdx.x;
+  if (b < 1u || b >= (1u << tv.depth)) return;
+  const uint32_t size = node_size(b, 31 - __clz((int)b), (uint32_t)tv.n + 1u);
+  if (size < 1u || size > (uint32_t)tv.n) return;  // no such node
+  const float4 nd = node_at(tv.nodes, b);
+  const uint32_t id = __float_as_uint(nd.w);
+  if (id >= (uint32_t)tv.n) return;
+  xyz[3 * (size_t)id] = nd.x;
+  xyz[3 * (size_t)id + 1] = nd.y;
+  xyz[3 * (size_t)id + 2] = nd.z;
+}
+
+template <int kSrc, bool kSor>
+__global__ __launch_bounds__(kKnnKBlock) void knearest_kernel(GridView g, TreeView tv, XTreeView xv, KnnQuery Q, int32_t k,
+                                                              float mr2, KnnOut O, int64_t guard) {
+  extern __shared__ uint64_t s_knn[];  // [k][64] keys, then the walk's frames [levels][64]
+  uint32_t *s_stack = reinterpret_cast<uint32_t *>(s_knn + (size_t)k * kKnnKBlock);
+  const int lane = (int)(threadIdx.x & 63u);
+  const uint32_t n_tiles = (uint32_t)((Q.nq + kKnnKBlock - 1) / kKnnKBlock);
+  const int64_t pos = (int64_t)xcd_tile(blockIdx.x, n_tiles) * kKnnKBlock + threadIdx.x;
+  // (the grid path keeps every lane of the wave to the end: fat rows are scanned by all 64)
+  const bool live = pos < Q.nq;
+  if (kSrc != kRangeGrid && !live) return;
+  int64_t i = 0;
+  float qx = 0.0f, qy = 0.0f, qz = 0.0f;
+  if (live) {
+    if (Q.own) {
+      const float4 r = Q.own[pos];
+      i = (int64_t)__float_as_uint(r.w);
+      qx = r.x; qy = r.y; qz = r.z;
+    } else {
+      i = Q.perm ? (int64_t)Q.perm[pos] : pos;
+      qx = Q.q[3 * i]; qy = Q.q[3 * i + 1]; qz = Q.q[3 * i + 2];
+    }
+  }
+  const bool finite = isfinite(qx) && isfinite(qy) && isfinite(qz);  // else: nothing (no DistSq compares below B)
+  TopK top;
+  top.init(s_knn + lane, k, mr2);
+  if constexpr (kSrc == kRangeGrid) {
+    bool active = live && finite, walk = false;
+    GridBox box;  // scanned so far; empty at first (z1 < z0)
+    box.x0 = box.y0 = box.z0 = 1;
+    box.x1 = box.y1 = box.z1 = 0;
+    const int cx = grid_cell(qx, g.lo[0], g.inv_h, g.nx), cy = grid_cell(qy, g.lo[1], g.inv_h, g.ny),
+              cz = grid_cell(qz, g.lo[2], g.inv_h, g.nz);
+    GridBox nb;  // the box after this round's shell
+    nb.x0 = max(cx - 1, 0); nb.x1 = min(cx + 1, g.nx - 1);
+    nb.y0 = max(cy - 1, 0); nb.y1 = min(cy + 1, g.ny - 1);
+    nb.z0 = max(cz - 1, 0); nb.z1 = min(cz + 1, g.nz - 1);
+    // every round: each active lane scans the shell nb \ box (up to two fat rows set aside), the wave scans the fat
+    // rows, each lane checks its certificate and picks the next shell, or leaves for the walk
+    while (__ballot(active) != 0ull) {
+      uint32_t fat_f0 = 0u, fat_e0 = 0u, fat_f1 = 0u, fat_e1 = 0u;
+      int nfat = 0;
+      if (active) {
+        for (int z = nb.z0; z <= nb.z1; z++) {
+          for (int y = nb.y0; y <= nb.y1; y++) {
+            const bool inner = z >= box.z0 && z <= box.z1 && y >= box.y0 && y <= box.y1;
+            // a row inside the old box in y and z: only its new ends; else the whole row
+            for (int part = 0; part < 2; part++) {
+              int x0, x1;
+              if (!inner) {
+                if (part == 1) break;
+                x0 = nb.x0; x1 = nb.x1;
+              } else {
+                x0 = part == 0 ? nb.x0 : box.x1 + 1;
+                x1 = part == 0 ? box.x0 - 1 : nb.x1;
+              }
+              if (x0 > x1) continue;
+              uint32_t f, e;
+              knn_row(g, z, y, x0, x1, f, e);
+              if (e > f && e - f >= kRangeFatRow && nfat < 2) {
+                if (nfat == 0) { fat_f0 = f; fat_e0 = e; }
+                else { fat_f1 = f; fat_e1 = e; }
+                nfat++;
+                continue;
+              }
+              for (; f < e; f++) top.take(g.pts[f], qx, qy, qz);
+            }
+          }
+        }
+      }
+      if (__ballot(nfat > 0) != 0ull) {
+        for (int fk = 0; fk < 2; fk++) {
+          unsigned long long owners = __ballot(nfat > fk);
+          while (owners != 0ull) {  // uniform
+            const int owner = __builtin_ctzll(owners);
+            owners &= owners - 1ull;
+            const float ox = __shfl(qx, owner), oy = __shfl(qy, owner), oz = __shfl(qz, owner);
+            const uint32_t rf = __shfl(fk == 0 ? fat_f0 : fat_f1, owner), re = __shfl(fk == 0 ? fat_e0 : fat_e1, owner);
+            for (uint32_t base = rf; base < re; base += 64u) {  // uniform
+              const uint32_t ow_lo = (uint32_t)__shfl((int)(uint32_t)top.worst, owner);
+              const uint32_t ow_hi = (uint32_t)__shfl((int)(uint32_t)(top.worst >> 32), owner);
+              const uint64_t ow = ((uint64_t)ow_hi << 32) | ow_lo;
+              uint64_t key = ~0ull;
+              const uint32_t r = base + (uint32_t)lane;
+              if (r < re) {
+                const float4 p = g.pts[r];
+                const float d = ref_dist_sq(p.x, p.y, p.z, ox, oy, oz);
+                if (d < mr2) {
+                  const uint64_t kk = TopK::key_of(d, __float_as_uint(p.w));
+                  key = kk < ow ? kk : ~0ull;
+                }
+              }
+              unsigned long long cand = __ballot(key != ~0ull);
+              while (cand != 0ull) {  // uniform; the owner inserts (and drops what its k-th key no longer admits)
+                const int l = __builtin_ctzll(cand);
+                cand &= cand - 1ull;
+                const uint32_t lo = (uint32_t)__shfl((int)(uint32_t)key, l);
+                const uint32_t hi = (uint32_t)__shfl((int)(uint32_t)(key >> 32), l);
+                if (lane == owner) top.insert_key(((uint64_t)hi << 32) | lo);
+              }
+            }
+          }
+        }
+      }
+      if (active) {
+        const GridBox cov = grid_cover(g, qx, qy, qz, top.lim);
+        box = nb;
+        if (box_inside(cov, box)) {
+          active = false;
+        } else {
+          // grow towards the cover, one cell per side a round while fewer than k are held (the cover is then the
+          // whole of max_range), straight to it once d_k is known
+          const bool full = top.c == top.k;
+          nb.x0 = cov.x0 < box.x0 ? (full ? cov.x0 : max(cov.x0, box.x0 - 1)) : box.x0;
+          nb.y0 = cov.y0 < box.y0 ? (full ? cov.y0 : max(cov.y0, box.y0 - 1)) : box.y0;
+          nb.z0 = cov.z0 < box.z0 ? (full ? cov.z0 : max(cov.z0, box.z0 - 1)) : box.z0;
+          nb.x1 = cov.x1 > box.x1 ? (full ? cov.x1 : min(cov.x1, box.x1 + 1)) : box.x1;
+          nb.y1 = cov.y1 > box.y1 ? (full ? cov.y1 : min(cov.y1, box.y1 + 1)) : box.y1;
+          nb.z1 = cov.z1 > box.z1 ? (full ? cov.z1 : min(cov.z1, box.z1 + 1)) : box.z1;
+          if (nb.x0 < cx - kGridWide || nb.x1 > cx + kGridWide || nb.y0 < cy - kGridWide || nb.y1 > cy + kGridWide ||
+              nb.z0 < cz - kGridWide || nb.z1 > cz + kGridWide) {
+            active = false;
+            walk = true;
+          }
+        }
+      }
+    }
+    if (!live) return;
+    if (walk) {  // the box would leave kGridWide: the implicit tree, from nothing
+      top.clear();
+      knn_walk(tv, s_stack + threadIdx.x, kKnnKBlock, qx, qy, qz, top);
+    }
+  } else if constexpr (kSrc == kRangeWalk) {
+    if (finite) knn_walk(tv, s_stack + threadIdx.x, kKnnKBlock, qx, qy, qz, top);
+  } else {
+    if (finite) {
+      auto hit = [&](const float4 &nd, float d) {
+        top.take(d, __float_as_uint(nd.w));
+        return true;
+      };
+      xwalk(xv, s_stack + threadIdx.x, kKnnKBlock, qx, qy, qz, guard, [&]() { return top.lim; }, hit, hit);
+    }
+  }
+  if constexpr (kSor) {
+    // the first mean_k entries other than the query's own id, float64 in ascending order
+    double sum = 0.0;
+    int taken = 0;
+    bool self = false;
+    for (int s = 0; s < top.c && taken < O.mean_k; s++) {
+      const uint64_t key = top.col[s * kKnnKBlock];
+      if (!self && (int64_t)(uint32_t)key == i) {
+        self = true;
+        continue;
+      }
+      sum += sqrt((double)__uint_as_float((uint32_t)(key >> 32)));
+      taken++;
+    }
+    O.mean[i] = sum / (double)O.mean_k;
+  } else {
+    const int64_t row = i * (int64_t)k;
+    for (int s = 0; s < k; s++) {
+      int32_t id = -1;
+      float d = mr2;
+      if (s < top.c) {
+        const uint64_t key = top.col[s * kKnnKBlock];
+        id = (int32_t)(uint32_t)key;
+        d = __uint_as_float((uint32_t)(key >> 32));
+      }
+      O.ids[row + s] = id;
+      O.dsq[row + s] = d;
+    }
+  }
+  if (O.counts) O.counts[i] = top.c;
+}
+
+template <bool kSor>
+pcgx_status knearest_launch(const pcgx_kdtree *t, const float *d_q, int64_t nq, int32_t k, float max_range,
+                            const KnnOut &O, hipStream_t st) {
+  Arena &ar = ctx().arena;
+  PCGX_TRY(ar.begin(st));
+  const RangeSrc src = range_source(t);  // as pcgx_kdtree_range_count takes it
+  XTreeView xv{};
+  if (src == kRangeXWalk) PCGX_TRY(xtree_view(t, &xv, st));
+  const TreeView tv = t->view();
+  KnnQuery Q{d_q, nullptr, nullptr, nq};
+  if (!d_q) {  // the tree's own points, Len() of them, deleted ones included
+    if (t->grid_ok) {
+      Q.own = t->grid.pts;  // cell order
+    } else if (src == kRangeXWalk) {
+      Q.q = t->d_xsrc;  // by id (xtree_view made it)
+    } else {
+      float *xyz = nullptr;
+      PCGX_TRY(ar.alloc_n((size_t)nq * 3, &xyz));
+      const unsigned slots = 1u << tv.depth;
+      hipLaunchKernelGGL(knn_own_points_kernel, dim3((slots + 255u) / 256u), dim3(256), 0, st, tv, xyz);
+      PCGX_HIP_TRY(hipGetLastError());
+      Q.q = xyz;
+    }
+  }
+  if (!Q.own && nq >= kKnnPresortMin) {
+    int32_t *perm = nullptr;
+    PCGX_TRY(ar.alloc_n((size_t)nq, &perm));
+    PCGX_TRY(morton_order(Q.q, nq, t->bbox_lo, t->bbox_hi, perm, st));
+    Q.perm = perm;
+  }
+  const float mr2 = max_range * max_range;
+  const dim3 grid(xcd_grid((unsigned)((nq + kKnnKBlock - 1) / kKnnKBlock))), block(kKnnKBlock);
+  const int64_t guard = 4 * t->n + 8;
+  const size_t list_bytes = (size_t)k * kKnnKBlock * sizeof(uint64_t);
+  if (src == kRangeXWalk) {
+    const size_t lds = list_bytes + (size_t)(xv.depth > 0 ? xv.depth : 1) * kKnnKBlock * sizeof(uint32_t);
+    hipLaunchKernelGGL((knearest_kernel<kRangeXWalk, kSor>), grid, block, lds, st, GridView{}, tv, xv, Q, k, mr2, O, guard);
+  } else if (src == kRangeGrid) {
+    hipLaunchKernelGGL((knearest_kernel<kRangeGrid, kSor>), grid, block, list_bytes + walk_stack_bytes(tv, kKnnKBlock), st,
+                       t->grid, tv, xv, Q, k, mr2, O, guard);
+  } else {
+    hipLaunchKernelGGL((knearest_kernel<kRangeWalk, kSor>), grid, block, list_bytes + walk_stack_bytes(tv, kKnnKBlock), st,
+                       GridView{}, tv, xv, Q, k, mr2, O, guard);
+  }
+  PCGX_HIP_TRY(hipGetLastError());
+  return PCGX_OK;
+}
+
+pcgx_status knearest_sor_enqueue(const pcgx_kdtree *t, int32_t mean_k, double *d_mean, hipStream_t st) {
+  KnnOut O{nullptr, nullptr, nullptr, d_mean, mean_k};
+  return knearest_launch<true>(t, nullptr, t->n, mean_k + 1, __builtin_inff(), O, st);
+}
+
+}  // namespace pcgx
+
+using namespace pcgx;
+
+namespace {
+
+pcgx_status knearest_check(const char *fn, const pcgx_kdtree *t, const float *q, int64_t nq, int32_t k, float max_range,
+                           const void *ids, const void *dist_sq) {
+  if (!t || nq < 0) return fail(PCGX_E_INVALID, "%s: bad argument", fn);
+  if (k < 1 || k > kKnnMaxK) return fail(PCGX_E_INVALID, "%s: k = %d outside [1, %d]", fn, (int)k, kKnnMaxK);
+  if (!(max_range >= 0.0f)) return fail(PCGX_E_INVALID, "%s: max_range must be >= 0 or +inf", fn);
+  if (!q && nq != t->n) return fail(PCGX_E_INVALID, "%s: q == NULL takes the tree's own points: nq must equal Len()", fn);
+  if (nq > 0 && (!ids || !dist_sq)) return fail(PCGX_E_INVALID, "%s: NULL ids / dist_sq", fn);
+  return PCGX_OK;
+}
+
+}  // namespace
+
+extern "C" pcgx_status pcgx_kdtree_knearest_dev(const pcgx_kdtree *t, const float *d_q, int64_t nq, int32_t k,
+                                                float max_range, int32_t *d_ids, float *d_dist_sq, int32_t *d_counts,
+                                                void *stream) {
+  PCGX_API_LOCK();
+  PCGX_TRY(knearest_check("pcgx_kdtree_knearest_dev", t, d_q, nq, k, max_range, d_ids, d_dist_sq));
+  if (nq == 0) return PCGX_OK;
+  PCGX_TRY(ensure_init());
+  KnnOut O{d_ids, d_dist_sq, d_counts, nullptr, 0};
+  return knearest_launch<false>(t, d_q, nq, k, max_range, O, pick_stream(stream));
+}
+
+extern "C" pcgx_status pcgx_kdtree_knearest(const pcgx_kdtree *t, const float *q, int64_t nq, int32_t k, float max_range,
+                                            int64_t *ids, float *dist_sq, int32_t *counts) {
+  PCGX_API_CALL();
+  PCGX_TRY(knearest_check("pcgx_kdtree_knearest", t, q, nq, k, max_range, ids, dist_sq));
+  if (nq == 0) return PCGX_OK;
+  PCGX_TRY(ensure_init());
+  hipStream_t st = ctx().stream;
+  Arena &ha = ctx().host_arena;
+  PCGX_TRY(ha.begin(st));
+  const size_t slots = (size_t)nq * (size_t)k;
+  float *d_q = nullptr, *d_d = nullptr;
+  int32_t *d_i = nullptr, *d_c = nullptr;
+  if (q) {
+    PCGX_TRY(ha.alloc_n((size_t)nq * 3, &d_q));
+    PCGX_TRY(staged_upload(d_q, q, (size_t)nq * 12, st));
+  }
+  PCGX_TRY(ha.alloc_n(slots, &d_i));
+  PCGX_TRY(ha.alloc_n(slots, &d_d));
+  if (counts) PCGX_TRY(ha.alloc_n((size_t)nq, &d_c));
+  PCGX_TRY(pcgx_kdtree_knearest_dev(t, d_q, nq, k, max_range, d_i, d_d, d_c, st));
+  // int32 on the device, int64 in the ABI (as Nearest's): widened in place from the back
+  PCGX_TRY(staged_download(ids, d_i, slots * 4, st));
+  const int32_t *narrow = reinterpret_cast<const int32_t *>(ids);
+  for (size_t s = slots; s-- > 0;) ids[s] = (int64_t)narrow[s];
+  PCGX_TRY(staged_download(dist_sq, d_d, slots * 4, st));
+  if (counts) PCGX_TRY(staged_download(counts, d_c, (size_t)nq * 4, st));
+  return PCGX_OK;
+}

@@ -12,6 +12,7 @@
 //   pcgx::sac::SAC          <- pc/sac.SAC over NewVoxelGridSurfaceModel (the plane model of a BucketVoxelGrid)
 //   pcgx::PointToPlaneICP   <- (extension, no counterpart in the reference) the same Fit shape with
 //                              the point-to-plane evaluator / Gauss-Newton updater, HasHessian() == true
+//   pcgx::StatisticalOutlierRemoval <- (extension, no counterpart) a filter.Filter on k-nearest distances
 //   pcgx::Comm              <- (no counterpart: the reference is one process) the exchange of the
 //                              several-GPU paths: PointToPointICP::FitSharded, VoxelGrid::FilterSharded
 #pragma once
@@ -164,6 +165,26 @@ class KDTree {  // pc/storage/kdtree/kdtree.go:14-23
                               n ? r.normals[0].data() : nullptr, r.curvature.data(), r.counts.data()));
     return r;
   }
+  // The k points with the smallest (DistSq, ID) among those with DistSq < maxRange^2, ascending (extension: no
+  // reference parity; include/pcgx.h, pcgx_kdtree_knearest: ties go by ID).
+  std::vector<Neighbor> KNearest(const Vec3 &p, int32_t k, float maxRange) const {
+    return KNearestBatch({p}, k, maxRange)[0];
+  }
+  // ... for every query; an empty `queries` takes the tree's own points (result in id order).
+  std::vector<std::vector<Neighbor>> KNearestBatch(const std::vector<Vec3> &queries, int32_t k, float maxRange) const {
+    const bool own = queries.empty();
+    const int64_t n = own ? Len() : (int64_t)queries.size();
+    std::vector<int64_t> ids((size_t)(n * (k > 0 ? k : 0)));
+    std::vector<float> d(ids.size());
+    std::vector<int32_t> counts((size_t)n);
+    check(pcgx_kdtree_knearest(h_.get(), own ? nullptr : queries[0].data(), n, k, maxRange, ids.data(), d.data(),
+                               counts.data()));
+    std::vector<std::vector<Neighbor>> out((size_t)n);
+    for (int64_t i = 0; i < n; i++)
+      for (int32_t s = 0; s < counts[(size_t)i]; s++)
+        out[(size_t)i].push_back(Neighbor{ids[(size_t)(i * k + s)], d[(size_t)(i * k + s)]});
+    return out;
+  }
   const pcgx_kdtree *handle() const { return h_.get(); }
 
  private:
@@ -192,6 +213,30 @@ class VoxelGrid {  // pc/filter/voxelgrid/voxelgrid.go:23-33 + option.go:14-18
     int64_t m = 0;
     check(pcgx_voxel_filter_sharded(comm.handle(), c.data, c.points, c.stride, c.xyz_offset, LeafSize.data(),
                                     ChunkSize.data(), out.data(), &m));
+    out.resize((size_t)m * c.stride);
+    return out;
+  }
+};
+
+// Statistical outlier removal (extension: no reference counterpart; PCL's StatisticalOutlierRemoval) in the shape of
+// filter.Filter (include/pcgx.h, pcgx_sor_filter).  Keeps the points whose mean distance to their MeanK nearest
+// others is at most mu + StddevMul * sigma (WithNegative(true): the others); non-finite points are dropped.
+class StatisticalOutlierRemoval {
+ public:
+  int32_t MeanK;
+  float StddevMul;
+  bool Negative = false;
+  std::vector<double> MeanDist;  // after Filter: by input index, NaN for non-finite points
+  std::array<double, 3> Stats{0.0, 0.0, 0.0};  // after Filter: {mu, sigma, threshold}
+  StatisticalOutlierRemoval(int32_t meanK, float stddevMul) : MeanK(meanK), StddevMul(stddevMul) {}
+  StatisticalOutlierRemoval &WithNegative(bool negative) { Negative = negative; return *this; }
+  // Filter: returns the kept records in input order (Width = size()/stride, Height = 1).
+  std::vector<uint8_t> Filter(const CloudView &c) {
+    std::vector<uint8_t> out((size_t)c.points * c.stride);
+    MeanDist.assign((size_t)c.points, 0.0);
+    int64_t m = 0;
+    check(pcgx_sor_filter(c.data, c.points, c.stride, c.xyz_offset, MeanK, StddevMul, Negative ? 1 : 0, out.data(), &m,
+                          MeanDist.data(), Stats.data()));
     out.resize((size_t)m * c.stride);
     return out;
   }

@@ -1,6 +1,6 @@
 """pc/storage/kdtree mirror: KDTree on the GPU behind the storage.Search shape
-(pc/storage/search.go:13-17): Vec3At / Len / Nearest, plus batched NearestBatch, and surface
-normals (Normals, an extension with no reference counterpart)."""
+(pc/storage/search.go:13-17): Vec3At / Len / Nearest, plus batched NearestBatch, and two extensions with no
+reference counterpart: surface normals (Normals) and k nearest neighbours (KNearest)."""
 import ctypes as C
 
 import numpy as np
@@ -169,6 +169,36 @@ class KDTree:
             self._h, L.ptr(int(d_q)) if d_q else None, int(nq), float(radius), L.ptr(vp), int(MinNeighbors),
             L.ptr(int(d_normals)), L.ptr(int(d_curvature)) if d_curvature else None,
             L.ptr(int(d_counts)) if d_counts else None, L.ptr(stream) if stream else None))
+
+    # -- extension (no reference parity): k nearest neighbours
+    def KNearest(self, p, k, maxRange):
+        """The k points with the smallest (DistSq, ID) among those with DistSq < maxRange^2, ascending ->
+        [Neighbor] of length <= k (include/pcgx.h, pcgx_kdtree_knearest: ties go by ID)."""
+        ids, dsq, counts = self.KNearestBatch(np.asarray(p, np.float32).reshape(1, 3), k, maxRange)
+        return [Neighbor(i, d) for i, d in zip(ids[0, :counts[0]], dsq[0, :counts[0]])]
+
+    def KNearestBatch(self, q, k, maxRange):
+        """KNearest for every row of q (None: the tree's own points, in id order) -> (ids int64 (n, k),
+        distSq float32 (n, k), counts int32 (n,)); slots past counts[i] are {-1, maxRange^2}."""
+        q = None if q is None else L.f32c(q).reshape(-1, 3)
+        n = self.Len() if q is None else len(q)
+        ids = np.empty((n, k), np.int64)
+        dsq = np.empty((n, k), np.float32)
+        counts = np.empty(n, np.int32)
+        L.check(L.lib().pcgx_kdtree_knearest(self._h, L.ptr(q), n, int(k), float(maxRange), L.ptr(ids), L.ptr(dsq),
+                                             L.ptr(counts)))
+        return ids, dsq, counts
+
+    def KNearestDev(self, k, maxRange, d_ids, d_dsq, d_counts=0, d_q=0, nq=None, stream=0):
+        """Device-resident KNearestBatch: raw device addresses (e.g. torch .data_ptr()); ids int32 [nq * k]; d_q 0
+        takes the tree's own points (nq = Len()).  Enqueued on `stream`, returns without waiting."""
+        if nq is None:
+            if d_q:
+                raise ValueError("nq is required with d_q")
+            nq = self.Len()
+        L.check(L.lib().pcgx_kdtree_knearest_dev(
+            self._h, L.ptr(int(d_q)) if d_q else None, int(nq), int(k), float(maxRange), L.ptr(int(d_ids)),
+            L.ptr(int(d_dsq)), L.ptr(int(d_counts)) if d_counts else None, L.ptr(stream) if stream else None))
 
     def NearestBatchDev(self, d_q, nq, maxRange, d_ids, d_dsq, presort=True, stream=0):
         """Device-resident variant: raw device addresses (e.g. torch .data_ptr())."""
