@@ -1055,7 +1055,7 @@ static pcgx_status enqueue_corr_patched(pcgx_icp_session *s, hipStream_t st) {
   XTreeView xv;
   PCGX_TRY(xtree_view(s->base, &xv, st));
   const size_t lds = (size_t)(xv.depth > 1 ? xv.depth : 2) * kIcpBlock * sizeof(uint32_t);
-  const int64_t guard = 4 * s->base->n + 8;
+  const int64_t guard = xwalk_guard(s->base->n);
   const float *x = s->d_xyz, *y = s->d_xyz + s->nt, *z = s->d_xyz + 2 * s->nt;
   ProfScope prof(PCGX_PROF_ICP_WALK, st);
   if (s->plane)

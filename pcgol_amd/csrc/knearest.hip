@@ -12,15 +12,16 @@
 // pcgx_kdtree_range_count takes them (range_source, range_enum.h):
 //   grid  (kRangeGrid): the 3 x 3 x 3 cells around the query, then shells; accepted when grid_cover(min(d_k, B)) lies
 //         inside the box scanned (the certificate knn_grid.h uses for k = 1).  A box beyond kGridWide cells of the
-//         query's own cell goes to the implicit-tree walk below, in the same lane.  Rows of kRangeFatRow records and
-//         more (a site of the cloud taken thousands of times) are scanned by the whole wave, the owner inserting what
-//         beats its k-th key.
-//   walk  (kRangeWalk: no grid, PCGX_RANGE_WALK=1): the implicit tree, a side pruned when fromPivotSq > min(d_k, B)
-//         (strict: an equal-DistSq point with a smaller id may lie beyond the plane), re-tested when a frame is popped;
+//         query's own cell goes to the implicit-tree walk below, in the same lane.  The shells' rows are scanned as
+//         Range's are (RowScan, range_enum.h): rows of kRangeFatRow records and more (a site of the cloud taken
+//         thousands of times) by the whole wave, the owner inserting what beats its k-th key.
+//   walk  (kRangeWalk: no grid, PCGX_RANGE_WALK=1): range_walk_nodes over the implicit tree, hits on B, a side pruned
+//         when fromPivotSq > min(d_k, B) (strict: an equal-DistSq point with a smaller id may lie beyond the plane),
+//         re-tested when a frame is popped;
 //   xwalk (kRangeXWalk: a handle that has seen DeletePoint): the patched tree's walk (knn_xwalk.h), same pruning.
-// Non-finite queries find nothing (no DistSq of theirs compares below B).  Queries: the caller's (Morton-ordered from
-// kKnnPresortMin on), or the tree's own points (q == NULL) in the grid's cell order.  SOR mode writes no ids: only the
-// mean of sqrt(DistSq) over the first mean_k entries other than the query's own id, in float64 (sor.hip).
+// Non-finite queries find nothing (no DistSq of theirs compares below B).  Queries: the caller's, or the tree's own
+// points (q == NULL), as query_source (range_enum.h) lays them out.  SOR mode writes no ids: only the mean of
+// sqrt(DistSq) over the first mean_k entries other than the query's own id, in float64 (sor.hip).
 #include <math.h>
 #include <stdlib.h>
 
@@ -31,15 +32,7 @@
 namespace pcgx {
 
 constexpr int kKnnKBlock = kRangeWalkBlock;  // one wave per workgroup: the top-k lists and walk stacks are [.][64] in LDS
-constexpr int64_t kKnnPresortMin = 16384;    // caller batches from this size on run in Morton order (as Range's)
 constexpr int kKnnMaxK = 64;
-
-struct KnnQuery {
-  const float *q;
-  const int32_t *perm;
-  const float4 *own;  // {x, y, z, bits(id)}: the tree's own points in cell order, else nullptr
-  int64_t nq;
-};
 
 struct KnnOut {
   int32_t *ids;      // [nq * k] (not SOR)
@@ -104,83 +97,8 @@ struct TopK {
   }
 };
 
-// Exact k-nearest walk of the implicit tree (range_walk_nodes' order and frame words) with the shrinking bound
-// top.lim: a frame is pushed only if its plane can still pass and tested again when it is popped.  Each node is
-// evaluated at most once: leaves on the way down, inner nodes when their frame is popped.
-__device__ __forceinline__ void knn_walk(const TreeView &tv, uint32_t *__restrict__ stk, const int stk_stride,
-                                         const float qx, const float qy, const float qz, TopK &top) {
-  const uint32_t np1 = (uint32_t)tv.n + 1u;
-  uint32_t b = 1;
-  int32_t n = tv.n, sp = 0;
-  bool desc = true;
-  for (int64_t guard = 2 * (int64_t)tv.n + 2; guard > 0; --guard) {
-    uint32_t at = b, fw = 0;
-    if (!desc) {
-      if (sp == 0) break;
-      fw = stk[(--sp) * stk_stride];
-      at = fw & 0x07FFFFFFu;
-    }
-    const float4 nd = node_at(tv.nodes, at);
-    const int32_t depth = 31 - __clz((int)at);
-    const int dim = depth % 3;
-    const float pv = sel3(dim, nd.x, nd.y, nd.z), qv = sel3(dim, qx, qy, qz);
-    const float fp = qv - pv;
-    if (desc) {
-      if (n == 1) {  // leaf
-        top.take(nd, qx, qy, qz);
-        desc = false;
-      } else {
-        const int32_t half = n >> 1;
-        const bool go_left = n == 2 || pv > qv;
-        if (!(fp * fp > top.lim)) {
-          const uint32_t size_bit = (uint32_t)n - ((np1 >> depth) - 1u);
-          stk[(sp++) * stk_stride] = b | (go_left ? (1u << 27) : 0u) | (size_bit << 31);
-        }
-        b = 2u * b + (go_left ? 0u : 1u);
-        n = go_left ? half : n - half - 1;
-      }
-    } else {
-      if (fp * fp > top.lim) continue;  // the bound shrank since the push: the pivot and the far side are out
-      top.take(nd, qx, qy, qz);
-      const int32_t fn = (int32_t)((np1 >> depth) - 1u + (fw >> 31));
-      if (fn != 2) {
-        const bool went_left = ((fw >> 27) & 1u) != 0u;
-        const int32_t half = fn >> 1;
-        b = 2u * at + (went_left ? 1u : 0u);
-        n = went_left ? fn - half - 1 : half;
-        desc = true;
-      }
-    }
-  }
-}
-
-// The cells of row (z, y) from x0 to x1 (inclusive) as one record range of the grid.
-__device__ __forceinline__ void knn_row(const GridView &g, int z, int y, int x0, int x1, uint32_t &f, uint32_t &e) {
-  const uint32_t row = ((uint32_t)z * (uint32_t)g.ny + (uint32_t)y) * (uint32_t)g.nx;
-  f = g.start[row + (uint32_t)x0];
-  e = g.start[row + (uint32_t)x1 + 1u];
-}
-
-__device__ __forceinline__ bool box_inside(const GridBox &a, const GridBox &b) {  // a within b
-  return a.x0 >= b.x0 && a.x1 <= b.x1 && a.y0 >= b.y0 && a.y1 <= b.y1 && a.z0 >= b.z0 && a.z1 <= b.z1;
-}
-
-// The own points of a handle without a grid by id, out of the BFS slots (q == NULL)
-__global__ __launch_bounds__(256) void knn_own_points_kernel(TreeView tv, float *__restrict__ xyz) {
-  const uint32_t b = blockIdx.x * 256u + threadIdx.x;
-  if (b < 1u || b >= (1u << tv.depth)) return;
-  const uint32_t size = node_size(b, 31 - __clz((int)b), (uint32_t)tv.n + 1u);
-  if (size < 1u || size > (uint32_t)tv.n) return;  // no such node
-  const float4 nd = node_at(tv.nodes, b);
-  const uint32_t id = __float_as_uint(nd.w);
-  if (id >= (uint32_t)tv.n) return;
-  xyz[3 * (size_t)id] = nd.x;
-  xyz[3 * (size_t)id + 1] = nd.y;
-  xyz[3 * (size_t)id + 2] = nd.z;
-}
-
 template <int kSrc, bool kSor>
-__global__ __launch_bounds__(kKnnKBlock) void knearest_kernel(GridView g, TreeView tv, XTreeView xv, KnnQuery Q, int32_t k,
+__global__ __launch_bounds__(kKnnKBlock) void knearest_kernel(GridView g, TreeView tv, XTreeView xv, QuerySource Q, int32_t k,
                                                               float mr2, KnnOut O, int64_t guard) {
   extern __shared__ uint64_t s_knn[];  // [k][64] keys, then the walk's frames [levels][64]
   uint32_t *s_stack = reinterpret_cast<uint32_t *>(s_knn + (size_t)k * kKnnKBlock);
@@ -192,19 +110,15 @@ __global__ __launch_bounds__(kKnnKBlock) void knearest_kernel(GridView g, TreeVi
   if (kSrc != kRangeGrid && !live) return;
   int64_t i = 0;
   float qx = 0.0f, qy = 0.0f, qz = 0.0f;
-  if (live) {
-    if (Q.own) {
-      const float4 r = Q.own[pos];
-      i = (int64_t)__float_as_uint(r.w);
-      qx = r.x; qy = r.y; qz = r.z;
-    } else {
-      i = Q.perm ? (int64_t)Q.perm[pos] : pos;
-      qx = Q.q[3 * i]; qy = Q.q[3 * i + 1]; qz = Q.q[3 * i + 2];
-    }
-  }
+  if (live) read_query(Q, pos, i, qx, qy, qz);
   const bool finite = isfinite(qx) && isfinite(qy) && isfinite(qz);  // else: nothing (no DistSq compares below B)
   TopK top;
   top.init(s_knn + lane, k, mr2);
+  // the implicit tree: hits on max_range^2 (TopK applies the key test), pruned on the shrinking min(d_k, B)
+  auto walk_tree = [&]() {
+    range_walk_nodes<true>(tv, s_stack + threadIdx.x, kKnnKBlock, qx, qy, qz, mr2, [&]() { return top.lim; },
+                           [&](const float4 &nd, float d) { top.take(d, __float_as_uint(nd.w)); });
+  };
   if constexpr (kSrc == kRangeGrid) {
     bool active = live && finite, walk = false;
     GridBox box;  // scanned so far; empty at first (z1 < z0)
@@ -216,73 +130,52 @@ __global__ __launch_bounds__(kKnnKBlock) void knearest_kernel(GridView g, TreeVi
     nb.x0 = max(cx - 1, 0); nb.x1 = min(cx + 1, g.nx - 1);
     nb.y0 = max(cy - 1, 0); nb.y1 = min(cy + 1, g.ny - 1);
     nb.z0 = max(cz - 1, 0); nb.z1 = min(cz + 1, g.nz - 1);
+    // (one record at a time: four in flight take 68 VGPRs, occupancy 7 instead of 8)
+    auto take = [&](const float4 &p) { top.take(p, qx, qy, qz); };
+    // the owner of a fat row inserts what beats its k-th key, 64 records at a time
+    auto fat = [&](int owner, uint32_t rf, uint32_t re, float ox, float oy, float oz) {
+      for (uint32_t base = rf; base < re; base += 64u) {  // uniform
+        const uint32_t ow_lo = (uint32_t)__shfl((int)(uint32_t)top.worst, owner);
+        const uint32_t ow_hi = (uint32_t)__shfl((int)(uint32_t)(top.worst >> 32), owner);
+        const uint64_t ow = ((uint64_t)ow_hi << 32) | ow_lo;
+        uint64_t key = ~0ull;
+        const uint32_t r = base + (uint32_t)lane;
+        if (r < re) {
+          const float4 p = g.pts[r];
+          const float d = ref_dist_sq(p.x, p.y, p.z, ox, oy, oz);
+          if (d < mr2) {
+            const uint64_t kk = TopK::key_of(d, __float_as_uint(p.w));
+            key = kk < ow ? kk : ~0ull;
+          }
+        }
+        unsigned long long cand = __ballot(key != ~0ull);
+        while (cand != 0ull) {  // uniform; the owner inserts (and drops what its k-th key no longer admits)
+          const int l = __builtin_ctzll(cand);
+          cand &= cand - 1ull;
+          const uint32_t lo = (uint32_t)__shfl((int)(uint32_t)key, l);
+          const uint32_t hi = (uint32_t)__shfl((int)(uint32_t)(key >> 32), l);
+          if (lane == owner) top.insert_key(((uint64_t)hi << 32) | lo);
+        }
+      }
+    };
     // every round: each active lane scans the shell nb \ box (up to two fat rows set aside), the wave scans the fat
     // rows, each lane checks its certificate and picks the next shell, or leaves for the walk
     while (__ballot(active) != 0ull) {
-      uint32_t fat_f0 = 0u, fat_e0 = 0u, fat_f1 = 0u, fat_e1 = 0u;
-      int nfat = 0;
+      RowScan rows;
       if (active) {
         for (int z = nb.z0; z <= nb.z1; z++) {
           for (int y = nb.y0; y <= nb.y1; y++) {
             const bool inner = z >= box.z0 && z <= box.z1 && y >= box.y0 && y <= box.y1;
             // a row inside the old box in y and z: only its new ends; else the whole row
-            for (int part = 0; part < 2; part++) {
-              int x0, x1;
-              if (!inner) {
-                if (part == 1) break;
-                x0 = nb.x0; x1 = nb.x1;
-              } else {
-                x0 = part == 0 ? nb.x0 : box.x1 + 1;
-                x1 = part == 0 ? box.x0 - 1 : nb.x1;
-              }
-              if (x0 > x1) continue;
-              uint32_t f, e;
-              knn_row(g, z, y, x0, x1, f, e);
-              if (e > f && e - f >= kRangeFatRow && nfat < 2) {
-                if (nfat == 0) { fat_f0 = f; fat_e0 = e; }
-                else { fat_f1 = f; fat_e1 = e; }
-                nfat++;
-                continue;
-              }
-              for (; f < e; f++) top.take(g.pts[f], qx, qy, qz);
+            for (int part = 0; part < (inner ? 2 : 1); part++) {
+              const int x0 = inner && part == 1 ? box.x1 + 1 : nb.x0;
+              const int x1 = inner && part == 0 ? box.x0 - 1 : nb.x1;
+              if (x0 <= x1) rows.row<1>(g, grid_row(g, z, y, x0, x1), take);
             }
           }
         }
       }
-      if (__ballot(nfat > 0) != 0ull) {
-        for (int fk = 0; fk < 2; fk++) {
-          unsigned long long owners = __ballot(nfat > fk);
-          while (owners != 0ull) {  // uniform
-            const int owner = __builtin_ctzll(owners);
-            owners &= owners - 1ull;
-            const float ox = __shfl(qx, owner), oy = __shfl(qy, owner), oz = __shfl(qz, owner);
-            const uint32_t rf = __shfl(fk == 0 ? fat_f0 : fat_f1, owner), re = __shfl(fk == 0 ? fat_e0 : fat_e1, owner);
-            for (uint32_t base = rf; base < re; base += 64u) {  // uniform
-              const uint32_t ow_lo = (uint32_t)__shfl((int)(uint32_t)top.worst, owner);
-              const uint32_t ow_hi = (uint32_t)__shfl((int)(uint32_t)(top.worst >> 32), owner);
-              const uint64_t ow = ((uint64_t)ow_hi << 32) | ow_lo;
-              uint64_t key = ~0ull;
-              const uint32_t r = base + (uint32_t)lane;
-              if (r < re) {
-                const float4 p = g.pts[r];
-                const float d = ref_dist_sq(p.x, p.y, p.z, ox, oy, oz);
-                if (d < mr2) {
-                  const uint64_t kk = TopK::key_of(d, __float_as_uint(p.w));
-                  key = kk < ow ? kk : ~0ull;
-                }
-              }
-              unsigned long long cand = __ballot(key != ~0ull);
-              while (cand != 0ull) {  // uniform; the owner inserts (and drops what its k-th key no longer admits)
-                const int l = __builtin_ctzll(cand);
-                cand &= cand - 1ull;
-                const uint32_t lo = (uint32_t)__shfl((int)(uint32_t)key, l);
-                const uint32_t hi = (uint32_t)__shfl((int)(uint32_t)(key >> 32), l);
-                if (lane == owner) top.insert_key(((uint64_t)hi << 32) | lo);
-              }
-            }
-          }
-        }
-      }
+      rows.share(qx, qy, qz, fat);
       if (active) {
         const GridBox cov = grid_cover(g, qx, qy, qz, top.lim);
         box = nb;
@@ -309,10 +202,10 @@ __global__ __launch_bounds__(kKnnKBlock) void knearest_kernel(GridView g, TreeVi
     if (!live) return;
     if (walk) {  // the box would leave kGridWide: the implicit tree, from nothing
       top.clear();
-      knn_walk(tv, s_stack + threadIdx.x, kKnnKBlock, qx, qy, qz, top);
+      walk_tree();
     }
   } else if constexpr (kSrc == kRangeWalk) {
-    if (finite) knn_walk(tv, s_stack + threadIdx.x, kKnnKBlock, qx, qy, qz, top);
+    if (finite) walk_tree();
   } else {
     if (finite) {
       auto hit = [&](const float4 &nd, float d) {
@@ -357,39 +250,19 @@ __global__ __launch_bounds__(kKnnKBlock) void knearest_kernel(GridView g, TreeVi
 template <bool kSor>
 pcgx_status knearest_launch(const pcgx_kdtree *t, const float *d_q, int64_t nq, int32_t k, float max_range,
                             const KnnOut &O, hipStream_t st) {
-  Arena &ar = ctx().arena;
-  PCGX_TRY(ar.begin(st));
+  PCGX_TRY(ctx().arena.begin(st));
   const RangeSrc src = range_source(t);  // as pcgx_kdtree_range_count takes it
   XTreeView xv{};
   if (src == kRangeXWalk) PCGX_TRY(xtree_view(t, &xv, st));
   const TreeView tv = t->view();
-  KnnQuery Q{d_q, nullptr, nullptr, nq};
-  if (!d_q) {  // the tree's own points, Len() of them, deleted ones included
-    if (t->grid_ok) {
-      Q.own = t->grid.pts;  // cell order
-    } else if (src == kRangeXWalk) {
-      Q.q = t->d_xsrc;  // by id (xtree_view made it)
-    } else {
-      float *xyz = nullptr;
-      PCGX_TRY(ar.alloc_n((size_t)nq * 3, &xyz));
-      const unsigned slots = 1u << tv.depth;
-      hipLaunchKernelGGL(knn_own_points_kernel, dim3((slots + 255u) / 256u), dim3(256), 0, st, tv, xyz);
-      PCGX_HIP_TRY(hipGetLastError());
-      Q.q = xyz;
-    }
-  }
-  if (!Q.own && nq >= kKnnPresortMin) {
-    int32_t *perm = nullptr;
-    PCGX_TRY(ar.alloc_n((size_t)nq, &perm));
-    PCGX_TRY(morton_order(Q.q, nq, t->bbox_lo, t->bbox_hi, perm, st));
-    Q.perm = perm;
-  }
+  QuerySource Q;
+  PCGX_TRY(query_source(t, src, d_q, nq, &Q, st));
   const float mr2 = max_range * max_range;
   const dim3 grid(xcd_grid((unsigned)((nq + kKnnKBlock - 1) / kKnnKBlock))), block(kKnnKBlock);
-  const int64_t guard = 4 * t->n + 8;
+  const int64_t guard = xwalk_guard(t->n);
   const size_t list_bytes = (size_t)k * kKnnKBlock * sizeof(uint64_t);
   if (src == kRangeXWalk) {
-    const size_t lds = list_bytes + (size_t)(xv.depth > 0 ? xv.depth : 1) * kKnnKBlock * sizeof(uint32_t);
+    const size_t lds = list_bytes + xwalk_stack_bytes(xv, kKnnKBlock);
     hipLaunchKernelGGL((knearest_kernel<kRangeXWalk, kSor>), grid, block, lds, st, GridView{}, tv, xv, Q, k, mr2, O, guard);
   } else if (src == kRangeGrid) {
     hipLaunchKernelGGL((knearest_kernel<kRangeGrid, kSor>), grid, block, list_bytes + walk_stack_bytes(tv, kKnnKBlock), st,
@@ -418,7 +291,7 @@ pcgx_status knearest_check(const char *fn, const pcgx_kdtree *t, const float *q,
   if (!t || nq < 0) return fail(PCGX_E_INVALID, "%s: bad argument", fn);
   if (k < 1 || k > kKnnMaxK) return fail(PCGX_E_INVALID, "%s: k = %d outside [1, %d]", fn, (int)k, kKnnMaxK);
   if (!(max_range >= 0.0f)) return fail(PCGX_E_INVALID, "%s: max_range must be >= 0 or +inf", fn);
-  if (!q && nq != t->n) return fail(PCGX_E_INVALID, "%s: q == NULL takes the tree's own points: nq must equal Len()", fn);
+  PCGX_TRY(own_query_check(fn, t, q, nq));
   if (nq > 0 && (!ids || !dist_sq)) return fail(PCGX_E_INVALID, "%s: NULL ids / dist_sq", fn);
   return PCGX_OK;
 }

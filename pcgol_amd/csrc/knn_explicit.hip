@@ -483,9 +483,9 @@ pcgx_status xtree_launch_nearest(const pcgx_kdtree *t, const float *d_q, const i
   if (nq == 0) return PCGX_OK;
   XTreeView xv;
   PCGX_TRY(xtree_view(t, &xv, st));
-  const size_t lds = (size_t)(xv.depth > 0 ? xv.depth : 1) * kXBlock * sizeof(uint32_t);
+  const size_t lds = xwalk_stack_bytes(xv, kXBlock);
   const unsigned blocks = (unsigned)((nq + kXBlock - 1) / kXBlock);
-  const int64_t guard = 4 * t->n + 8;  // a walk takes at most two steps per node
+  const int64_t guard = xwalk_guard(t->n);
   ProfScope prof(PCGX_PROF_KNN_WALK, st);
   if (min_dist_sq > 0.0f)
     hipLaunchKernelGGL(xnearest_kernel<true>, dim3(blocks), dim3(kXBlock), lds, st, xv, d_q, d_perm, nq, max_range_sq,
@@ -517,7 +517,7 @@ inline void host_xwalk(const pcgx_kdtree *t, const float qv[3], Bound &&bound, L
   bool desc = true;
   const float *P = t->points.data();
   const pcgx_kdtree::XNode *X = t->xnodes.data();
-  for (int64_t guard = 4 * t->n + 8; guard > 0; --guard) {
+  for (int64_t guard = xwalk_guard(t->n); guard > 0; --guard) {
     if (desc) {  // searchLeafNode step (kdtree.go:202-221)
       const pcgx_kdtree::XNode &nd = X[cur];
       const float *p = P + 3 * (size_t)nd.id;

@@ -36,6 +36,10 @@ struct GridBox {
   int x0, x1, y0, y1, z0, z1;  // inclusive cell ranges
 };
 
+__device__ __forceinline__ bool box_inside(const GridBox &a, const GridBox &b) {  // a within b
+  return a.x0 >= b.x0 && a.x1 <= b.x1 && a.y0 >= b.y0 && a.y1 <= b.y1 && a.z0 >= b.z0 && a.z1 <= b.z1;
+}
+
 // Cells that hold every point whose computed DistSq to q is <= lim.  Such a point has
 // |p.x - q.x| <= sqrt(lim) (1 + 2e-7) (DistSq >= fl(dx^2), dx = fl(p.x - q.x)); rad below is larger,
 // fl(q.x + rad) >= p.x and fl(q.x - rad) <= p.x by monotonic rounding, and grid_cell is monotonic.

@@ -16,6 +16,13 @@ struct XTreeView {
 
 constexpr int kXBlock = 256;
 
+// LDS of a block's xwalk frames: [depth][block] words
+inline size_t xwalk_stack_bytes(const XTreeView &xv, const int block) {
+  return (size_t)(xv.depth > 0 ? xv.depth : 1) * block * sizeof(uint32_t);
+}
+// xwalk's `guard` on a tree of n points: a walk takes at most two steps per node
+inline int64_t xwalk_guard(const int64_t n) { return 4 * n + 8; }
+
 // frame word: node index (27 bits) | side taken << 27
 // on_leaf / on_pivot(node {x, y, z, bits(id)}, DistSq): called for every leaf / pivot the reference
 // evaluates, in its order; return false to stop (MinDistSq cut).  bound(): current pruning bound (best.d for Nearest, maxRange^2 for Range).

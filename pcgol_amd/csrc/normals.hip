@@ -15,8 +15,7 @@
 //   grid  (kRangeGrid): grid_radius_scan over the cells grid_cover names, fat rows scanned by the whole wave;
 //   walk  (kRangeWalk: no grid, PCGX_RANGE_WALK=1): range_walk_nodes over the implicit tree;
 //   xwalk (kRangeXWalk: a handle that has seen DeletePoint): the patched tree's walk of knn_xwalk.h.
-// Queries: the caller's (Morton-ordered from kNormPresortMin on), or the tree's own points (q == NULL) in the grid's
-// cell order, where neighbouring lanes read the same cells; results are written at the query's index / point id.
+// Queries: the caller's, or the tree's own points (q == NULL), as query_source (range_enum.h) lays them out.
 #include <math.h>
 #include <stdlib.h>
 
@@ -27,16 +26,7 @@
 namespace pcgx {
 
 constexpr int kNormBlock = kRangeWalkBlock;     // one wave per workgroup: the walks' LDS frame stacks are [level][64]
-constexpr int64_t kNormPresortMin = 16384;      // caller batches from this size on run in Morton order (as Range's)
 constexpr int kJacobiSweeps = 8;                // upper bound; a sweep that finds nothing to rotate ends the solve
-
-// where the queries come from: own[pos] ({x, y, z, bits(id)}: the tree's own points in cell order), else q[perm[pos]]
-struct NormQuery {
-  const float *q;
-  const int32_t *perm;
-  const float4 *own;
-  int64_t nq;
-};
 
 struct NormOut {
   float *normals;    // [3 nq]
@@ -198,22 +188,8 @@ __device__ __forceinline__ void normals_finish(const NormAcc &a, const float qx,
   if (O.counts) O.counts[i] = a.n;
 }
 
-// The tree's own points by id, out of the BFS slots (a handle without a grid, q == NULL)
-__global__ __launch_bounds__(256) void normals_own_points_kernel(TreeView tv, float *__restrict__ xyz) {
-  const uint32_t b = blockIdx.x * 256u + threadIdx.x;
-  if (b < 1u || b >= (1u << tv.depth)) return;
-  const uint32_t size = node_size(b, 31 - __clz((int)b), (uint32_t)tv.n + 1u);
-  if (size < 1u || size > (uint32_t)tv.n) return;  // no such node
-  const float4 nd = node_at(tv.nodes, b);
-  const uint32_t id = __float_as_uint(nd.w);
-  if (id >= (uint32_t)tv.n) return;
-  xyz[3 * (size_t)id] = nd.x;
-  xyz[3 * (size_t)id + 1] = nd.y;
-  xyz[3 * (size_t)id + 2] = nd.z;
-}
-
 template <int kSrc>
-__global__ __launch_bounds__(kNormBlock) void normals_kernel(GridView g, TreeView tv, XTreeView xv, NormQuery Q,
+__global__ __launch_bounds__(kNormBlock) void normals_kernel(GridView g, TreeView tv, XTreeView xv, QuerySource Q,
                                                              float bound, NormOut O, int64_t guard) {
   extern __shared__ uint32_t s_stack[];
   const uint32_t n_tiles = (uint32_t)((Q.nq + kNormBlock - 1) / kNormBlock);
@@ -223,16 +199,7 @@ __global__ __launch_bounds__(kNormBlock) void normals_kernel(GridView g, TreeVie
   if (kSrc != kRangeGrid && !live) return;
   int64_t i = 0;
   float qx = 0.0f, qy = 0.0f, qz = 0.0f;
-  if (live) {
-    if (Q.own) {
-      const float4 r = Q.own[pos];
-      i = (int64_t)__float_as_uint(r.w);
-      qx = r.x; qy = r.y; qz = r.z;
-    } else {
-      i = Q.perm ? (int64_t)Q.perm[pos] : pos;
-      qx = Q.q[3 * i]; qy = Q.q[3 * i + 1]; qz = Q.q[3 * i + 2];
-    }
-  }
+  if (live) read_query(Q, pos, i, qx, qy, qz);
   NormAcc acc;
   acc.clear();
   auto take = [&](const float4 &p) {
@@ -254,9 +221,10 @@ __global__ __launch_bounds__(kNormBlock) void normals_kernel(GridView g, TreeVie
     });
     if (!live) return;
   } else if constexpr (kSrc == kRangeWalk) {
-    range_walk_nodes(tv, s_stack + threadIdx.x, kNormBlock, qx, qy, qz, bound, [&](const float4 &nd, float) {
-      acc.add(nd.x, nd.y, nd.z, qx, qy, qz);  // (range_walk_nodes reports only DistSq < bound)
-    });
+    range_walk_nodes<false>(tv, s_stack + threadIdx.x, kNormBlock, qx, qy, qz, bound, [=]() { return bound; },
+                            [&](const float4 &nd, float) {
+                              acc.add(nd.x, nd.y, nd.z, qx, qy, qz);  // (range_walk_nodes reports only DistSq < bound)
+                            });
   } else {
     auto hit = [&](const float4 &nd, float) {
       take(nd);
@@ -277,7 +245,7 @@ pcgx_status normals_check(const char *fn, const pcgx_kdtree *t, const float *q, 
                           const float *normals) {
   if (!t || nq < 0) return fail(PCGX_E_INVALID, "%s: bad argument", fn);
   if (!(radius > 0.0f) || !(radius < __builtin_inff())) return fail(PCGX_E_INVALID, "%s: radius must be finite and > 0", fn);
-  if (!q && nq != t->n) return fail(PCGX_E_INVALID, "%s: q == NULL takes the tree's own points: nq must equal Len()", fn);
+  PCGX_TRY(own_query_check(fn, t, q, nq));
   if (nq > 0 && !normals) return fail(PCGX_E_INVALID, "%s: NULL normals", fn);
   return PCGX_OK;
 }
@@ -286,35 +254,13 @@ pcgx_status normals_check(const char *fn, const pcgx_kdtree *t, const float *q, 
 pcgx_status normals_enqueue(const pcgx_kdtree *t, const float *d_q, int64_t nq, float radius, const float viewpoint[3],
                             int32_t min_neighbors, float *d_normals, float *d_curvature, int32_t *d_counts,
                             hipStream_t st) {
-  Arena &ar = ctx().arena;
-  PCGX_TRY(ar.begin(st));
+  PCGX_TRY(ctx().arena.begin(st));
   const RangeSrc src = range_source(t);  // as pcgx_kdtree_range_count takes it
   XTreeView xv{};
   if (src == kRangeXWalk) PCGX_TRY(xtree_view(t, &xv, st));
   const TreeView tv = t->view();
-  NormQuery Q{d_q, nullptr, nullptr, nq};
-  if (!d_q) {  // the tree's own points, Len() of them, deleted ones included
-    if (t->grid_ok) {
-      Q.own = t->grid.pts;  // cell order
-    } else {
-      float *xyz = nullptr;
-      if (src == kRangeXWalk) {
-        xyz = t->d_xsrc;  // by id (xtree_view made it)
-      } else {
-        PCGX_TRY(ar.alloc_n((size_t)nq * 3, &xyz));
-        const unsigned slots = 1u << tv.depth;
-        hipLaunchKernelGGL(normals_own_points_kernel, dim3((slots + 255u) / 256u), dim3(256), 0, st, tv, xyz);
-        PCGX_HIP_TRY(hipGetLastError());
-      }
-      Q.q = xyz;
-    }
-  }
-  if (!Q.own && nq >= kNormPresortMin) {
-    int32_t *perm = nullptr;
-    PCGX_TRY(ar.alloc_n((size_t)nq, &perm));
-    PCGX_TRY(morton_order(Q.q, nq, t->bbox_lo, t->bbox_hi, perm, st));
-    Q.perm = perm;
-  }
+  QuerySource Q;
+  PCGX_TRY(query_source(t, src, d_q, nq, &Q, st));
   NormOut O{d_normals, d_curvature, d_counts, 0.0f, 0.0f, 0.0f, min_neighbors < 3 ? 3 : min_neighbors};
   if (viewpoint) {
     O.vx = viewpoint[0];
@@ -323,10 +269,10 @@ pcgx_status normals_enqueue(const pcgx_kdtree *t, const float *d_q, int64_t nq, 
   }
   const float bound = radius * radius;
   const dim3 grid(xcd_grid((unsigned)((nq + kNormBlock - 1) / kNormBlock))), block(kNormBlock);
-  const int64_t guard = 4 * t->n + 8;
+  const int64_t guard = xwalk_guard(t->n);
   if (src == kRangeXWalk) {
-    const size_t lds = (size_t)(xv.depth > 0 ? xv.depth : 1) * kNormBlock * sizeof(uint32_t);
-    hipLaunchKernelGGL(normals_kernel<kRangeXWalk>, grid, block, lds, st, GridView{}, tv, xv, Q, bound, O, guard);
+    hipLaunchKernelGGL(normals_kernel<kRangeXWalk>, grid, block, xwalk_stack_bytes(xv, kNormBlock), st, GridView{}, tv, xv,
+                       Q, bound, O, guard);
   } else if (src == kRangeGrid) {
     hipLaunchKernelGGL(normals_kernel<kRangeGrid>, grid, block, 0, st, t->grid, tv, xv, Q, bound, O, guard);
   } else {

@@ -23,7 +23,8 @@
 // Two entry points because the result length is data dependent: pcgx_kdtree_range_count
 // (walk, count) and pcgx_kdtree_range_fill (walk again, write at the caller's offsets, then
 // one stable sort of the whole batch by (query, DistSq) with the radix sort of sort.hip).
-// One query per lane; 4-byte frames [level][thread] in LDS as in knn_walk.h.
+// One query per lane; 4-byte frames [level][thread] in LDS as in knn_walk.h.  Also here: query_source (range_enum.h),
+// where Range, normals and k nearest neighbours take their queries from.
 #include <stdlib.h>
 #include <string.h>
 
@@ -36,7 +37,6 @@
 namespace pcgx {
 
 constexpr int kRangeBlock = kRangeWalkBlock;
-constexpr int64_t kRangePresortMin = 16384;  // batches from this size on are walked in Morton order
 
 // kFill == false: counts[i] = number of neighbours.  kFill == true: neighbours of query i are
 // written from offsets[i] in discovery order: {point id, DistSq bits, query index}.
@@ -75,7 +75,7 @@ __global__ __launch_bounds__(kSrc == kRangeXWalk ? kXBlock : kRangeBlock) void r
     ++found;
   };
   if constexpr (kSrc == kRangeWalk) {
-    range_walk_nodes(tv, s_stack + threadIdx.x, kBlock, qx, qy, qz, bound, hit);
+    range_walk_nodes<false>(tv, s_stack + threadIdx.x, kBlock, qx, qy, qz, bound, [=]() { return bound; }, hit);
   } else {
     auto visit = [&](const float4 &nd, float d) {
       if (d < bound) hit(nd, d);  // kdtree.go:166-169,178-181
@@ -282,6 +282,50 @@ __global__ __launch_bounds__(256) void range_widen_check_kernel(const uint32_t *
 }  // namespace pcgx
 
 namespace pcgx {
+// The tree's own points by id, out of the BFS slots (query_source on a handle without a grid)
+__global__ __launch_bounds__(256) void own_points_kernel(TreeView tv, float *__restrict__ xyz) {
+  const uint32_t b = blockIdx.x * 256u + threadIdx.x;
+  if (b < 1u || b >= (1u << tv.depth)) return;
+  const uint32_t size = node_size(b, 31 - __clz((int)b), (uint32_t)tv.n + 1u);
+  if (size < 1u || size > (uint32_t)tv.n) return;  // no such node
+  const float4 nd = node_at(tv.nodes, b);
+  const uint32_t id = __float_as_uint(nd.w);
+  if (id >= (uint32_t)tv.n) return;
+  xyz[3 * (size_t)id] = nd.x;
+  xyz[3 * (size_t)id + 1] = nd.y;
+  xyz[3 * (size_t)id + 2] = nd.z;
+}
+
+pcgx_status query_source(const pcgx_kdtree *t, RangeSrc src, const float *d_q, int64_t nq, QuerySource *Q,
+                         hipStream_t st) {
+  Arena &ar = ctx().arena;
+  *Q = QuerySource{d_q, nullptr, nullptr, nq};
+  if (!d_q) {
+    if (t->grid_ok) {
+      Q->own = t->grid.pts;
+      return PCGX_OK;
+    }
+    if (src == kRangeXWalk) {
+      Q->q = t->d_xsrc;
+    } else {
+      const TreeView tv = t->view();
+      float *xyz = nullptr;
+      PCGX_TRY(ar.alloc_n((size_t)nq * 3, &xyz));
+      const unsigned slots = 1u << tv.depth;
+      hipLaunchKernelGGL(own_points_kernel, dim3((slots + 255u) / 256u), dim3(256), 0, st, tv, xyz);
+      PCGX_HIP_TRY(hipGetLastError());
+      Q->q = xyz;
+    }
+  }
+  if (nq >= kPresortMin) {
+    int32_t *perm = nullptr;
+    PCGX_TRY(ar.alloc_n((size_t)nq, &perm));
+    PCGX_TRY(morton_order(Q->q, nq, t->bbox_lo, t->bbox_hi, perm, st));
+    Q->perm = perm;
+  }
+  return PCGX_OK;
+}
+
 static pcgx_status range_inverse_map(const pcgx_kdtree *tc, const uint32_t **out, hipStream_t st) {
   pcgx_kdtree *t = const_cast<pcgx_kdtree *>(tc);  // made once per handle, on first use
   std::lock_guard<std::mutex> lock(t->mu);
@@ -340,11 +384,9 @@ static pcgx_status range_launch(const pcgx_kdtree *t, RangeSrc src, const float 
     } else {
       XTreeView xv;
       PCGX_TRY(xtree_view(t, &xv, st));
-      const size_t lds = (size_t)(xv.depth > 0 ? xv.depth : 1) * kXBlock * sizeof(uint32_t);
-      const int64_t guard = 4 * t->n + 8;  // a walk takes at most two steps per node
       hipLaunchKernelGGL((range_kernel<kRangeXWalk, kFill>), dim3((unsigned)((nq + kXBlock - 1) / kXBlock)), dim3(kXBlock),
-                         lds, st, TreeView{}, xv, d_q, perm, nq, bound, counts, offsets, total, out_id, out_key, out_query,
-                         guard);
+                         xwalk_stack_bytes(xv, kXBlock), st, TreeView{}, xv, d_q, perm, nq, bound, counts, offsets, total,
+                         out_id, out_key, out_query, xwalk_guard(t->n));
     }
   }
   PCGX_HIP_TRY(hipGetLastError());
@@ -370,13 +412,10 @@ extern "C" pcgx_status pcgx_kdtree_range_count(const pcgx_kdtree *t, const float
   PCGX_TRY(ctx().host_arena.alloc_n((size_t)nq * 3, &d_q));
   PCGX_TRY(ctx().host_arena.alloc_n((size_t)nq, &d_c));
   PCGX_TRY(staged_upload(d_q, q, (size_t)nq * 12, st));
-  int32_t *perm = nullptr;
-  if (nq >= kRangePresortMin) {
-    PCGX_TRY(ctx().arena.begin(st));
-    PCGX_TRY(ctx().arena.alloc_n((size_t)nq, &perm));
-    PCGX_TRY(morton_order(d_q, nq, t->bbox_lo, t->bbox_hi, perm, st));
-  }
-  PCGX_TRY(range_launch<false>(t, src, d_q, perm, nq, max_range * max_range, d_c, nullptr, 0, nullptr, nullptr, nullptr,
+  QuerySource Q;
+  PCGX_TRY(ctx().arena.begin(st));
+  PCGX_TRY(query_source(t, src, d_q, nq, &Q, st));
+  PCGX_TRY(range_launch<false>(t, src, d_q, Q.perm, nq, max_range * max_range, d_c, nullptr, 0, nullptr, nullptr, nullptr,
                                nullptr, st));
   PCGX_TRY(staged_download(counts, d_c, (size_t)nq * 8, st));
   return PCGX_OK;
@@ -426,12 +465,9 @@ extern "C" pcgx_status pcgx_kdtree_range_fill(const pcgx_kdtree *t, const float 
   PCGX_TRY(staged_upload(d_q, q, (size_t)nq * 12, st));
   PCGX_TRY(staged_upload(d_off, offsets, (size_t)(nq + 1) * 8, st));
   PCGX_HIP_TRY(hipMemsetAsync(d_bad, 0, 4, st));
-  int32_t *qperm = nullptr;
-  if (nq >= kRangePresortMin) {
-    PCGX_TRY(ar.alloc_n((size_t)nq, &qperm));
-    PCGX_TRY(morton_order(d_q, nq, t->bbox_lo, t->bbox_hi, qperm, st));
-  }
-  PCGX_TRY(range_launch<true>(t, src, d_q, qperm, nq, max_range * max_range, nullptr, d_off, total, d_id, d_key, d_query,
+  QuerySource Q;
+  PCGX_TRY(query_source(t, src, d_q, nq, &Q, st));
+  PCGX_TRY(range_launch<true>(t, src, d_q, Q.perm, nq, max_range * max_range, nullptr, d_off, total, d_id, d_key, d_query,
                               d_bad, st));
   const unsigned tb = (unsigned)((total + 255) / 256);
   hipLaunchKernelGGL(range_iota_kernel, dim3(tb), dim3(256), 0, st, vals[0], total);
