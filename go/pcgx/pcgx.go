@@ -326,6 +326,52 @@ func (k *KDTree) NormalsAt(q []mat.Vec3, radius float32, viewpoint mat.Vec3, min
 	return normals, curvature, counts, nil
 }
 
+// Covariance modes of KDTree.Covariances (include/pcgx.h, pcgx_kdtree_covariances).
+const (
+	CovRaw   = int(C.PCGX_COV_RAW)   // the covariance as it is
+	CovPlane = int(C.PCGX_COV_PLANE) // I - (1 - epsilon) u u^T: Generalized ICP's regularised plane
+)
+
+// Covariances returns the covariance of every query's kk nearest neighbours (KNearestBatch's lists; extension: no
+// reference parity; include/pcgx.h, pcgx_kdtree_covariances) as xx, xy, xz, yy, yz, zz, the unit normal u of the
+// neighbourhood turned towards viewpoint, and the neighbour count.  mode CovPlane gives I - (1 - epsilon) u u^T,
+// CovRaw the covariance as it is; fewer than 3 neighbours, or all at one place, give I / 0 and a zero normal.
+// q == nil takes the tree's own points, in id order.
+func (k *KDTree) Covariances(q []mat.Vec3, kk int, maxRange float32, mode int, epsilon float32, viewpoint mat.Vec3) ([][6]float32, []mat.Vec3, []int32, error) {
+	runtime.LockOSThread() // the error text is thread-local on the C side: call and pcgx_last_error on one OS thread
+	defer runtime.UnlockOSThread()
+	defer runtime.KeepAlive(k) // the finalizer must not free the handle while a call is in flight
+	var qp *C.float
+	n := len(q)
+	if q == nil {
+		var ln C.int64_t
+		if err := status(C.pcgx_kdtree_len(k.t.h, &ln)); err != nil {
+			return nil, nil, nil, err
+		}
+		n = int(ln)
+	} else if n > 0 {
+		qp = (*C.float)(unsafe.Pointer(&q[0]))
+	}
+	cov := make([][6]float32, n)
+	normals := make([]mat.Vec3, n)
+	counts := make([]int32, n)
+	if n == 0 {
+		return cov, normals, counts, nil
+	}
+	vp := viewpoint
+	rc := C.pcgx_kdtree_covariances(k.t.h, qp, C.int64_t(n), C.int32_t(kk), C.float(maxRange), C.int32_t(mode),
+		C.float(epsilon), (*C.float)(unsafe.Pointer(&vp[0])), (*C.float)(unsafe.Pointer(&cov[0][0])),
+		(*C.float)(unsafe.Pointer(&normals[0])), (*C.int32_t)(unsafe.Pointer(&counts[0])))
+	runtime.KeepAlive(q)
+	runtime.KeepAlive(cov)
+	runtime.KeepAlive(normals)
+	runtime.KeepAlive(counts)
+	if err := status(rc); err != nil {
+		return nil, nil, nil, err
+	}
+	return cov, normals, counts, nil
+}
+
 // KNearest returns the kk points of the tree with the smallest (DistSq, ID) among those with DistSq < maxRange^2,
 // ascending (extension: no reference parity; include/pcgx.h, pcgx_kdtree_knearest: ties go by ID).  Like Nearest it
 // is one blocking GPU call and panics where the call fails (kk outside [1, 64], a NaN maxRange).

@@ -786,6 +786,37 @@ PCGX_API pcgx_status pcgx_kdtree_knearest_dev(const pcgx_kdtree *t, const float 
                                               float max_range, int32_t *d_ids, float *d_dist_sq,
                                               int32_t *d_counts, void *stream);
 
+/* ------------------------------------------- k-NN covariances (extension: no reference parity)
+ * NOT in the reference.  The per-point covariances Generalized ICP (Segal, Haehnel, Thrun 2009) takes, from k nearest
+ * neighbourhoods, which adapt to the point density by themselves.  For each query i:
+ *   N(q)  = exactly the list pcgx_kdtree_knearest(t, q, k, max_range) returns: the same sources (grid, forced walk,
+ *           patched tree after DeletePoint), the same (DistSq, id) order, the same count; a tree point is its own
+ *           neighbour.  n = |N(q)|.
+ *   C     = sum d d^T / n - m m^T with d = p - q and m = sum d / n, in float64, summed in N(q)'s order
+ *           (pcgx_kdtree_normals' moments and formula).
+ *   PCGX_COV_RAW:   C as it is.
+ *   PCGX_COV_PLANE: I - (1 - epsilon) u u^T = V diag(epsilon, 1, 1) V^T, u the unit eigenvector of C's smallest
+ *                   eigenvalue (pcgx_kdtree_normals' Jacobi solve): Segal's regularisation, fast_gicp's PLANE.
+ *   Degenerate: n < 3, or all of N(q) at one place (the normals' exact box test): I for PLANE, 0 for RAW.
+ *   cov6[6i .. 6i+5] = xx, xy, xz, yy, yz, zz in float32.
+ *   normals (may be NULL): u turned towards the viewpoint (NULL: the origin) as pcgx_kdtree_normals turns it; 0 where
+ *   degenerate.  counts (may be NULL): n.
+ * q == NULL: the queries are the tree's own points (nq must equal Len()), the output in id order -- one covariance per
+ * base id, deleted ids included.  PCGX_E_INVALID: k outside [1, 64], epsilon outside (0, 1], an unknown mode, a NaN or
+ * negative max_range, q == NULL with nq != Len(), cov6 == NULL with nq > 0.  Always computed on the device; the cost is
+ * pcgx_kdtree_knearest's plus k reads by id per query and the 3 x 3 solve, which PCGX_COV_RAW skips when normals is
+ * NULL.  On a handle without deletions the first call builds an id -> node map once and waits for it. */
+enum { PCGX_COV_RAW = 0, PCGX_COV_PLANE = 1 };
+PCGX_API pcgx_status pcgx_kdtree_covariances(const pcgx_kdtree *t, const float *q, int64_t nq, int32_t k,
+                                             float max_range, int32_t mode, float epsilon, const float viewpoint[3],
+                                             float *cov6 /* [6nq] */, float *normals /* [3nq], may be NULL */,
+                                             int32_t *counts /* [nq], may be NULL */);
+/* Same, every array device resident, enqueued on `stream` (NULL: the library's); returns without waiting. */
+PCGX_API pcgx_status pcgx_kdtree_covariances_dev(const pcgx_kdtree *t, const float *d_q, int64_t nq, int32_t k,
+                                                 float max_range, int32_t mode, float epsilon,
+                                                 const float viewpoint[3], float *d_cov6, float *d_normals,
+                                                 int32_t *d_counts, void *stream);
+
 /* ------------------------------------------- statistical outlier removal (extension: no reference parity)
  * PCL's StatisticalOutlierRemoval / Open3D's remove_statistical_outlier over an AoS cloud (stride / xyz_off as
  * pcgx_voxel_filter).

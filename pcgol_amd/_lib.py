@@ -29,6 +29,7 @@ PCGX_SUMS_REFERENCE, PCGX_SUMS_F64_TREE, PCGX_SUMS_REFERENCE_CHAIN = range(3)  #
 PCGX_PCD_MAX_FIELDS = 64
 
 PCGX_KNN_PRESORT = 1
+PCGX_COV_RAW, PCGX_COV_PLANE = 0, 1  # pcgx_kdtree_covariances' mode
 PROF_ICP_WALK, PROF_KNN_WALK, PROF_VOXEL_ALL, PROF_SORT_SCATTER, PROF_ICP_GRID, PROF_KNN_GRID = range(6)
 PROF_STRICT_TERMS, PROF_STRICT_SUM, PROF_STRICT_CHAIN, PROF_STRICT_JOB, PROF_ICP_LEFTOVER = 6, 7, 8, 9, 10
 
@@ -252,6 +253,8 @@ SIGNATURES = {
     "pcgx_kdtree_normals_dev": (_i32, [_vp, _vp, _i64, _f32, _vp, _i32, _vp, _vp, _vp, _vp]),
     "pcgx_kdtree_knearest": (_i32, [_vp, _vp, _i64, _i32, _f32, _vp, _vp, _vp]),
     "pcgx_kdtree_knearest_dev": (_i32, [_vp, _vp, _i64, _i32, _f32, _vp, _vp, _vp, _vp]),
+    "pcgx_kdtree_covariances": (_i32, [_vp, _vp, _i64, _i32, _f32, _i32, _f32, _vp, _vp, _vp, _vp]),
+    "pcgx_kdtree_covariances_dev": (_i32, [_vp, _vp, _i64, _i32, _f32, _i32, _f32, _vp, _vp, _vp, _vp, _vp]),
     "pcgx_sor_filter": (_i32, [_vp, _i64, _i32, _i32, _i32, _f32, _i32, _vp, C.POINTER(_i64), _vp, _vp]),
     "pcgx_sor_filter_dev": (_i32, [_vp, _i64, _i32, _i32, _i32, _f32, _i32, _vp, C.POINTER(_i64), _vp, _vp, _vp]),
 }

@@ -21,10 +21,16 @@
 //   xwalk (kRangeXWalk: a handle that has seen DeletePoint): the patched tree's walk (knn_xwalk.h), same pruning.
 // Non-finite queries find nothing (no DistSq of theirs compares below B).  Queries: the caller's, or the tree's own
 // points (q == NULL), as query_source (range_enum.h) lays them out.  SOR mode writes no ids: only the mean of
-// sqrt(DistSq) over the first mean_k entries other than the query's own id, in float64 (sor.hip).
+// sqrt(DistSq) over the first mean_k entries other than the query's own id, in float64 (sor.hip).  Covariance mode
+// (kCov, pcgx_kdtree_covariances) writes no ids either: after the search the lane fetches each listed point's xyz by id
+// (the id -> node map range_inverse_map makes, or the patched tree's copy by id), sums NormAcc (cov3.h) in the list's
+// (DistSq, id) order -- so the result is a function of the query and the cloud alone -- and solves as normals.hip does.
 #include <math.h>
 #include <stdlib.h>
 
+#include <type_traits>
+
+#include "cov3.h"
 #include "knn_grid.h"
 #include "knn_xwalk.h"
 #include "range_walk.h"
@@ -41,6 +47,56 @@ struct KnnOut {
   double *mean;      // SOR: [nq] by id, compact
   int32_t mean_k;    // SOR: k - 1
 };
+
+// Covariance mode: the outputs, and where a listed neighbour's xyz is fetched by id
+struct CovOut {
+  float *cov6;          // [6 nq]: xx, xy, xz, yy, yz, zz
+  float *normals;       // [3 nq] or nullptr
+  int32_t *counts;      // [nq] or nullptr
+  const uint32_t *inv;  // grid, walk: id -> BFS slot of its node in the implicit tree (range_inverse_map)
+  const float *xyz;     // patched tree: the cloud's points by id (t->d_xsrc)
+  float vx, vy, vz;     // viewpoint of the normals
+  float eps;            // PLANE: I - (1 - eps) u u^T
+  int32_t plane;        // PCGX_COV_PLANE, else PCGX_COV_RAW
+};
+
+// moments of the list -> covariance and normal of query i (include/pcgx.h, pcgx_kdtree_covariances)
+__device__ __forceinline__ void covariance_finish(const NormAcc &a, const float qx, const float qy, const float qz,
+                                                  const CovOut &O, const int64_t i) {
+  // degenerate (fewer than 3, or all at one place): I for PLANE, 0 for RAW, normal 0
+  const double diag = O.plane ? 1.0 : 0.0;
+  double cxx = diag, cxy = 0.0, cxz = 0.0, cyy = diag, cyz = 0.0, czz = diag;
+  float nx = 0.0f, ny = 0.0f, nz = 0.0f;
+  if (a.n >= 3 && !(a.lox == a.hix && a.loy == a.hiy && a.loz == a.hiz)) {
+    double A[3][3], V[3][3];
+    norm_acc_cov(a, A);
+    if (!O.plane) {
+      cxx = A[0][0]; cxy = A[0][1]; cxz = A[0][2]; cyy = A[1][1]; cyz = A[1][2]; czz = A[2][2];
+    }
+    // (tr > 0 for a spread neighbourhood unless rounding cancels it: then PLANE and the normal as if degenerate)
+    const double tr = A[0][0] + A[1][1] + A[2][2];
+    if ((O.plane || O.normals) && tr > 0.0) {
+      double e0, e1, e2, ux, uy, uz;
+      norm_acc_solve(A, V, tr, e0, e1, e2, ux, uy, uz);
+      if (O.plane) {  // V diag(eps, 1, 1) V^T
+        const double f = 1.0 - (double)O.eps;
+        cxx = 1.0 - f * ux * ux; cxy = -f * ux * uy; cxz = -f * ux * uz;
+        cyy = 1.0 - f * uy * uy; cyz = -f * uy * uz; czz = 1.0 - f * uz * uz;
+      }
+      face_viewpoint(ux, uy, uz, O.vx, O.vy, O.vz, qx, qy, qz);
+      nx = (float)ux;
+      ny = (float)uy;
+      nz = (float)uz;
+    }
+  }
+  float *c = O.cov6 + 6 * i;
+  c[0] = (float)cxx; c[1] = (float)cxy; c[2] = (float)cxz; c[3] = (float)cyy; c[4] = (float)cyz; c[5] = (float)czz;
+  if (O.normals) {
+    O.normals[3 * i] = nx;
+    O.normals[3 * i + 1] = ny;
+    O.normals[3 * i + 2] = nz;
+  }
+}
 
 // One lane's best k, ascending, in LDS column `col` (slot s at col[s * 64]).
 struct TopK {
@@ -97,9 +153,11 @@ struct TopK {
   }
 };
 
-template <int kSrc, bool kSor>
+// (kCov: the covariance mode's outputs take KnnOut's place, so the other modes' arguments and code stay as they were)
+template <int kSrc, bool kSor, bool kCov = false>
 __global__ __launch_bounds__(kKnnKBlock) void knearest_kernel(GridView g, TreeView tv, XTreeView xv, QuerySource Q, int32_t k,
-                                                              float mr2, KnnOut O, int64_t guard) {
+                                                              float mr2, std::conditional_t<kCov, CovOut, KnnOut> O,
+                                                              int64_t guard) {
   extern __shared__ uint64_t s_knn[];  // [k][64] keys, then the walk's frames [levels][64]
   uint32_t *s_stack = reinterpret_cast<uint32_t *>(s_knn + (size_t)k * kKnnKBlock);
   const int lane = (int)(threadIdx.x & 63u);
@@ -215,7 +273,27 @@ __global__ __launch_bounds__(kKnnKBlock) void knearest_kernel(GridView g, TreeVi
       xwalk(xv, s_stack + threadIdx.x, kKnnKBlock, qx, qy, qz, guard, [&]() { return top.lim; }, hit, hit);
     }
   }
-  if constexpr (kSor) {
+  if constexpr (kCov) {
+    // the listed points by id, in the list's (DistSq, id) order
+    NormAcc acc;
+    acc.clear();
+    for (int s = 0; s < top.c; s++) {
+      const uint32_t id = (uint32_t)top.col[s * kKnnKBlock];
+      float px, py, pz;
+      if constexpr (kSrc == kRangeXWalk) {
+        px = O.xyz[3 * (size_t)id];
+        py = O.xyz[3 * (size_t)id + 1];
+        pz = O.xyz[3 * (size_t)id + 2];
+      } else {
+        const float4 nd = node_at(tv.nodes, O.inv[id]);
+        px = nd.x;
+        py = nd.y;
+        pz = nd.z;
+      }
+      acc.add(px, py, pz, qx, qy, qz);
+    }
+    covariance_finish(acc, qx, qy, qz, O, i);
+  } else if constexpr (kSor) {
     // the first mean_k entries other than the query's own id, float64 in ascending order
     double sum = 0.0;
     int taken = 0;
@@ -247,13 +325,17 @@ __global__ __launch_bounds__(kKnnKBlock) void knearest_kernel(GridView g, TreeVi
   if (O.counts) O.counts[i] = top.c;
 }
 
-template <bool kSor>
+template <bool kSor, bool kCov = false>
 pcgx_status knearest_launch(const pcgx_kdtree *t, const float *d_q, int64_t nq, int32_t k, float max_range,
-                            const KnnOut &O, hipStream_t st) {
+                            std::conditional_t<kCov, CovOut, KnnOut> O, hipStream_t st) {
   PCGX_TRY(ctx().arena.begin(st));
   const RangeSrc src = range_source(t);  // as pcgx_kdtree_range_count takes it
   XTreeView xv{};
   if (src == kRangeXWalk) PCGX_TRY(xtree_view(t, &xv, st));
+  if constexpr (kCov) {  // where the kernel finds a listed point's xyz (xtree_view made d_xsrc)
+    if (src == kRangeXWalk) O.xyz = t->d_xsrc;
+    else PCGX_TRY(range_inverse_map(t, &O.inv, st));
+  }
   const TreeView tv = t->view();
   QuerySource Q;
   PCGX_TRY(query_source(t, src, d_q, nq, &Q, st));
@@ -263,12 +345,12 @@ pcgx_status knearest_launch(const pcgx_kdtree *t, const float *d_q, int64_t nq, 
   const size_t list_bytes = (size_t)k * kKnnKBlock * sizeof(uint64_t);
   if (src == kRangeXWalk) {
     const size_t lds = list_bytes + xwalk_stack_bytes(xv, kKnnKBlock);
-    hipLaunchKernelGGL((knearest_kernel<kRangeXWalk, kSor>), grid, block, lds, st, GridView{}, tv, xv, Q, k, mr2, O, guard);
+    hipLaunchKernelGGL((knearest_kernel<kRangeXWalk, kSor, kCov>), grid, block, lds, st, GridView{}, tv, xv, Q, k, mr2, O, guard);
   } else if (src == kRangeGrid) {
-    hipLaunchKernelGGL((knearest_kernel<kRangeGrid, kSor>), grid, block, list_bytes + walk_stack_bytes(tv, kKnnKBlock), st,
+    hipLaunchKernelGGL((knearest_kernel<kRangeGrid, kSor, kCov>), grid, block, list_bytes + walk_stack_bytes(tv, kKnnKBlock), st,
                        t->grid, tv, xv, Q, k, mr2, O, guard);
   } else {
-    hipLaunchKernelGGL((knearest_kernel<kRangeWalk, kSor>), grid, block, list_bytes + walk_stack_bytes(tv, kKnnKBlock), st,
+    hipLaunchKernelGGL((knearest_kernel<kRangeWalk, kSor, kCov>), grid, block, list_bytes + walk_stack_bytes(tv, kKnnKBlock), st,
                        GridView{}, tv, xv, Q, k, mr2, O, guard);
   }
   PCGX_HIP_TRY(hipGetLastError());
@@ -293,6 +375,15 @@ pcgx_status knearest_check(const char *fn, const pcgx_kdtree *t, const float *q,
   if (!(max_range >= 0.0f)) return fail(PCGX_E_INVALID, "%s: max_range must be >= 0 or +inf", fn);
   PCGX_TRY(own_query_check(fn, t, q, nq));
   if (nq > 0 && (!ids || !dist_sq)) return fail(PCGX_E_INVALID, "%s: NULL ids / dist_sq", fn);
+  return PCGX_OK;
+}
+
+pcgx_status covariances_check(const char *fn, const pcgx_kdtree *t, const float *q, int64_t nq, int32_t k,
+                              float max_range, int32_t mode, float epsilon, const float *cov6) {
+  if (!cov6 && nq > 0) return fail(PCGX_E_INVALID, "%s: NULL cov6", fn);
+  PCGX_TRY(knearest_check(fn, t, q, nq, k, max_range, cov6, cov6));
+  if (mode != PCGX_COV_RAW && mode != PCGX_COV_PLANE) return fail(PCGX_E_INVALID, "%s: unknown mode %d", fn, (int)mode);
+  if (!(epsilon > 0.0f && epsilon <= 1.0f)) return fail(PCGX_E_INVALID, "%s: epsilon must lie in (0, 1]", fn);
   return PCGX_OK;
 }
 
@@ -335,5 +426,48 @@ extern "C" pcgx_status pcgx_kdtree_knearest(const pcgx_kdtree *t, const float *q
   for (size_t s = slots; s-- > 0;) ids[s] = (int64_t)narrow[s];
   PCGX_TRY(staged_download(dist_sq, d_d, slots * 4, st));
   if (counts) PCGX_TRY(staged_download(counts, d_c, (size_t)nq * 4, st));
+  return PCGX_OK;
+}
+
+extern "C" pcgx_status pcgx_kdtree_covariances_dev(const pcgx_kdtree *t, const float *d_q, int64_t nq, int32_t k,
+                                                   float max_range, int32_t mode, float epsilon,
+                                                   const float viewpoint[3], float *d_cov6, float *d_normals,
+                                                   int32_t *d_counts, void *stream) {
+  PCGX_API_LOCK();
+  PCGX_TRY(covariances_check("pcgx_kdtree_covariances_dev", t, d_q, nq, k, max_range, mode, epsilon, d_cov6));
+  if (nq == 0) return PCGX_OK;
+  PCGX_TRY(ensure_init());
+  CovOut O{d_cov6, d_normals, d_counts, nullptr, nullptr, 0.0f, 0.0f, 0.0f, epsilon, mode == PCGX_COV_PLANE ? 1 : 0};
+  if (viewpoint) {
+    O.vx = viewpoint[0];
+    O.vy = viewpoint[1];
+    O.vz = viewpoint[2];
+  }
+  return knearest_launch<false, true>(t, d_q, nq, k, max_range, O, pick_stream(stream));
+}
+
+extern "C" pcgx_status pcgx_kdtree_covariances(const pcgx_kdtree *t, const float *q, int64_t nq, int32_t k,
+                                               float max_range, int32_t mode, float epsilon, const float viewpoint[3],
+                                               float *cov6, float *normals, int32_t *counts) {
+  PCGX_API_CALL();
+  PCGX_TRY(covariances_check("pcgx_kdtree_covariances", t, q, nq, k, max_range, mode, epsilon, cov6));
+  if (nq == 0) return PCGX_OK;
+  PCGX_TRY(ensure_init());
+  hipStream_t st = ctx().stream;
+  Arena &ha = ctx().host_arena;
+  PCGX_TRY(ha.begin(st));
+  float *d_q = nullptr, *d_c = nullptr, *d_n = nullptr;
+  int32_t *d_k = nullptr;
+  if (q) {
+    PCGX_TRY(ha.alloc_n((size_t)nq * 3, &d_q));
+    PCGX_TRY(staged_upload(d_q, q, (size_t)nq * 12, st));
+  }
+  PCGX_TRY(ha.alloc_n((size_t)nq * 6, &d_c));
+  if (normals) PCGX_TRY(ha.alloc_n((size_t)nq * 3, &d_n));
+  if (counts) PCGX_TRY(ha.alloc_n((size_t)nq, &d_k));
+  PCGX_TRY(pcgx_kdtree_covariances_dev(t, d_q, nq, k, max_range, mode, epsilon, viewpoint, d_c, d_n, d_k, st));
+  PCGX_TRY(staged_download(cov6, d_c, (size_t)nq * 24, st));
+  if (normals) PCGX_TRY(staged_download(normals, d_n, (size_t)nq * 12, st));
+  if (counts) PCGX_TRY(staged_download(counts, d_k, (size_t)nq * 4, st));
   return PCGX_OK;
 }

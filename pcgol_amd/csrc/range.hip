@@ -326,7 +326,7 @@ pcgx_status query_source(const pcgx_kdtree *t, RangeSrc src, const float *d_q, i
   return PCGX_OK;
 }
 
-static pcgx_status range_inverse_map(const pcgx_kdtree *tc, const uint32_t **out, hipStream_t st) {
+pcgx_status range_inverse_map(const pcgx_kdtree *tc, const uint32_t **out, hipStream_t st) {
   pcgx_kdtree *t = const_cast<pcgx_kdtree *>(tc);  // made once per handle, on first use
   std::lock_guard<std::mutex> lock(t->mu);
   if (!t->d_inv) {
@@ -340,6 +340,8 @@ static pcgx_status range_inverse_map(const pcgx_kdtree *tc, const uint32_t **out
       hipLaunchKernelGGL(range_invert_nodes_kernel, dim3((slots + 255u) / 256u), dim3(256), 0, st, tv, p);
       e = hipGetLastError();
     }
+    // complete before it is published: a later caller on another stream reads it without ordering (once per handle)
+    if (e == hipSuccess) e = hipStreamSynchronize(st);
     if (e != hipSuccess) {
       dev_cache_free(p);
       return fail(PCGX_E_HIP, "range: building the id -> node map failed: %s", hipGetErrorString(e));

@@ -144,6 +144,11 @@ constexpr int64_t kPresortMin = 16384;
 pcgx_status query_source(const pcgx_kdtree *t, RangeSrc src, const float *d_q, int64_t nq, QuerySource *Q,
                          hipStream_t st);
 
+// *out = the map point id -> BFS slot of its node in the handle's implicit tree, made once per handle on first use (on
+// st, which it then waits for: callers on other streams use it unordered; range.hip).  k-NN covariances fetch their
+// neighbours' xyz by id through it.
+pcgx_status range_inverse_map(const pcgx_kdtree *t, const uint32_t **out, hipStream_t st);
+
 // q == NULL asks for the tree's own points: then nq must be Len().
 inline pcgx_status own_query_check(const char *fn, const pcgx_kdtree *t, const float *q, const int64_t nq) {
   if (!q && nq != t->n) return fail(PCGX_E_INVALID, "%s: q == NULL takes the tree's own points: nq must equal Len()", fn);

@@ -19,6 +19,7 @@
 #include <array>
 #include <functional>
 #include <initializer_list>
+#include <limits>
 #include <memory>
 #include <cstring>
 #include <random>
@@ -184,6 +185,29 @@ class KDTree {  // pc/storage/kdtree/kdtree.go:14-23
       for (int32_t s = 0; s < counts[(size_t)i]; s++)
         out[(size_t)i].push_back(Neighbor{ids[(size_t)(i * k + s)], d[(size_t)(i * k + s)]});
     return out;
+  }
+  // The covariance of every query's k nearest neighbours (KNearestBatch's lists; extension: no reference parity;
+  // include/pcgx.h, pcgx_kdtree_covariances).  mode PCGX_COV_PLANE (Generalized ICP's input): I - (1 - epsilon) u u^T
+  // with u the unit normal; PCGX_COV_RAW: the covariance as it is.  Fewer than 3 neighbours, or all at one place: I
+  // (PLANE) / 0 (RAW), normal {0, 0, 0}.  An empty `queries` takes the tree's own points: the result is in id order.
+  struct CovariancesResult {
+    std::vector<std::array<float, 6>> cov;  // xx, xy, xz, yy, yz, zz
+    std::vector<Vec3> normals;              // u turned towards the viewpoint
+    std::vector<int32_t> counts;
+  };
+  CovariancesResult Covariances(int32_t k, float maxRange = std::numeric_limits<float>::infinity(),
+                                int32_t mode = PCGX_COV_PLANE, float epsilon = 1e-3f,
+                                const std::vector<Vec3> &queries = {}, const Vec3 &viewpoint = Vec3{0.0f, 0.0f, 0.0f}) const {
+    const bool own = queries.empty();
+    const int64_t n = own ? Len() : (int64_t)queries.size();
+    CovariancesResult r;
+    r.cov.resize((size_t)n);
+    r.normals.resize((size_t)n);
+    r.counts.resize((size_t)n);
+    check(pcgx_kdtree_covariances(h_.get(), own ? nullptr : queries[0].data(), n, k, maxRange, mode, epsilon,
+                                  viewpoint.data(), n ? r.cov[0].data() : nullptr, n ? r.normals[0].data() : nullptr,
+                                  r.counts.data()));
+    return r;
   }
   const pcgx_kdtree *handle() const { return h_.get(); }
 

@@ -1,6 +1,7 @@
 """pc/storage/kdtree mirror: KDTree on the GPU behind the storage.Search shape
-(pc/storage/search.go:13-17): Vec3At / Len / Nearest, plus batched NearestBatch, and two extensions with no
-reference counterpart: surface normals (Normals) and k nearest neighbours (KNearest)."""
+(pc/storage/search.go:13-17): Vec3At / Len / Nearest, plus batched NearestBatch, and extensions with no
+reference counterpart: surface normals (Normals), k nearest neighbours (KNearest) and their covariances
+(Covariances)."""
 import ctypes as C
 
 import numpy as np
@@ -200,11 +201,52 @@ class KDTree:
             self._h, L.ptr(int(d_q)) if d_q else None, int(nq), int(k), float(maxRange), L.ptr(int(d_ids)),
             L.ptr(int(d_dsq)), L.ptr(int(d_counts)) if d_counts else None, L.ptr(stream) if stream else None))
 
+    # -- extension (no reference parity): covariances of k-NN neighbourhoods (Generalized ICP's input)
+    def Covariances(self, k, MaxRange=np.inf, Mode="plane", Epsilon=1e-3, Queries=None, Viewpoint=None):
+        """Covariance of the k nearest neighbours (KNearestBatch's lists) of every query -> (cov (n,6) float32 as xx,
+        xy, xz, yy, yz, zz; normals (n,3) float32; counts (n,) int32).  Mode "plane": I - (1 - Epsilon) u u^T, u the
+        unit normal (Segal's GICP regularisation); "raw": the covariance as it is.  Fewer than 3 neighbours, or all
+        at one place: I ("plane") / 0 ("raw"), normal 0.  Queries None: the tree's own points, in id order;
+        Viewpoint None: the origin (include/pcgx.h, pcgx_kdtree_covariances).  The normals always come back, so
+        "raw" runs the eigen-solve too; CovariancesDev without d_normals skips it."""
+        q = None if Queries is None else L.f32c(Queries).reshape(-1, 3)
+        n = self.Len() if q is None else len(q)
+        vp = None if Viewpoint is None else L.f32c(Viewpoint).reshape(3)
+        cov = np.empty((n, 6), np.float32)
+        normals = np.empty((n, 3), np.float32)
+        counts = np.empty(n, np.int32)
+        L.check(L.lib().pcgx_kdtree_covariances(self._h, L.ptr(q), n, int(k), float(MaxRange), _cov_mode(Mode),
+                                                float(Epsilon), L.ptr(vp), L.ptr(cov), L.ptr(normals), L.ptr(counts)))
+        return cov, normals, counts
+
+    def CovariancesDev(self, k, d_cov6, d_normals=0, d_counts=0, d_q=0, nq=None, MaxRange=np.inf, Mode="plane",
+                       Epsilon=1e-3, Viewpoint=None, stream=0):
+        """Device-resident Covariances: raw device addresses (e.g. torch .data_ptr()); d_q 0 takes the tree's own
+        points (nq = Len()).  Enqueued on `stream`, returns without waiting."""
+        if nq is None:
+            if d_q:
+                raise ValueError("nq is required with d_q")
+            nq = self.Len()
+        vp = None if Viewpoint is None else L.f32c(Viewpoint).reshape(3)
+        L.check(L.lib().pcgx_kdtree_covariances_dev(
+            self._h, L.ptr(int(d_q)) if d_q else None, int(nq), int(k), float(MaxRange), _cov_mode(Mode),
+            float(Epsilon), L.ptr(vp), L.ptr(int(d_cov6)), L.ptr(int(d_normals)) if d_normals else None,
+            L.ptr(int(d_counts)) if d_counts else None, L.ptr(stream) if stream else None))
+
     def NearestBatchDev(self, d_q, nq, maxRange, d_ids, d_dsq, presort=True, stream=0):
         """Device-resident variant: raw device addresses (e.g. torch .data_ptr())."""
         L.check(L.lib().pcgx_kdtree_nearest_batch_dev(
             self._h, L.ptr(d_q), nq, maxRange, self.MinDistSq, L.PCGX_KNN_PRESORT if presort else 0,
             L.ptr(d_ids), L.ptr(d_dsq), L.ptr(stream) if stream else None))
+
+
+def _cov_mode(mode):
+    """"plane" / "raw" (or the PCGX_COV_* value) -> pcgx_kdtree_covariances' mode"""
+    if isinstance(mode, str):
+        if mode not in ("plane", "raw"):
+            raise ValueError("Mode must be 'plane' or 'raw', not %r" % mode)
+        return L.PCGX_COV_PLANE if mode == "plane" else L.PCGX_COV_RAW
+    return int(mode)
 
 
 New = KDTree.New
