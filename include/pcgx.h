@@ -742,6 +742,9 @@ PCGX_API pcgx_status pcgx_icp_gauss_newton_update(const pcgx_icp_params *p, floa
  *   else, in float64 with d = p - q: C = sum d d^T / count - mean mean^T (mean = sum d / count), eigenvalues
  *   l0 <= l1 <= l2; normal = unit eigenvector of l0, negated if normal . (v - q) < 0, rounded to float32;
  *   curvature = max(l0, 0) / (l0 + l1 + l2) (PCL's surface variation).
+ *   Cancelled trace: when the float64 trace of C rounds to <= 0 the query is answered as if degenerate: normal
+ *   (0, 0, 0), curvature NaN.  sum d d^T / count - mean mean^T is within (2 count + 4) 2^-53 sum |d|^2 / count of the
+ *   exact C, so this happens only where the neighbours' spread is below ~1e-8 of their distance from the query.
  * q == NULL: the tree's own points (deleted ones included), nq must equal Len(); the output is in the tree's id
  * order, i.e. exactly the base_normals pcgx_icp_plane_session_create / pcgx_icp_plane_fit take.  curvature and
  * counts may be NULL.  A radius that is not finite and > 0, q == NULL with nq != Len() or normals == NULL with
@@ -798,6 +801,9 @@ PCGX_API pcgx_status pcgx_kdtree_knearest_dev(const pcgx_kdtree *t, const float 
  *   PCGX_COV_PLANE: I - (1 - epsilon) u u^T = V diag(epsilon, 1, 1) V^T, u the unit eigenvector of C's smallest
  *                   eigenvalue (pcgx_kdtree_normals' Jacobi solve): Segal's regularisation, fast_gicp's PLANE.
  *   Degenerate: n < 3, or all of N(q) at one place (the normals' exact box test): I for PLANE, 0 for RAW.
+ *   Cancelled trace: when the float64 trace of C rounds to <= 0 (only where the neighbours' spread is below ~1e-8 of
+ *   their distance from the query: each entry of C is within (2 n + 4) 2^-53 sum |d|^2 / n of the exact one) nothing
+ *   can be solved: PLANE is I and the normal 0 as if degenerate, RAW is C as computed (then not positive definite).
  *   cov6[6i .. 6i+5] = xx, xy, xz, yy, yz, zz in float32.
  *   normals (may be NULL): u turned towards the viewpoint (NULL: the origin) as pcgx_kdtree_normals turns it; 0 where
  *   degenerate.  counts (may be NULL): n.

@@ -7,7 +7,9 @@
 //   count  = |N(q)|; below max(min_neighbors, 3), or when all of N(q) coincide: normal 0, curvature NaN;
 //   else, in float64 with d = p - q (centred on the query: small cancellation), mean = sum d / count,
 //          C = sum d d^T / count - mean mean^T, eigenvalues l0 <= l1 <= l2:
-//          normal = unit eigenvector of l0 turned towards v, curvature = max(l0, 0) / (l0 + l1 + l2).
+//          normal = unit eigenvector of l0 turned towards v, curvature = max(l0, 0) / (l0 + l1 + l2);
+//          when the float64 trace of C rounds to <= 0 (the neighbours' spread below ~1e-8 of their distance from
+//          the query: the moments cancel) nothing can be solved: normal 0, curvature NaN, as if degenerate.
 // Nothing is materialised: each lane enumerates its query's neighbours exactly as the range kernels do and keeps
 // count, sum d (3), the upper triangle of sum d d^T (6) and the box of the neighbours (6 floats: "all coincide" is
 // exact, whatever the summation rounds) in registers, then solves the 3 x 3 eigenproblem in the same kernel by

@@ -146,7 +146,9 @@ class KDTree:
         """Unit normal of the radius neighbourhood (DistSq < radius^2, Range's set) of every query ->
         (normals (n,3) float32, curvature (n,) float32, counts (n,) int32).  Queries None: the tree's own
         points, in id order (the BaseNormals of PointToPlaneEvaluator).  Fewer than max(MinNeighbors, 3)
-        neighbours, or all of them at one place: normal 0, curvature NaN (include/pcgx.h)."""
+        neighbours, or all of them at one place: normal 0, curvature NaN (include/pcgx.h).  The same where the
+        float64 trace of the covariance rounds to <= 0, which takes neighbours whose spread is below ~1e-8 of
+        their distance from the query."""
         q = None if Queries is None else L.f32c(Queries).reshape(-1, 3)
         n = self.Len() if q is None else len(q)
         vp = L.f32c(Viewpoint).reshape(3)
@@ -206,7 +208,9 @@ class KDTree:
         """Covariance of the k nearest neighbours (KNearestBatch's lists) of every query -> (cov (n,6) float32 as xx,
         xy, xz, yy, yz, zz; normals (n,3) float32; counts (n,) int32).  Mode "plane": I - (1 - Epsilon) u u^T, u the
         unit normal (Segal's GICP regularisation); "raw": the covariance as it is.  Fewer than 3 neighbours, or all
-        at one place: I ("plane") / 0 ("raw"), normal 0.  Queries None: the tree's own points, in id order;
+        at one place: I ("plane") / 0 ("raw"), normal 0.  Where the float64 trace of the covariance rounds to <= 0
+        (neighbours whose spread is below ~1e-8 of their distance from the query): I ("plane") and normal 0 as well,
+        "raw" the covariance as computed.  Queries None: the tree's own points, in id order;
         Viewpoint None: the origin (include/pcgx.h, pcgx_kdtree_covariances).  The normals always come back, so
         "raw" runs the eigen-solve too; CovariancesDev without d_normals skips it."""
         q = None if Queries is None else L.f32c(Queries).reshape(-1, 3)

@@ -6,7 +6,12 @@ tests/knn_oracle.py gives, n = |N(q)|), mode and epsilon:
   degenerate (n < 3, or all of N(q) at one place): RAW 0, PLANE I, normal 0;
   RAW: C;  PLANE: I - (1 - eps) u u^T with u the unit eigenvector of C's smallest eigenvalue;
   normal: u, negated where u . (v - q) < 0.
-Six values per query: xx, xy, xz, yy, yz, zz."""
+Six values per query: xx, xy, xz, yy, yz, zz.
+
+This is the well-conditioned restatement: it evaluates the kernel's formula in the kernel's precision, so where that
+formula cancels (a query far from its neighbours compared with their spread) it is as wrong as the kernel, differently.
+tests/cov_exact.py is the reference that is exact there (rational arithmetic, with a derived error bound for the
+float64 formula); tests/test_gpu_cov_conditioning.py compares the kernels with it."""
 import numpy as np
 
 RAW, PLANE = 0, 1
