@@ -22,6 +22,7 @@
 
 #include "knn_grid.h"
 #include "knn_xwalk.h"
+#include "icp_step_plan.h"
 #include "strict_terms.h"
 
 namespace pcgx {
@@ -640,8 +641,7 @@ struct pcgx_icp_session {
   uint32_t *d_pos_of = nullptr;  // [nt] position of the caller's target i in the session's order
   uint32_t *d_orig_of = nullptr;      // strict sums: [nt] the caller's index of the target at a position
   float4 *d_match_caller = nullptr;   // strict sums: match[] in the caller's target order
-  bool caller_order_fresh = false;    // the last correspondence pass wrote d_match_caller as well
-  bool tile_sums_fresh = false;       // ... and formed the strict sums' float64 tile sums on its way out
+  bool caller_order_fresh = false;    // the last step left every pair in d_match_caller as well (decide_step; small_steps: not)
   int strict = 0;                // sequential float32 sums: 1 = in parallel (strict.hip), 2 = one wave (icp_strict_sums_kernel)
   bool strict_explicit = false;  // asked for by name (set_strict, PCGX_SUMS_REFERENCE_CHAIN, the environment): a sharded step refuses
                                  // it; the default (sums_mode 0) quietly becomes float64 sums there
@@ -661,9 +661,8 @@ struct pcgx_icp_session {
   int32_t host_iter = 0;     // Evaluates enqueued since the device's loop state was last WRITTEN (session made, reset, set_pose):
                              // what settle() compares with the device's num_iteration, which those writes zero -- not the updater's
                              // `iter`, which set_pose may start anywhere
-  bool spec_walk = true;     // the leftover walk is not launched behind a grid pass from a Fit's second Evaluate on (enqueue_corr)
+  bool spec_walk = true;     // the leftover walk is not launched behind a grid pass from a Fit's second Evaluate on (plan_step)
   bool spec_pending = false; // ... and steps enqueued that way have not been looked at yet (settle())
-  bool certify_next = false; // enqueue_corr left the step's correspondence to the summary kernel (CertifiedTerms): enqueue_strict
   hipStream_t spec_stream = nullptr;  // ... on this stream (entry points without a stream argument settle there)
   hipStream_t used[4] = {nullptr, nullptr, nullptr, nullptr};  // the streams work on this session's buffers was enqueued on
   int n_used = 0;                                               // (5: more than four -- pcgx_icp_session_free waits for the device)
@@ -1040,9 +1039,6 @@ extern "C" pcgx_status pcgx_icp_plane_session_create(const pcgx_kdtree *base, co
   return session_create(base, base_normals, damping, target, nt, on_device, params, d_sums30, out);
 }
 
-// Walk knobs of the ICP kernel (the hinted walk of iterations >= 1 profits from resolving wrong
-// leaf predictions in lockstep during the chunk preparation; the cold C2 walk does not):
-// PCGX_ICP_TIGHT (default 32: the whole descent), PCGX_ICP_CHUNKS (default 2 chunks per refill section).
 static int icp_knob(const char *name, int def, int lo, int hi) {
   if (const char *e = getenv(name)) {
     const int v = atoi(e);
@@ -1051,45 +1047,36 @@ static int icp_knob(const char *name, int def, int lo, int hi) {
   return def;
 }
 
-static pcgx_status enqueue_corr_patched(pcgx_icp_session *s, hipStream_t st) {
-  XTreeView xv;
-  PCGX_TRY(xtree_view(s->base, &xv, st));
-  const size_t lds = (size_t)(xv.depth > 1 ? xv.depth : 2) * kIcpBlock * sizeof(uint32_t);
-  const int64_t guard = xwalk_guard(s->base->n);
-  const float *x = s->d_xyz, *y = s->d_xyz + s->nt, *z = s->d_xyz + 2 * s->nt;
-  ProfScope prof(PCGX_PROF_ICP_WALK, st);
-  if (s->plane)
-    hipLaunchKernelGGL((icp_corr_xkernel<false, true>), dim3(s->grid), dim3(kIcpBlock), lds, st, xv, x, y, z, s->nt,
-                       s->d_state, s->kp, s->d_match, s->d_partials, s->d_match_id, (const float4 *)s->d_normals, guard);
-  else if (s->kp.min_dist_sq > 0.0f && s->strict)
-    hipLaunchKernelGGL((icp_corr_xkernel<true, false, false>), dim3(s->grid), dim3(kIcpBlock), lds, st, xv, x, y, z, s->nt,
-                       s->d_state, s->kp, s->d_match, s->d_partials, (uint32_t *)nullptr, (const float4 *)nullptr, guard);
-  else if (s->kp.min_dist_sq > 0.0f)
-    hipLaunchKernelGGL((icp_corr_xkernel<true, false>), dim3(s->grid), dim3(kIcpBlock), lds, st, xv, x, y, z, s->nt,
-                       s->d_state, s->kp, s->d_match, s->d_partials, (uint32_t *)nullptr, (const float4 *)nullptr, guard);
-  else if (s->strict)
-    hipLaunchKernelGGL((icp_corr_xkernel<false, false, false>), dim3(s->grid), dim3(kIcpBlock), lds, st, xv, x, y, z, s->nt,
-                       s->d_state, s->kp, s->d_match, s->d_partials, (uint32_t *)nullptr, (const float4 *)nullptr, guard);
-  else
-    hipLaunchKernelGGL((icp_corr_xkernel<false, false>), dim3(s->grid), dim3(kIcpBlock), lds, st, xv, x, y, z, s->nt,
-                       s->d_state, s->kp, s->d_match, s->d_partials, (uint32_t *)nullptr, (const float4 *)nullptr, guard);
-  PCGX_HIP_TRY(hipGetLastError());
-  return PCGX_OK;
+// The knobs of a step (icp_step_plan.h), read from the environment once per process, at its first step.
+static const StepKnobs &step_knobs() {
+  static const StepKnobs knobs = [] {
+    StepKnobs k;
+    k.tight = icp_knob("PCGX_ICP_TIGHT", 32, 0, 32);
+    k.chunks = icp_knob("PCGX_ICP_CHUNKS", 2, 1, 64);
+    k.left_blocks = icp_knob("PCGX_ICP_LEFTOVER_BLOCKS", 128, 8, 4096) & ~7;
+    k.cert_on = icp_knob("PCGX_ICP_CERT", 1, 0, 1) != 0;
+    k.spec_on = icp_knob("PCGX_ICP_SPEC_WALK", 1, 0, 1) != 0;
+    k.fused_from = icp_knob("PCGX_ICP_FUSED_FROM", 2, 0, 1 << 30);
+    k.test_force_walk = icp_knob("PCGX_TEST_ICP_FORCE_WALK", 0, 0, 1 << 30);
+    k.test_fused_search = icp_knob("PCGX_TEST_ICP_FUSED_SEARCH", 0, 0, 1 << 30);
+    k.test_fused_grid_walk = icp_knob("PCGX_TEST_ICP_FUSED_GRID_WALK", 0, 0, 1 << 30);
+    return k;
+  }();
+  return knobs;
 }
 
-static pcgx_status enqueue_corr(pcgx_icp_session *s, hipStream_t st, bool may_speculate = false) {
-  static const int tight = icp_knob("PCGX_ICP_TIGHT", 32, 0, 32), chunks = icp_knob("PCGX_ICP_CHUNKS", 2, 1, 64);
+// What the step that begins here launches: the resources it may need (each may fail softly), the session's facts,
+// plan_step().  The one place that writes what a step leaves for the next one.
+static pcgx_status decide_step(pcgx_icp_session *s, hipStream_t st, bool may_speculate, StepPlan *plan) {
   // a deletion made after the session was created: from now on the reference's patched tree is walked
   // (the same handle's Nearest / Range already do), without hints from earlier iterations
   if (!s->patched && s->base->n_deleted > 0) s->patched = true;
-  s->certify_next = false;
   PCGX_TRY(general_prepare(s, st));
-  const bool caller_had_pairs = s->caller_order_fresh;  // the pass before this one left every pair in the caller's order too
-  s->caller_order_fresh = false;
-  s->tile_sums_fresh = false;
-  if (s->patched) return enqueue_corr_patched(s, st);
-  if (s->strict == 1 && !s->plane && s->nt > 0) {
-    // the strict sums run in the caller's target order: the kernels below also leave every pair there
+  StepFacts f;
+  f.caller_had_pairs = s->caller_order_fresh;
+  s->caller_order_fresh = false;  // (a step that fails below leaves none)
+  if (!s->patched && s->strict == 1 && !s->plane && s->nt > 0) {
+    // the strict sums run in the caller's target order: the correspondence kernels also leave every pair there
     if (!s->d_match_caller) {
       hipError_t e = dev_cache_alloc((void **)&s->d_orig_of, (size_t)s->nt * sizeof(uint32_t));
       if (e == hipSuccess) e = dev_cache_alloc((void **)&s->d_match_caller, (size_t)s->nt * sizeof(float4));
@@ -1104,145 +1091,169 @@ static pcgx_status enqueue_corr(pcgx_icp_session *s, hipStream_t st, bool may_sp
                            (const uint32_t *)s->d_pos_of, s->nt, s->d_orig_of);
       }
     }
-    s->caller_order_fresh = s->d_match_caller != nullptr;
     if (!s->strict_buf)
       PCGX_TRY(strict_create(s->nt, s->d_xyz, s->d_xyz + s->nt, s->d_xyz + 2 * s->nt, (const uint32_t *)s->d_pos_of,
                              &s->strict_buf, st));
+    f.exchange = strict_work(s->strict_buf, s->kp)->exchange;
   }
-  TreeView tv = s->base->view();
-  tv.tight_levels = tight;
-  tv.chunks_per_refill = chunks;
-  const size_t lds = walk_lds_bytes(tv, kIcpBlock);
-  const float *x = s->d_xyz, *y = s->d_xyz + s->nt, *z = s->d_xyz + 2 * s->nt;
-  const bool grid = grid_enabled(s->base) && !(s->kp.min_dist_sq > 0.0f) && s->nt > 0;
-  // with the grid pass before it the correspondence kernel finds (nearly) every pair in place: its workgroups
-  // form the strict sums' tile sums on their way out (else strict_tilesum_kernel does, after this launch)
-  // (unless the summary kernel forms and exchanges them itself, StrictWork::exchange: the default)
-  s->tile_sums_fresh = grid && s->caller_order_fresh && s->strict == 1 && !s->plane && !strict_work(s->strict_buf, s->kp)->exchange;
-  const StrictWork strict_w = s->tile_sums_fresh ? *strict_work(s->strict_buf, s->kp) : StrictWork();
-  // Strict sessions behind a grid pass: the correspondence kernel is there for the few targets the grid could not
-  // certify (none at C4) and forms no sums -- 128 workgroups instead of two per CU: the launch of 512 of them, 66 KB
-  // of LDS each, cost 4-6 us per iteration to find nothing to do.
-  static const int left_blocks = icp_knob("PCGX_ICP_LEFTOVER_BLOCKS", 128, 8, 4096) & ~7;
-  const int n_corr = (grid && s->strict && !s->plane && s->grid > left_blocks) ? left_blocks : s->grid;
-  static const bool cert_on = icp_knob("PCGX_ICP_CERT", 1, 0, 1) != 0;  // (0: every pair is searched for, as before round 5)
-  float *cert = (grid && cert_on && s->base->grid.cert) ? s->d_match_cert : nullptr;
-  // The leftover walk behind the grid pass finds nothing to do in iteration after iteration (C4: never anything), and
-  // its launch is 5 us of a 70 us step.  From a Fit's second Evaluate on it is therefore NOT launched behind a strict
-  // session's grid pass -- on the speculation that the grid answers every target; a target it cannot answer ends the
-  // step on the device (icp_grid_kernel: `done` 2) and settle() enqueues it again with the walk, as every step after it.
-  static const bool spec_on = icp_knob("PCGX_ICP_SPEC_WALK", 1, 0, 1) != 0;
-  static const int test_force_walk = icp_knob("PCGX_TEST_ICP_FORCE_WALK", 0, 0, 1 << 30);
-  const bool no_walk = may_speculate && spec_on && s->spec_walk && grid && s->strict == 1 && !s->plane && s->host_iter >= 1 &&
-                       !s->tile_sums_fresh;
-  if (no_walk) {
+  f.patched = s->patched;
+  f.plane = s->plane;
+  f.strict = s->strict;
+  f.min_dist = s->kp.min_dist_sq > 0.0f;
+  f.has_targets = s->nt > 0;
+  f.grid_enabled = grid_enabled(s->base);
+  f.has_cert = s->base->grid.cert != nullptr;
+  f.have_match_caller = s->d_match_caller != nullptr;
+  f.spec_walk = s->spec_walk;
+  f.host_iter = s->host_iter;
+  f.may_speculate = may_speculate;
+  f.grid = s->grid;
+  *plan = plan_step(f, step_knobs());
+  s->caller_order_fresh = plan->next_caller_had_pairs;
+  if (plan->no_walk) {
     s->spec_pending = true;
     s->spec_stream = st;
   }
-  // From a Fit's K-th Evaluate on (PCGX_ICP_FUSED_FROM, 0: never) not even the grid pass runs: 98.5 % of the targets
-  // keep their partner from the third iteration on, and the summary kernel reads every target and its partner anyway --
-  // it tests the certificates and searches the rest itself (strict.hip, strict_sum_kernel<., ., true>).  The same
-  // speculation as no_walk: a target the grid cannot answer ends the step with `done` 2, settle() enqueues it again.
-  // (K = 2: 0.0673 ms a C4 step against 0.0680 with K = 3, where iteration 2 still runs the grid pass: DESIGN 3.1)
-  static const int fused_from = icp_knob("PCGX_ICP_FUSED_FROM", 2, 0, 1 << 30);
-  s->certify_next = no_walk && fused_from > 0 && s->host_iter >= fused_from && cert != nullptr && caller_had_pairs &&
-                    s->caller_order_fresh && strict_work(s->strict_buf, s->kp)->exchange;
-  if (s->certify_next) return PCGX_OK;  // (nothing in front of the summary kernel)
-  if (grid) {
-    ProfScope prof_grid(PCGX_PROF_ICP_GRID, st);
-    const unsigned gb = (unsigned)((s->nt + kIcpGridBlock - 1) / kIcpGridBlock);
-    if (s->plane)
-      hipLaunchKernelGGL(icp_grid_kernel<true>, dim3(xcd_grid(gb)), dim3(kIcpGridBlock), 0, st, s->base->grid, x, y, z, s->nt,
-                         s->d_state, s->kp, s->d_match, s->d_match_id, (const float4 *)s->d_normals, s->d_first_leaf,
-                         s->d_walk_list, s->d_walk_count, (uint32_t)s->grid, s->d_partials, (unsigned long long *)nullptr,
-                         (const uint32_t *)nullptr, (float4 *)nullptr, cert);
-    else if (s->strict)
-      hipLaunchKernelGGL((icp_grid_kernel<false, false, false>),
-                         dim3(xcd_grid((unsigned)((s->nt + kIcpStrictGridBlock - 1) / kIcpStrictGridBlock))),
-                         dim3(kIcpStrictGridBlock), 0, st, s->base->grid, x, y, z,
-                         s->nt, s->d_state, s->kp, s->d_match, s->d_match_id, (const float4 *)s->d_normals,
-                         s->d_first_leaf, s->d_walk_list, s->d_walk_count, (uint32_t)n_corr, s->d_partials,
-                         (unsigned long long *)nullptr, (const uint32_t *)(s->caller_order_fresh ? s->d_orig_of : nullptr),
-                         s->caller_order_fresh ? s->d_match_caller : nullptr, cert, caller_had_pairs ? 1 : 0, no_walk ? 0 : 1, test_force_walk);
-    else
-      hipLaunchKernelGGL(icp_grid_kernel<false>, dim3(xcd_grid(gb)), dim3(kIcpGridBlock), 0, st, s->base->grid, x, y, z, s->nt,
-                         s->d_state, s->kp, s->d_match, s->d_match_id, (const float4 *)s->d_normals, s->d_first_leaf,
-                         s->d_walk_list, s->d_walk_count, (uint32_t)s->grid, s->d_partials, (unsigned long long *)nullptr,
-                         (const uint32_t *)nullptr, (float4 *)nullptr, cert);
-  }
-  // timed (pcgx_prof_enable) when it is the kernel that does the work: with the grid pass before it
-  // it walks next to nothing, and a second pair of events per step costs more than it
-  if (no_walk) return PCGX_OK;  // (nothing behind the grid pass)
-  ProfScope prof(grid ? PCGX_PROF_ICP_LEFTOVER : PCGX_PROF_ICP_WALK, st);
-#define PCGX_LAUNCH_CORR(MD, PL, GR)                                                                                  \
-  do {                                                                                                                \
-  if (s->strict && !PL)                                                                                               \
-    hipLaunchKernelGGL((icp_corr_kernel<MD, false, GR, false>), dim3(n_corr), dim3(kIcpBlock), lds, st, tv, x, y, z, \
-                       s->nt, s->d_state, s->kp, s->d_match, s->d_first_leaf, s->d_partials, s->d_match_id,           \
-                       (const float4 *)s->d_normals, s->d_walk_list, s->d_walk_count,                                 \
-                       (int32_t)((s->nt + kIcpGridBlock - 1) / kIcpGridBlock),                                        \
-                       (const uint32_t *)(s->caller_order_fresh ? s->d_orig_of : nullptr),                            \
-                       s->caller_order_fresh ? s->d_match_caller : nullptr, strict_w,                                 \
-                       (int32_t)((GR) && s->tile_sums_fresh ? 1 : 0), cert, s->base->grid.cert);                      \
-  else                                                                                                                \
-  hipLaunchKernelGGL((icp_corr_kernel<MD, PL, GR>), dim3(s->grid), dim3(kIcpBlock), lds, st, tv, x, y, z, s->nt,     \
-                     s->d_state, s->kp, s->d_match, s->d_first_leaf, s->d_partials, s->d_match_id,                   \
-                     (const float4 *)s->d_normals, s->d_walk_list, s->d_walk_count,                                  \
-                     (int32_t)((s->nt + kIcpGridBlock - 1) / kIcpGridBlock), (const uint32_t *)nullptr,               \
-                     (float4 *)nullptr, StrictWork(), 0, cert, s->base->grid.cert);                                   \
-  } while (0)
-  if (s->plane) {
-    if (grid) PCGX_LAUNCH_CORR(false, true, true);
-    else PCGX_LAUNCH_CORR(false, true, false);
-  } else if (s->kp.min_dist_sq > 0.0f) {
-    PCGX_LAUNCH_CORR(true, false, false);
-  } else {
-    if (grid) PCGX_LAUNCH_CORR(false, false, true);
-    else PCGX_LAUNCH_CORR(false, false, false);
-  }
-#undef PCGX_LAUNCH_CORR
   return PCGX_OK;
 }
 
+static pcgx_status enqueue_corr_patched(pcgx_icp_session *s, hipStream_t st) {
+  XTreeView xv;
+  PCGX_TRY(xtree_view(s->base, &xv, st));
+  const size_t lds = (size_t)(xv.depth > 1 ? xv.depth : 2) * kIcpBlock * sizeof(uint32_t);
+  const int64_t guard = xwalk_guard(s->base->n);
+  const float *x = s->d_xyz, *y = s->d_xyz + s->nt, *z = s->d_xyz + 2 * s->nt;
+  ProfScope prof(PCGX_PROF_ICP_WALK, st);
+  const auto launch = [&](auto kernel) {  // (d_match_id, d_normals: a plane session's, else nullptr)
+    hipLaunchKernelGGL(kernel, dim3(s->grid), dim3(kIcpBlock), lds, st, xv, x, y, z, s->nt, s->d_state, s->kp, s->d_match,
+                       s->d_partials, s->d_match_id, (const float4 *)s->d_normals, guard);
+  };
+  const bool min_dist = s->kp.min_dist_sq > 0.0f;
+  if (s->plane) launch(icp_corr_xkernel<false, true>);
+  else if (min_dist && s->strict) launch(icp_corr_xkernel<true, false, false>);
+  else if (min_dist) launch(icp_corr_xkernel<true, false>);
+  else if (s->strict) launch(icp_corr_xkernel<false, false, false>);
+  else launch(icp_corr_xkernel<false, false>);
+  PCGX_HIP_TRY(hipGetLastError());
+  return PCGX_OK;
+}
+
+// The correspondence part of a step.  WHAT runs -- the patched tree's walk, the tree walk, the grid pass with or without
+// the leftover walk behind it, nothing (certified in the summary kernel) -- is decided by plan_step (icp_step_plan.h)
+// from the facts decide_step gathers; the reasons and measurements are beside the expressions there.
+static pcgx_status enqueue_corr(pcgx_icp_session *s, hipStream_t st, const StepPlan &p) {
+  if (p.corr == kCorrPatched) return enqueue_corr_patched(s, st);
+  if (p.corr == kCorrNone) return PCGX_OK;  // (nothing in front of the summary kernel)
+  const StepKnobs &k = step_knobs();
+  const float *x = s->d_xyz, *y = s->d_xyz + s->nt, *z = s->d_xyz + 2 * s->nt;
+  const uint32_t *orig_of = p.write_caller ? s->d_orig_of : nullptr;
+  float4 *match_caller = p.write_caller ? s->d_match_caller : nullptr;
+  float *cert = p.cert ? s->d_match_cert : nullptr;
+  const bool grid = p.corr != kCorrWalk;
+  if (grid) {
+    ProfScope prof_grid(PCGX_PROF_ICP_GRID, st);
+    const bool strict_grid = s->strict && !s->plane;  // (the variant that reads its last three arguments)
+    const auto launch = [&](auto kernel, int block) {
+      hipLaunchKernelGGL(kernel, dim3(xcd_grid((unsigned)((s->nt + block - 1) / block))), dim3(block), 0, st, s->base->grid, x,
+                         y, z, s->nt, s->d_state, s->kp, s->d_match, s->d_match_id, (const float4 *)s->d_normals,
+                         s->d_first_leaf, s->d_walk_list, s->d_walk_count, (uint32_t)p.n_corr, s->d_partials,
+                         (unsigned long long *)nullptr, orig_of, match_caller, cert, p.grid_has_caller_pairs ? 1 : 0,
+                         p.no_walk ? 0 : 1, strict_grid ? k.test_force_walk : 0);
+    };
+    if (s->plane) launch(icp_grid_kernel<true>, kIcpGridBlock);
+    else if (s->strict) launch(icp_grid_kernel<false, false, false>, kIcpStrictGridBlock);
+    else launch(icp_grid_kernel<false>, kIcpGridBlock);
+  }
+  // timed (pcgx_prof_enable) when it is the kernel that does the work: with the grid pass before it
+  // it walks next to nothing, and a second pair of events per step costs more than it
+  if (p.corr == kCorrGrid) return PCGX_OK;  // (nothing behind the grid pass)
+  ProfScope prof(grid ? PCGX_PROF_ICP_LEFTOVER : PCGX_PROF_ICP_WALK, st);
+  TreeView tv = s->base->view();
+  tv.tight_levels = k.tight;
+  tv.chunks_per_refill = k.chunks;
+  const size_t lds = walk_lds_bytes(tv, kIcpBlock);
+  const StrictWork strict_w = p.tile_sums ? *strict_work(s->strict_buf, s->kp) : StrictWork();
+  const auto launch = [&](auto kernel) {
+    hipLaunchKernelGGL(kernel, dim3(p.n_corr), dim3(kIcpBlock), lds, st, tv, x, y, z, s->nt, s->d_state, s->kp, s->d_match,
+                       s->d_first_leaf, s->d_partials, s->d_match_id, (const float4 *)s->d_normals, s->d_walk_list,
+                       s->d_walk_count, (int32_t)((s->nt + kIcpGridBlock - 1) / kIcpGridBlock), orig_of, match_caller, strict_w,
+                       (int32_t)(p.tile_sums ? 1 : 0), cert, s->base->grid.cert);
+  };
+  // (a strict session's kernels form no float64 sums: kSums false)
+  if (s->plane) {
+    if (grid) launch(icp_corr_kernel<false, true, true>);
+    else launch(icp_corr_kernel<false, true, false>);
+  } else if (s->kp.min_dist_sq > 0.0f) {
+    if (s->strict) launch(icp_corr_kernel<true, false, false, false>);
+    else launch(icp_corr_kernel<true, false, false>);
+  } else if (s->strict) {
+    if (grid) launch(icp_corr_kernel<false, false, true, false>);
+    else launch(icp_corr_kernel<false, false, false, false>);
+  } else {
+    if (grid) launch(icp_corr_kernel<false, false, true>);
+    else launch(icp_corr_kernel<false, false, false>);
+  }
+  return PCGX_OK;
+}
+
+// The pair array and its pos_of the strict sums read: pairs already in the caller's order need no gather through pos_of.
+struct StrictPairs {
+  const float4 *match;
+  const uint32_t *pos_of;
+};
+static StrictPairs strict_pairs(const pcgx_icp_session *s, bool caller_order) {
+  if (caller_order) return {s->d_match_caller, nullptr};
+  return {s->d_match, s->d_pos_of};
+}
+
+// The sums of a step behind its correspondence part, with or without the update of the loop state.
 template <bool kFuseUpdate>
-static pcgx_status enqueue_strict(pcgx_icp_session *s, hipStream_t st) {
+static pcgx_status enqueue_sums(pcgx_icp_session *s, hipStream_t st, const StepPlan &p) {
   if (s->strict == 1) {  // the whole GPU: strict.hip
     if (!s->strict_buf)
       PCGX_TRY(strict_create(s->nt, s->d_xyz, s->d_xyz + s->nt, s->d_xyz + 2 * s->nt, (const uint32_t *)s->d_pos_of,
                              &s->strict_buf, st));
-    const bool first_iter = s->host_iter++ == 0;
-    if (s->certify_next) {  // the step's correspondence in the summary kernel (enqueue_corr)
-      s->certify_next = false;
-      static const int force_search = icp_knob("PCGX_TEST_ICP_FUSED_SEARCH", 0, 0, 1 << 30);
-      static const int force_grid_walk = icp_knob("PCGX_TEST_ICP_FUSED_GRID_WALK", 0, 0, 1 << 30);
-      CertifiedTerms C;
+    s->host_iter++;
+    CertifiedTerms C;
+    if (p.certify) {  // the step's correspondence in the summary kernel
       C.grid = s->base->grid;
       C.max_dist_sq = s->kp.max_dist_sq;
       C.match_caller = s->d_match_caller;
       C.match = s->d_match;
       C.match_cert = s->d_match_cert;
       C.pos_of = s->d_pos_of;
-      C.test_force_walk = force_search;
-      C.test_force_grid_walk = force_grid_walk;
-      PCGX_TRY(strict_enqueue(s->strict_buf, (const float4 *)s->d_match_caller, (const uint32_t *)nullptr, s->d_state,
-                              s->d_sums, s->kp, kFuseUpdate, false, first_iter, st, &C));
-    } else if (s->caller_order_fresh)  // pairs already in the caller's order: no gather through pos_of
-      PCGX_TRY(strict_enqueue(s->strict_buf, (const float4 *)s->d_match_caller, (const uint32_t *)nullptr, s->d_state,
-                              s->d_sums, s->kp, kFuseUpdate, s->tile_sums_fresh, first_iter, st));
-    else
-      PCGX_TRY(strict_enqueue(s->strict_buf, (const float4 *)s->d_match, (const uint32_t *)s->d_pos_of, s->d_state,
-                              s->d_sums, s->kp, kFuseUpdate, false, first_iter, st));
-    return PCGX_OK;
-  }
-  // strict 2: the plain dependent chain, one wave (kept as the on-device cross-check of strict 1)
-  if (!s->d_terms) {  // first strict launch of the session
-    s->nt_pad = (s->nt + 63) & ~(int64_t)63;
-    const size_t np = (size_t)(s->nt_pad ? s->nt_pad : 64);
-    PCGX_HIP_TRY(dev_cache_alloc((void **)&s->d_terms, 9 * np * sizeof(float)));
-    PCGX_HIP_TRY(dev_cache_alloc((void **)&s->d_valid, (np / 64) * sizeof(unsigned long long)));
-  }
-  return strict_check_enqueue(s->d_xyz, s->nt, s->nt_pad, (const float4 *)s->d_match, (const uint32_t *)s->d_pos_of, s->d_state, s->kp,
-                              s->d_terms, s->d_valid, s->d_sums, kFuseUpdate, st);
+      C.test_force_walk = step_knobs().test_fused_search;
+      C.test_force_grid_walk = step_knobs().test_fused_grid_walk;
+    }
+    const StrictPairs pairs = strict_pairs(s, p.sums_caller);
+    PCGX_TRY(strict_enqueue(s->strict_buf, pairs.match, pairs.pos_of, s->d_state, s->d_sums, s->kp, kFuseUpdate,
+                            p.have_tile_sums, p.first_iter, st, p.certify ? &C : nullptr));
+  } else if (s->strict) {  // strict 2: the plain dependent chain, one wave (kept as the on-device cross-check of strict 1)
+    if (!s->d_terms) {  // first strict launch of the session
+      s->nt_pad = (s->nt + 63) & ~(int64_t)63;
+      const size_t np = (size_t)(s->nt_pad ? s->nt_pad : 64);
+      PCGX_HIP_TRY(dev_cache_alloc((void **)&s->d_terms, 9 * np * sizeof(float)));
+      PCGX_HIP_TRY(dev_cache_alloc((void **)&s->d_valid, (np / 64) * sizeof(unsigned long long)));
+    }
+    PCGX_TRY(strict_check_enqueue(s->d_xyz, s->nt, s->nt_pad, (const float4 *)s->d_match, (const uint32_t *)s->d_pos_of,
+                                  s->d_state, s->kp, s->d_terms, s->d_valid, s->d_sums, kFuseUpdate, st));
+  } else if (s->plane)
+    hipLaunchKernelGGL((icp_final_reduce_kernel<kFuseUpdate, true>), dim3(1), dim3(1024), 0, st, s->d_partials, s->grid,
+                       s->d_state, s->d_sums, s->kp);
+  else
+    hipLaunchKernelGGL((icp_final_reduce_kernel<kFuseUpdate, false>), dim3(1), dim3(64 * S_COUNT), 0, st, s->d_partials,
+                       s->grid, s->d_state, s->d_sums, s->kp);
+  PCGX_HIP_TRY(hipGetLastError());
+  return PCGX_OK;
+}
+
+// One Evaluate, decided (decide_step, plan_step) and enqueued; kFuseUpdate: and the update of the loop state behind it.
+template <bool kFuseUpdate>
+static pcgx_status enqueue_step(pcgx_icp_session *s, hipStream_t st, bool may_speculate) {
+  StepPlan plan;
+  PCGX_TRY(decide_step(s, st, may_speculate, &plan));
+  PCGX_TRY(enqueue_corr(s, st, plan));
+  return enqueue_sums<kFuseUpdate>(s, st, plan);
 }
 
 // Steps enqueued without the leftover walk (enqueue_corr) are looked at: if one of them met a target the grid could not
@@ -1267,10 +1278,7 @@ static pcgx_status settle(pcgx_icp_session *s, hipStream_t st) {
   // slots and set arrival bits, which the chain kernel -- gone at once -- did not zero)
   PCGX_TRY(strict_reset(s->strict_buf, st));
   s->host_iter = h.num_iteration;
-  for (int32_t k = 0; k < missing; k++) {
-    PCGX_TRY(enqueue_corr(s, st, false));
-    PCGX_TRY(enqueue_strict<true>(s, st));
-  }
+  for (int32_t k = 0; k < missing; k++) PCGX_TRY(enqueue_step<true>(s, st, false));  // (a replay never speculates)
   PCGX_HIP_TRY(hipGetLastError());
   return PCGX_OK;
 }
@@ -1294,17 +1302,7 @@ extern "C" pcgx_status pcgx_icp_session_partials(pcgx_icp_session *s, void *stre
   hipStream_t st = pick_stream(stream);
   s->touch(st);
   PCGX_TRY(settle(s, st));  // (steps enqueued without the leftover walk: enqueue_corr)
-  PCGX_TRY(enqueue_corr(s, st));
-  if (s->strict)
-    PCGX_TRY(enqueue_strict<false>(s, st));
-  else if (s->plane)
-    hipLaunchKernelGGL((icp_final_reduce_kernel<false, true>), dim3(1), dim3(1024), 0, st, s->d_partials, s->grid,
-                       s->d_state, s->d_sums, s->kp);
-  else
-    hipLaunchKernelGGL((icp_final_reduce_kernel<false, false>), dim3(1), dim3(64 * S_COUNT), 0, st, s->d_partials,
-                       s->grid, s->d_state, s->d_sums, s->kp);
-  PCGX_HIP_TRY(hipGetLastError());
-  return PCGX_OK;
+  return enqueue_step<false>(s, st, false);
 }
 
 extern "C" pcgx_status pcgx_icp_session_update(pcgx_icp_session *s, void *stream) {
@@ -1329,7 +1327,6 @@ static bool small_now(const pcgx_icp_session *s) {
 }
 static pcgx_status small_steps(pcgx_icp_session *s, hipStream_t st, int iters, uint32_t *mail_seq = nullptr) {
   s->caller_order_fresh = false;
-  s->tile_sums_fresh = false;
   s->host_iter += iters;
   static std::atomic<uint32_t> launches{0};  // (one count for the process: a block of the cache keeps its last session's words)
   // ONE such launch at a time on a device: its workgroups wait for each other inside the launch, all of them have to be
@@ -1368,17 +1365,7 @@ extern "C" pcgx_status pcgx_icp_session_step(pcgx_icp_session *s, void *stream) 
   hipStream_t st = pick_stream(stream);
   s->touch(st);
   if (small_now(s)) return small_steps(s, st, 1);
-  PCGX_TRY(enqueue_corr(s, st, true));
-  if (s->strict)
-    PCGX_TRY(enqueue_strict<true>(s, st));
-  else if (s->plane)
-    hipLaunchKernelGGL((icp_final_reduce_kernel<true, true>), dim3(1), dim3(1024), 0, st, s->d_partials, s->grid,
-                       s->d_state, s->d_sums, s->kp);
-  else
-    hipLaunchKernelGGL((icp_final_reduce_kernel<true, false>), dim3(1), dim3(64 * S_COUNT), 0, st, s->d_partials,
-                       s->grid, s->d_state, s->d_sums, s->kp);
-  PCGX_HIP_TRY(hipGetLastError());
-  return PCGX_OK;
+  return enqueue_step<true>(s, st, true);  // (not settled first: the step may be speculated on, plan_step)
 }
 
 // One iteration of a Fit whose target is spread over the ranks of `c`.  Two numeric modes:
@@ -1414,7 +1401,9 @@ static pcgx_status step_sharded_impl(pcgx_icp_session *s, pcgx_comm *c, void *st
     RingView ring;
     const bool have_ring = comm_ring_step(c, step, &ring);
     if (!s->shard_failed) {
-      const pcgx_status rc = enqueue_corr(s, st);
+      StepPlan plan;
+      pcgx_status rc = decide_step(s, st, false, &plan);
+      if (rc == PCGX_OK) rc = enqueue_corr(s, st, plan);
       if (rc != PCGX_OK) {
         *local_rc = rc;
         s->shard_failed = true;
@@ -1425,19 +1414,15 @@ static pcgx_status step_sharded_impl(pcgx_icp_session *s, pcgx_comm *c, void *st
                                            &s->strict_buf, st);
       if (rc != PCGX_OK) return rc;  // (no buffers at all: this rank cannot even raise its flag)
     }
+    // (a rank that failed enqueued no correspondence: what the session last left, as the plan of a step that was made)
+    const StrictPairs pairs = strict_pairs(s, s->caller_order_fresh);
     if (have_ring) {
       const bool first_iter = s->host_iter++ == 0;
-      if (s->caller_order_fresh)
-        return strict_enqueue_ring(s->strict_buf, (const float4 *)s->d_match_caller, (const uint32_t *)nullptr, s->d_state,
-                                   s->d_sums, s->kp, ring, s->shard_failed, first_iter, st);
-      return strict_enqueue_ring(s->strict_buf, (const float4 *)s->d_match, (const uint32_t *)s->d_pos_of, s->d_state,
-                                 s->d_sums, s->kp, ring, s->shard_failed, first_iter, st);
+      return strict_enqueue_ring(s->strict_buf, pairs.match, pairs.pos_of, s->d_state, s->d_sums, s->kp, ring, s->shard_failed,
+                                 first_iter, st);
     }
-    if (s->caller_order_fresh)
-      return strict_enqueue_sharded(s->strict_buf, (const float4 *)s->d_match_caller, (const uint32_t *)nullptr, s->d_state,
-                                    s->d_sums, s->kp, c, rank, world, s->shard_failed, st);
-    return strict_enqueue_sharded(s->strict_buf, (const float4 *)s->d_match, (const uint32_t *)s->d_pos_of, s->d_state,
-                                  s->d_sums, s->kp, c, rank, world, s->shard_failed, st);
+    return strict_enqueue_sharded(s->strict_buf, pairs.match, pairs.pos_of, s->d_state, s->d_sums, s->kp, c, rank, world,
+                                  s->shard_failed, st);
   }
   const int n = s->n_sums();
   if (!s->d_xchg) {

@@ -1,0 +1,103 @@
+#!/usr/bin/env python3
+"""Is the device code of this tree the device code of another commit?  (What a host-side refactor has to show.)
+
+For every file of pcgol_amd.build.SOURCES the device side is compiled to assembly (the flags of pcgol_amd/build.py plus
+--cuda-device-only -S) from the working tree and from `git archive REV`, and compared function by function: as maps
+name -> text of the functions (a kernel with its descriptor and resource comments) and of the entries of the
+code-object metadata, because the order in which template instantiations are emitted follows the host's launch sites
+and may move.  What moves with that order is normalised away: the function index in local labels (.LBB<i>_<n>,
+.Lfunc_end<i>, the comments' BB<i>_<n>) and the __hip_cuid_<hash> symbol, which differs between two compiles of one source.
+
+    python tools/compare_device_code.py [--rev HEAD] [--jobs 8] [file.hip ...]
+
+Needs hipcc, no GPU.  Exit status 0: every function of every file is textually identical."""
+import argparse
+import concurrent.futures
+import io
+import os
+import re
+import subprocess
+import sys
+import tarfile
+import tempfile
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from pcgol_amd import build as B  # noqa: E402
+
+BEGIN = re.compile(r"-- Begin function (\S+)")
+LABEL = re.compile(r"\b(L?BB|Lfunc_end|Lfunc_begin|Ltmp)\d+")  # (BB<i>_<n> without .L: the comments' loop headers)
+
+
+def device_asm(tree, src):
+    cmd = [B.hipcc()] + B.flags() + ["--cuda-device-only", "-S", "-w", "-o", "-",
+                                     os.path.join(tree, "pcgol_amd", "csrc", src)]
+    return subprocess.run(cmd, check=True, stdout=subprocess.PIPE, cwd=tree).stdout.decode()
+
+
+def split(asm):
+    """-> {key: text}: 'fn NAME' per function, 'meta NAME' per metadata entry, 'rest' for what belongs to no function"""
+    lines = [LABEL.sub(lambda m: m.group(1), ln) for ln in asm.splitlines() if "__hip_cuid_" not in ln]
+    out, key = {"rest": []}, "rest"
+    for ln in lines:
+        m = BEGIN.search(ln)
+        if m:
+            prev = out[key]
+            key = "fn " + m.group(1)
+            assert key not in out, key
+            # (the section switch in front of a function is the function's, not its predecessor's)
+            out[key] = [prev.pop()] if prev and prev[-1].split()[:1] in ([".text"], [".section"]) else []
+        elif ".AMDGPU.gpr_maximums" in ln or ln.strip() == ".amdgpu_metadata":
+            key = "rest"
+        out[key].append(ln)
+    # the metadata's kernel entries: a YAML list under amdhsa.kernels, each entry with its .name
+    rest, meta, entry = [], {}, None
+
+    def flush(entry):
+        name = [x.split(":", 1)[1].strip() for x in entry or [] if x.strip().startswith(".name:") and x.startswith("    .")]
+        if name:
+            meta["meta " + name[0]] = entry
+        else:
+            rest.extend(entry or [])
+
+    for ln in out["rest"] + [""]:
+        if ln.startswith("  - ") or not ln.startswith("    "):
+            flush(entry)
+            entry = [] if ln.startswith("  - ") else None
+        (rest if entry is None else entry).append(ln)
+    out["rest"] = rest
+    out.update(meta)
+    return {k: "\n".join(v) for k, v in out.items()}
+
+
+def compare(src, here, there):
+    a, b = split(device_asm(here, src)), split(device_asm(there, src))
+    differing = sorted(k for k in set(a) | set(b) if a.get(k) != b.get(k))
+    return src, sum(k.startswith("fn ") for k in a), sum(k.startswith("meta ") for k in a), differing
+
+
+def main():
+    ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    ap.add_argument("--rev", default="HEAD", help="the commit to compare the working tree with (default HEAD)")
+    ap.add_argument("--jobs", type=int, default=min(8, os.cpu_count() or 1))
+    ap.add_argument("sources", nargs="*", help="files of pcgol_amd/csrc (default: all of build.SOURCES)")
+    args = ap.parse_args()
+    sources = args.sources or B.SOURCES
+    with tempfile.TemporaryDirectory() as there:
+        tar = subprocess.run(["git", "-C", ROOT, "archive", args.rev, "pcgol_amd", "include"], check=True,
+                             stdout=subprocess.PIPE).stdout
+        tarfile.open(fileobj=io.BytesIO(tar)).extractall(there)
+        with concurrent.futures.ThreadPoolExecutor(args.jobs) as pool:
+            results = list(pool.map(lambda s: compare(s, ROOT, there), sources))
+    n_fn = n_kernels = n_diff = 0
+    for src, fns, kernels, differing in results:
+        print("%-24s %3d functions (%3d kernels): %s" % (src, fns, kernels, "identical" if not differing else "DIFFER"))
+        for k in differing:
+            print("    " + k)
+        n_fn, n_kernels, n_diff = n_fn + fns, n_kernels + kernels, n_diff + len(differing)
+    print("%d files, %d functions, %d kernels compared with %s: %d differ" % (len(results), n_fn, n_kernels, args.rev, n_diff))
+    return 1 if n_diff else 0
+
+
+if __name__ == "__main__":
+    sys.exit(main())
