@@ -9,6 +9,8 @@
 package icp
 
 import (
+	"math"
+
 	"github.com/seqsense/pcgol/mat"
 	"github.com/seqsense/pcgol/pc"
 	ref "github.com/seqsense/pcgol/pc/registration/icp"
@@ -179,4 +181,38 @@ func (r *PointToPointICPGradient) updater() *GradientDescentUpdaterFactory {
 		return u
 	}
 	return nil
+}
+
+// GeneralizedICP is Generalized ICP (Segal, Haehnel, Thrun 2009) beside the reference's point-to-point Fit: an
+// extension with no counterpart in the reference (include/pcgx.h "Generalized ICP").  Fit computes both clouds'
+// regularised-plane covariances from their K nearest neighbours on the device and registers; base must be a GPU tree.
+// Zero values: K 20, Epsilon 1e-3, neighbours at any distance, the updater's defaults (threshold 0.01, 20 iterations).
+type GeneralizedICP struct {
+	MaxDist      float32
+	MinPairs     int
+	K            int
+	Epsilon      float32
+	CovMaxRange  float32
+	Threshold    mat.Vec6
+	MaxIteration int
+	Damping      float32
+}
+
+func (r *GeneralizedICP) Fit(base storage.Search, target pc.Vec3RandomAccessor) (mat.Mat4, Stat, error) {
+	k, ok := base.(*pcgx.KDTree)
+	if !ok {
+		return mat.Mat4{}, Stat{}, pcgx.ErrNeedsDevice
+	}
+	kk, eps, rng := r.K, r.Epsilon, r.CovMaxRange
+	if kk == 0 {
+		kk = 20
+	}
+	if eps == 0 {
+		eps = 1e-3
+	}
+	if rng == 0 {
+		rng = float32(math.Inf(1))
+	}
+	g := pcgx.GICP{MaxDist: r.MaxDist, MinPairs: r.MinPairs, Threshold: r.Threshold, MaxIteration: r.MaxIteration, Damping: r.Damping}
+	return g.FitKNN(k, target, kk, rng, eps)
 }

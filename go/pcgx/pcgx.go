@@ -898,6 +898,83 @@ func FitPlane(base *KDTree, target pc.Vec3RandomAccessor, e *PlaneEvaluator, thr
 	return trans, stat, status(rc)
 }
 
+// ------------------------------------------ Generalized ICP (extension)
+
+// GICP is Generalized ICP (Segal, Haehnel, Thrun 2009; include/pcgx.h "Generalized ICP"): the residual r = p - b of
+// each nearest-point pair weighed by (C_b + R C_t R^T)^-1, Gauss-Newton on the same 6x6 normal equations as the
+// point-to-plane extension.  No counterpart in the reference.  Pairs whose covariances cannot be inverted are dropped
+// and do not count as pairs.
+type GICP struct {
+	MaxDist      float32
+	MinPairs     int
+	Threshold    mat.Vec6
+	MaxIteration int
+	Damping      float32
+}
+
+func (g *GICP) params() C.pcgx_icp_params {
+	var p C.pcgx_icp_params
+	p.max_dist, p.min_pairs, p.max_iteration = C.float(g.MaxDist), C.int32_t(g.MinPairs), C.int32_t(g.MaxIteration)
+	for i := 0; i < 6; i++ {
+		p.threshold[i] = C.float(g.Threshold[i])
+	}
+	return p
+}
+
+func gicpStat(st *C.pcgx_icp_stat, stat *icp.Stat, rc C.pcgx_status) error {
+	stat.NumIteration = int(st.num_iteration)
+	stat.Value = float32(st.evaluated.value)
+	for i := 0; i < 6; i++ {
+		stat.Gradient[i] = float32(st.evaluated.gradient[i])
+	}
+	if rc == C.PCGX_E_SINGULAR {
+		return ErrSingular
+	}
+	return status(rc)
+}
+
+// Fit takes the covariances from the caller: baseCov per base point in the tree's id order, targetCov per target
+// point in the target's own frame, each xx, xy, xz, yy, yz, zz (KDTree.Covariances of a tree over each cloud).
+func (g *GICP) Fit(base *KDTree, baseCov [][6]float32, target pc.Vec3RandomAccessor, targetCov [][6]float32) (mat.Mat4, icp.Stat, error) {
+	runtime.LockOSThread() // the error text is thread-local on the C side: call and pcgx_last_error on one OS thread
+	defer runtime.UnlockOSThread()
+	defer runtime.KeepAlive(base)
+	var trans mat.Mat4
+	stat := icp.Stat{}
+	if len(baseCov) != base.Len() || len(baseCov) == 0 || len(targetCov) != target.Len() || len(targetCov) == 0 {
+		return trans, stat, errors.New("pcgx: one covariance per base point and per target point is required")
+	}
+	p := g.params()
+	t := packVec3(target)
+	var st C.pcgx_icp_stat
+	rc := C.pcgx_icp_gicp_fit(base.t.h, (*C.float)(unsafe.Pointer(&baseCov[0][0])), (*C.float)(unsafe.Pointer(&t[0])),
+		(*C.float)(unsafe.Pointer(&targetCov[0][0])), C.int64_t(target.Len()), &p, C.float(g.Damping),
+		(*C.float)(unsafe.Pointer(&trans[0])), &st, (*C.float)(unsafe.Pointer(&stat.Hessian[0])))
+	runtime.KeepAlive(baseCov)
+	runtime.KeepAlive(targetCov)
+	return trans, stat, gicpStat(&st, &stat, rc)
+}
+
+// FitKNN is the one call: both clouds' regularised-plane covariances from their k nearest neighbours (CovPlane,
+// epsilon, neighbours within covMaxRange) are computed on the device and never leave it.
+func (g *GICP) FitKNN(base *KDTree, target pc.Vec3RandomAccessor, k int, covMaxRange, epsilon float32) (mat.Mat4, icp.Stat, error) {
+	runtime.LockOSThread() // the error text is thread-local on the C side: call and pcgx_last_error on one OS thread
+	defer runtime.UnlockOSThread()
+	defer runtime.KeepAlive(base)
+	var trans mat.Mat4
+	stat := icp.Stat{}
+	p := g.params()
+	t := packVec3(target)
+	var tp *C.float
+	if len(t) > 0 {
+		tp = (*C.float)(unsafe.Pointer(&t[0]))
+	}
+	var st C.pcgx_icp_stat
+	rc := C.pcgx_icp_gicp_fit_knn(base.t.h, tp, C.int64_t(target.Len()), C.int32_t(k), C.float(covMaxRange), C.float(epsilon),
+		&p, C.float(g.Damping), (*C.float)(unsafe.Pointer(&trans[0])), &st, (*C.float)(unsafe.Pointer(&stat.Hessian[0])))
+	return trans, stat, gicpStat(&st, &stat, rc)
+}
+
 // ------------------------------------------------- bucket grid, segmentation
 
 // BucketGrid is pc/storage/voxelgrid.VoxelGrid filled with Add(point i, i) for

@@ -823,6 +823,66 @@ PCGX_API pcgx_status pcgx_kdtree_covariances_dev(const pcgx_kdtree *t, const flo
                                                  const float viewpoint[3], float *d_cov6, float *d_normals,
                                                  int32_t *d_counts, void *stream);
 
+/* ------------------------------------------- Generalized ICP (extension: no reference parity)
+ * NOT in the reference: pcgol has nothing like it.  Generalized ICP (Segal, Haehnel, Thrun 2009; fast_gicp, PCL's
+ * GeneralizedIterativeClosestPoint) as a third kind of session and Fit beside point-to-point and point-to-plane: the
+ * consumer of pcgx_kdtree_covariances.  Tests check against a NumPy float64 restatement (tests/gicp_oracle.py).
+ * Inputs: a base tree; base_cov6[6 * Len()], float32 xx, xy, xz, yy, yz, zz per base id in id order -- exactly what
+ * pcgx_kdtree_covariances(q == NULL) writes, deleted ids included; the target, nt points; target_cov6[6 * nt] in the
+ * caller's target order, computed in the target's own frame.
+ * Pairs: at pose T (the session's float32 trans) exactly the pairs the reference corresponder finds for the
+ * re-projected target p_i = Mat4.Transform(T, target_i) (float32, the bits pcgx_mat4_transform gives): the partner is
+ * Nearest(p_i, MaxDist) on the base, after DeletePoint too.  MinDistSq > 0 is refused, as for plane sessions.  Before
+ * the first update (iter == 0) the target is a plain copy and T counts as the identity, as for the other kinds.
+ * Per pair (i -> base id j), everything float64 from the float32 inputs widened, R the upper-left 3 x 3 of T, the pose
+ * increment p' = p + t + w x p with parameters {t0, t1, t2, w0, w1, w2} as everywhere here:
+ *   r   = p_i - b_j
+ *   S   = C_b[j] + R C_t[i] R^T                           (symmetric 3 x 3)
+ *   M   = S^-1                                            (held fixed within an iteration: its dependence on R is
+ *                                                          not differentiated -- GICP as Segal and fast_gicp have it)
+ *   J_k = e_k (k = 0..2),  J_{3+k} = e_k x p_i            (d r / d parameter k)
+ *   e   = r^T M r;  g_k = J_k^T M r;  H_kl = J_k^T M J_l  (k <= l)
+ * The exchange vector has the plane session's 30 doubles: {sum e, sum g [6], upper triangle of sum H row-major [21],
+ * sum w, pair count} with w = 1; Evaluated.Value is the mean squared Mahalanobis distance.  Evaluate tail, Gauss-Newton
+ * update (flat test, damping, pose composition, iteration cap, PCGX_E_SINGULAR), sums_count / read_sums_n / hessian /
+ * result / reset / set_pose / partials / update / step / step_sharded and the host pieces
+ * pcgx_icp_plane_finish_evaluate / pcgx_icp_gauss_newton_update are the plane session's, unchanged.
+ * Pairs that cannot be inverted are DROPPED, and counted: a pair is used only if S is positive definite by the rule the
+ * Gauss-Newton solve uses -- trace(S) > 0 and every pivot of its float64 Cholesky factorisation > 1e-12 trace(S).  NaN
+ * or negative covariances fail that by themselves.  A dropped pair is in none of the 30 sums, the pair count included:
+ * MinPairs tests the pairs actually used.  pcgx_icp_gicp_session_dropped returns how many pairs the session's last
+ * evaluation dropped (on a sharded target: of this rank's tile).
+ *   PCGX_COV_PLANE covariances never drop a pair: S then has eigenvalues in [2 epsilon, 2], cond(S) <= 1 / epsilon
+ *   (degenerate points give I).
+ *   PCGX_COV_RAW covariances of a locally flat surface make S singular along the shared normal, and the pairs are
+ *   dropped: RAW is the caller's to regularise before it comes here.
+ * Restrictions, as for plane sessions: the default weight only; sums_mode is ignored (float64 sums in a fixed order:
+ * two runs are bit-identical); pcgx_icp_session_set_strict is refused; no one-launch small Fit.
+ * on_device covers the target and BOTH covariance arrays.  Device buffers: base_cov6 has been read when create
+ * returns; target and target_cov6 are read asynchronously on the library's stream and must stay alive until the
+ * session's first synchronising call (result, read_sums_n, dropped, ...).
+ * Sharded (pcgx_icp_session_step_sharded, the 30-double float64 exchange): a rank holds a tile of the target and that
+ * tile's covariances -- computed over the WHOLE target before it is cut into tiles, else the neighbourhoods at the
+ * tile borders differ from the unsharded Fit's.  pcgx_icp_fit_multi and the ring form are not offered. */
+PCGX_API pcgx_status pcgx_icp_gicp_session_create(const pcgx_kdtree *base, const float *base_cov6, const float *target,
+                                                  const float *target_cov6, int64_t nt, int32_t on_device,
+                                                  const pcgx_icp_params *params, float damping, double *d_sums30,
+                                                  pcgx_icp_session **out);
+/* Pairs the last evaluation dropped (0 before the first). */
+PCGX_API pcgx_status pcgx_icp_gicp_session_dropped(pcgx_icp_session *s, void *stream, int64_t *n);
+/* Whole Fit on the device from host arrays; hessian36 may be NULL.  PCGX_E_NOT_ENOUGH_PAIRS counts used pairs;
+ * PCGX_E_SINGULAR if sum H is not positive definite. */
+PCGX_API pcgx_status pcgx_icp_gicp_fit(const pcgx_kdtree *base, const float *base_cov6, const float *target,
+                                       const float *target_cov6, int64_t nt, const pcgx_icp_params *params,
+                                       float damping, float trans16[16], pcgx_icp_stat *stat, float hessian36[36]);
+/* The same from the clouds alone: builds a tree over the target (host memory), runs pcgx_kdtree_covariances_dev(k,
+ * cov_max_range, PCGX_COV_PLANE, epsilon) on both clouds and the Fit; the covariances never leave the device, and the
+ * result equals pcgx_kdtree_covariances on both clouds followed by pcgx_icp_gicp_fit bit for bit.  Returns the tree
+ * build's and the covariance calls' errors unchanged; nt == 0 is PCGX_E_NOT_ENOUGH_PAIRS. */
+PCGX_API pcgx_status pcgx_icp_gicp_fit_knn(const pcgx_kdtree *base, const float *target, int64_t nt, int32_t k,
+                                           float cov_max_range, float epsilon, const pcgx_icp_params *params,
+                                           float damping, float trans16[16], pcgx_icp_stat *stat, float hessian36[36]);
+
 /* ------------------------------------------- statistical outlier removal (extension: no reference parity)
  * PCL's StatisticalOutlierRemoval / Open3D's remove_statistical_outlier over an AoS cloud (stride / xyz_off as
  * pcgx_voxel_filter).

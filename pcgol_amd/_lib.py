@@ -255,6 +255,12 @@ SIGNATURES = {
     "pcgx_kdtree_knearest_dev": (_i32, [_vp, _vp, _i64, _i32, _f32, _vp, _vp, _vp, _vp]),
     "pcgx_kdtree_covariances": (_i32, [_vp, _vp, _i64, _i32, _f32, _i32, _f32, _vp, _vp, _vp, _vp]),
     "pcgx_kdtree_covariances_dev": (_i32, [_vp, _vp, _i64, _i32, _f32, _i32, _f32, _vp, _vp, _vp, _vp, _vp]),
+    "pcgx_icp_gicp_session_create": (_i32, [_vp, _vp, _vp, _vp, _i64, _i32, C.POINTER(IcpParams), _f32, _vp,
+                                            C.POINTER(_vp)]),
+    "pcgx_icp_gicp_session_dropped": (_i32, [_vp, _vp, C.POINTER(_i64)]),
+    "pcgx_icp_gicp_fit": (_i32, [_vp, _vp, _vp, _vp, _i64, C.POINTER(IcpParams), _f32, _vp, C.POINTER(IcpStat), _vp]),
+    "pcgx_icp_gicp_fit_knn": (_i32, [_vp, _vp, _i64, _i32, _f32, _f32, C.POINTER(IcpParams), _f32, _vp,
+                                     C.POINTER(IcpStat), _vp]),
     "pcgx_sor_filter": (_i32, [_vp, _i64, _i32, _i32, _i32, _f32, _i32, _vp, C.POINTER(_i64), _vp, _vp]),
     "pcgx_sor_filter_dev": (_i32, [_vp, _i64, _i32, _i32, _i32, _f32, _i32, _vp, C.POINTER(_i64), _vp, _vp, _vp]),
 }

@@ -24,6 +24,7 @@
 #include "knn_xwalk.h"
 #include "icp_step_plan.h"
 #include "strict_terms.h"
+#include "gicp_terms.h"
 
 namespace pcgx {
 
@@ -608,6 +609,111 @@ __global__ __launch_bounds__(256) void pack_normals_kernel(const float *__restri
   if (i < n) out[i] = make_float4(n3[3 * i], n3[3 * i + 1], n3[3 * i + 2], 0.0f);
 }
 
+// GICP sessions (include/pcgx.h, "Generalized ICP"): covariances xx, xy, xz, yy, yz, zz per base id -> two float4 per
+// id (one 32-byte gather per pair); the target's -> three float2 per target in the session's order (perm: position ->
+// the caller's index, nullptr: the caller's order).
+__global__ __launch_bounds__(256) void pack_base_cov_kernel(const float *__restrict__ c6, int64_t n,
+                                                            float4 *__restrict__ out) {
+  const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  out[2 * i] = make_float4(c6[6 * i], c6[6 * i + 1], c6[6 * i + 2], c6[6 * i + 3]);
+  out[2 * i + 1] = make_float4(c6[6 * i + 4], c6[6 * i + 5], 0.0f, 0.0f);
+}
+
+__global__ __launch_bounds__(256) void gather_target_cov_kernel(const float *__restrict__ c6,
+                                                                const int32_t *__restrict__ perm, int64_t n,
+                                                                float2 *__restrict__ out) {
+  const int64_t pos = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (pos >= n) return;
+  const int64_t i = perm ? (int64_t)perm[pos] : pos;
+  out[3 * pos] = make_float2(c6[6 * i], c6[6 * i + 1]);
+  out[3 * pos + 1] = make_float2(c6[6 * i + 2], c6[6 * i + 3]);
+  out[3 * pos + 2] = make_float2(c6[6 * i + 4], c6[6 * i + 5]);
+}
+
+// The sums of a GICP session's Evaluate, behind the correspondence kernels (which leave match[] / match_id[] and form
+// no sums of their own: kSums false): workgroup b streams targets [b per, (b + 1) per) of the session's order in a
+// fixed thread assignment -- the original point, re-projected as the correspondence kernels re-project it, its
+// covariance, its pair and the partner's covariance record (the one gather) -- forms the pair's terms (gicp_terms.h)
+// and reduces the 30 float64 sums in a fixed order (lanes, waves) into its row of block_partials;
+// icp_final_reduce_kernel<., true> follows.  A pair whose S is not positive definite is in none of the sums;
+// dropped[b] counts this workgroup's.  Algorithmic bytes per target: point 12, covariance 24, pair 16 + 4, partner's
+// covariance 32.
+constexpr int kGicpBlock = 256;
+
+__global__ __launch_bounds__(kGicpBlock) void icp_gicp_sums_kernel(
+    const float *__restrict__ tx, const float *__restrict__ ty, const float *__restrict__ tz, int64_t nt,
+    const IcpState *__restrict__ state, const float4 *__restrict__ match, const uint32_t *__restrict__ match_id,
+    const float4 *__restrict__ base_cov, const float2 *__restrict__ target_cov, double *__restrict__ block_partials,
+    uint32_t *__restrict__ dropped) {
+  constexpr int NS = (int)P_COUNT;
+  __shared__ double s_red[kGicpBlock / 64][NS];
+  __shared__ uint32_t s_drop[kGicpBlock / 64];
+  if (state->done) return;  // uniform
+  // Before the first update targetTransformed is a plain copy (icp.go:27-30): the pose is the identity then
+  const bool project = state->iter > 0;
+  float m[16];
+#pragma unroll
+  for (int i = 0; i < 16; i++) m[i] = project ? state->trans[i] : (i % 5 == 0 ? 1.0f : 0.0f);
+  double acc[NS];
+#pragma unroll
+  for (int k = 0; k < NS; k++) acc[k] = 0.0;
+  uint32_t n_drop = 0;
+  const int64_t per = (nt + gridDim.x - 1) / gridDim.x;
+  const int64_t r_begin = (int64_t)blockIdx.x * per;
+  int64_t r_end = r_begin + per;
+  if (r_end > nt) r_end = nt;
+  for (int64_t i = r_begin + threadIdx.x; i < r_end; i += kGicpBlock) {
+    // every load of the target's own record is issued before the first use
+    const float4 bp = match[i];
+    float x0 = tx[i], y0 = ty[i], z0 = tz[i];
+    const float2 t0 = target_cov[3 * i], t1 = target_cov[3 * i + 1], t2 = target_cov[3 * i + 2];
+    if (bp.w >= 0.0f) {  // correspondence.go:27-29
+      const uint32_t id = match_id[i];
+      const float4 c0 = base_cov[2 * (int64_t)id], c1 = base_cov[2 * (int64_t)id + 1];
+      if (project) {  // icp.go:62-64
+        float px, py, pz;
+        mat4_transform(m, x0, y0, z0, px, py, pz);
+        x0 = px; y0 = py; z0 = pz;
+      }
+      const float cb[6] = {c0.x, c0.y, c0.z, c0.w, c1.x, c1.y};
+      const float ct[6] = {t0.x, t0.y, t1.x, t1.y, t2.x, t2.y};
+      double e, g[6], H[21];
+      if (gicp_terms(x0, y0, z0, bp.x, bp.y, bp.z, cb, ct, m, e, g, H)) {
+        acc[P_VALUE] += e;
+#pragma unroll
+        for (int a = 0; a < 6; a++) acc[P_G0 + a] += g[a];
+#pragma unroll
+        for (int a = 0; a < 21; a++) acc[P_H0 + a] += H[a];
+        acc[P_WEIGHT] += 1.0;
+        acc[P_PAIRS] += 1.0;
+      } else {
+        n_drop++;
+      }
+    }
+  }
+  const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+#pragma unroll
+  for (int k = 0; k < NS; k++) {
+    const double v = wave_sum_f64(acc[k]);
+    if (lane == 0) s_red[wave][k] = v;
+  }
+#pragma unroll
+  for (int o = 32; o > 0; o >>= 1) n_drop += __shfl_down(n_drop, o);
+  if (lane == 0) s_drop[wave] = n_drop;
+  __syncthreads();
+  if (threadIdx.x < NS) {
+    double v = 0.0;
+    for (int w = 0; w < kGicpBlock / 64; w++) v += s_red[w][threadIdx.x];
+    block_partials[(int64_t)blockIdx.x * NS + threadIdx.x] = v;
+  }
+  if (threadIdx.x == 0) {
+    uint32_t d = 0;
+    for (int w = 0; w < kGicpBlock / 64; w++) d += s_drop[w];
+    dropped[blockIdx.x] = d;
+  }
+}
+
 __global__ __launch_bounds__(256) void invert_positions_kernel(const uint32_t *__restrict__ pos_of, int64_t n,
                                                                uint32_t *__restrict__ orig_of) {
   const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
@@ -684,6 +790,13 @@ struct pcgx_icp_session {
   bool plane = false;              // point-to-plane / Gauss-Newton session (30 sums)
   uint32_t *d_match_id = nullptr;  // plane: [nt] matched base id
   float4 *d_normals = nullptr;     // plane: [base n] unit normals in base id order
+  // GICP sessions (include/pcgx.h, "Generalized ICP"): plane is set as well -- the same 30 sums, Gauss-Newton update, no
+  // reference sums, no strict path; d_normals stays nullptr, the correspondence kernels form no sums (kSums false)
+  bool gicp = false;
+  float4 *d_base_cov = nullptr;    // gicp: [2 * base n] covariance record per base id
+  float2 *d_target_cov = nullptr;  // gicp: [3 * nt] covariances in the session's target order
+  uint32_t *d_dropped = nullptr;   // gicp: [gicp_grid] pairs dropped in the last evaluation, per workgroup
+  int gicp_grid = 1;               // gicp: workgroups of icp_gicp_sums_kernel = its rows of d_partials
   int n_sums() const { return plane ? (int)P_COUNT : (int)S_COUNT; }
   int grid = 1;
   IcpKernelParams kp;
@@ -849,6 +962,9 @@ extern "C" pcgx_status pcgx_icp_session_free(pcgx_icp_session *s) {
   dev_cache_free(s->d_walk_count);
   dev_cache_free(s->d_match_id);
   dev_cache_free(s->d_normals);
+  dev_cache_free(s->d_base_cov);
+  dev_cache_free(s->d_target_cov);
+  dev_cache_free(s->d_dropped);
   if (s->own_sums) dev_cache_free(s->d_sums);
   dev_cache_free(s->d_xchg);
   dev_cache_free(s->d_small_sync);
@@ -859,10 +975,13 @@ extern "C" pcgx_status pcgx_icp_session_free(pcgx_icp_session *s) {
 
 // normals == nullptr: the reference's point-to-point session; else a plane session (normals:
 // packed xyz per base point in id order, host or device memory like the target).
+// base_cov6 != nullptr: a GICP session (base_cov6 per base id, target_cov6 per target in the caller's order; where the
+// target is).
 static pcgx_status session_create(const pcgx_kdtree *base, const float *normals, float damping,
                                   const float *target, int64_t nt, int32_t target_on_device,
                                   const pcgx_icp_params *params, double *d_sums,
-                                  pcgx_icp_session **out) {
+                                  pcgx_icp_session **out, const float *base_cov6 = nullptr,
+                                  const float *target_cov6 = nullptr) {
   if (!out) return fail(PCGX_E_INVALID, "pcgx_icp_session_create: out is NULL");
   *out = nullptr;
   if (!base || !params || nt < 0 || (nt > 0 && !target))
@@ -872,6 +991,8 @@ static pcgx_status session_create(const pcgx_kdtree *base, const float *normals,
                                 "cannot run on the device)", params->weight_fn);
   if (normals && params->weight_fn != PCGX_WEIGHT_ONE)
     return fail(PCGX_E_INVALID, "the point-to-plane extension takes the default weight only");
+  if (base_cov6 && params->weight_fn != PCGX_WEIGHT_ONE)
+    return fail(PCGX_E_INVALID, "the GICP extension takes the default weight only");
   if (params->sums_mode < 0 || params->sums_mode >= PCGX_SUMS_KINDS)
     return fail(PCGX_E_INVALID, "pcgx_icp_session_create: sums_mode %d is none of PCGX_SUMS_*", params->sums_mode);
   PCGX_TRY(ensure_init());
@@ -892,7 +1013,8 @@ static pcgx_status session_create(const pcgx_kdtree *base, const float *normals,
   s->patched = patched;
   const_cast<pcgx_kdtree *>(base)->sessions.fetch_add(1);
   s->nt = nt;
-  s->plane = normals != nullptr;
+  s->gicp = base_cov6 != nullptr;
+  s->plane = normals != nullptr || s->gicp;
   // the reference's own sums unless the caller asks otherwise (include/pcgx.h, PCGX_SUMS_*); the
   // point-to-plane extension has no reference sums to reproduce
   s->strict = s->plane ? 0 : (params->sums_mode == PCGX_SUMS_REFERENCE ? 1 : (params->sums_mode == PCGX_SUMS_F64_TREE ? 0 : 2));
@@ -905,6 +1027,10 @@ static pcgx_status session_create(const pcgx_kdtree *base, const float *normals,
   s->kp.gn.damping = damping;
   s->max_iteration = s->kp.upd.max_iteration;
   s->grid = icp_grid(nt, base->view());
+  if (s->gicp) {
+    const int64_t g = (nt + kGicpBlock - 1) / kGicpBlock, cap = (int64_t)ctx().num_cu * 8;
+    s->gicp_grid = (int)(g < 1 ? 1 : (g > cap ? cap : g));
+  }
   pcgx_status rc = PCGX_OK;
   auto bail = [&](pcgx_status code) {
     pcgx_icp_session_free(s);
@@ -914,7 +1040,8 @@ static pcgx_status session_create(const pcgx_kdtree *base, const float *normals,
   if ((e = dev_cache_alloc((void **)&s->d_xyz, (size_t)(nt ? nt : 1) * 12)) != hipSuccess ||
       (e = dev_cache_alloc((void **)&s->d_state, sizeof(IcpState))) != hipSuccess ||
       (e = dev_cache_alloc((void **)&s->d_partials,
-                           ((size_t)s->grid + (size_t)(nt / kIcpGridBlock) + 1) * s->n_sums() * sizeof(double))) != hipSuccess ||
+                           ((size_t)s->grid + (size_t)(nt / kIcpGridBlock) + 1 + (size_t)(s->gicp ? s->gicp_grid : 0)) *
+                               s->n_sums() * sizeof(double))) != hipSuccess ||
       (e = dev_cache_alloc((void **)&s->d_pos_of, (size_t)(nt ? nt : 1) * sizeof(uint32_t))) != hipSuccess ||
       (e = dev_cache_alloc((void **)&s->d_match, (size_t)(nt ? nt : 1) * sizeof(float4))) != hipSuccess ||
       (e = dev_cache_alloc((void **)&s->d_match_cert, (size_t)(nt ? nt : 1) * sizeof(float))) != hipSuccess ||
@@ -929,7 +1056,29 @@ static pcgx_status session_create(const pcgx_kdtree *base, const float *normals,
       return bail(fail(PCGX_E_OOM, "icp session allocation failed: %s", hipGetErrorString(e)));
     s->own_sums = true;
   }
-  if (s->plane) {
+  if (s->gicp) {
+    const int64_t nb = n_base_ids;
+    if ((e = dev_cache_alloc((void **)&s->d_match_id, (size_t)(nt ? nt : 1) * sizeof(uint32_t))) != hipSuccess ||
+        (e = dev_cache_alloc((void **)&s->d_base_cov, (size_t)nb * 2 * sizeof(float4))) != hipSuccess ||
+        (e = dev_cache_alloc((void **)&s->d_target_cov, (size_t)(nt ? nt : 1) * 3 * sizeof(float2))) != hipSuccess ||
+        (e = dev_cache_alloc((void **)&s->d_dropped, (size_t)s->gicp_grid * sizeof(uint32_t))) != hipSuccess)
+      return bail(fail(PCGX_E_OOM, "icp session allocation failed: %s", hipGetErrorString(e)));
+    if ((e = hipMemsetAsync(s->d_dropped, 0, (size_t)s->gicp_grid * sizeof(uint32_t), st)) != hipSuccess)
+      return bail(fail(PCGX_E_HIP, "icp session setup failed: %s", hipGetErrorString(e)));
+    Arena &ar = ctx().arena;
+    if ((rc = ar.begin(st)) != PCGX_OK) return bail(rc);
+    const float *d_c6 = base_cov6;
+    if (!target_on_device) {
+      float *stage = nullptr;
+      if ((rc = ar.alloc_n((size_t)nb * 6, &stage)) != PCGX_OK) return bail(rc);
+      if ((rc = staged_upload(stage, base_cov6, (size_t)nb * 24, st)) != PCGX_OK) return bail(rc);
+      d_c6 = stage;
+    }
+    hipLaunchKernelGGL(pack_base_cov_kernel, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, st, d_c6, nb,
+                       s->d_base_cov);
+    if ((e = hipStreamSynchronize(st)) != hipSuccess)
+      return bail(fail(PCGX_E_HIP, "icp session setup failed: %s", hipGetErrorString(e)));
+  } else if (s->plane) {
     const int64_t nb = n_base_ids;
     if ((e = dev_cache_alloc((void **)&s->d_match_id, (size_t)(nt ? nt : 1) * sizeof(uint32_t))) != hipSuccess ||
         (e = dev_cache_alloc((void **)&s->d_normals, (size_t)nb * sizeof(float4))) != hipSuccess)
@@ -1004,6 +1153,17 @@ static pcgx_status session_create(const pcgx_kdtree *base, const float *normals,
     if (!s->small)
       hipLaunchKernelGGL(gather_soa_kernel, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, st, d_q, perm, nt,
                          s->d_xyz, s->d_xyz + nt, s->d_xyz + 2 * nt, s->d_pos_of);
+    if (s->gicp) {  // the target's covariances, into the same order
+      const float *d_c6 = target_cov6;
+      if (!target_on_device) {
+        float *stage = nullptr;
+        if ((rc = ar.alloc_n((size_t)nt * 6, &stage)) != PCGX_OK) return bail(rc);
+        if ((rc = staged_upload(stage, target_cov6, (size_t)nt * 24, st)) != PCGX_OK) return bail(rc);
+        d_c6 = stage;
+      }
+      hipLaunchKernelGGL(gather_target_cov_kernel, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, st, d_c6,
+                         (const int32_t *)perm, nt, s->d_target_cov);
+    }
     t_phase[4] = trace ? now_us() : 0.0;  // order + gather enqueued
     // No wait here: what follows on this session is enqueued on this stream, behind the gather, or on another stream
     // through an entry point that names it -- those wait for this one first (touch(): a session's first use on a stream
@@ -1037,6 +1197,35 @@ extern "C" pcgx_status pcgx_icp_plane_session_create(const pcgx_kdtree *base, co
     return fail(PCGX_E_INVALID, "pcgx_icp_plane_session_create: MinDistSq > 0 (approximate search) is not offered here");
   if (!(damping >= 0.0f)) return fail(PCGX_E_INVALID, "pcgx_icp_plane_session_create: damping must be >= 0");
   return session_create(base, base_normals, damping, target, nt, on_device, params, d_sums30, out);
+}
+
+extern "C" pcgx_status pcgx_icp_gicp_session_create(const pcgx_kdtree *base, const float *base_cov6, const float *target,
+                                                    const float *target_cov6, int64_t nt, int32_t on_device,
+                                                    const pcgx_icp_params *params, float damping, double *d_sums30,
+                                                    pcgx_icp_session **out) {
+  PCGX_API_LOCK();
+  if (!base_cov6 || (nt > 0 && !target_cov6))
+    return fail(PCGX_E_INVALID, "pcgx_icp_gicp_session_create: a covariance array is NULL");
+  if (params && params->min_dist_sq > 0.0f)
+    return fail(PCGX_E_INVALID, "pcgx_icp_gicp_session_create: MinDistSq > 0 (approximate search) is not offered here");
+  if (!(damping >= 0.0f)) return fail(PCGX_E_INVALID, "pcgx_icp_gicp_session_create: damping must be >= 0");
+  return session_create(base, nullptr, damping, target, nt, on_device, params, d_sums30, out, base_cov6, target_cov6);
+}
+
+extern "C" pcgx_status pcgx_icp_gicp_session_dropped(pcgx_icp_session *s, void *stream, int64_t *n) {
+  PCGX_API_LOCK();
+  if (!s || !n) return fail(PCGX_E_INVALID, "pcgx_icp_gicp_session_dropped: bad argument");
+  if (!s->gicp) return fail(PCGX_E_INVALID, "pcgx_icp_gicp_session_dropped: not a GICP session");
+  hipStream_t st = pick_stream(stream);
+  s->touch(st);
+  PCGX_TRY(settle(s, st));
+  std::vector<uint32_t> h((size_t)s->gicp_grid);
+  PCGX_HIP_TRY(hipMemcpyAsync(h.data(), s->d_dropped, h.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  PCGX_HIP_TRY(hipStreamSynchronize(st));
+  int64_t sum = 0;
+  for (uint32_t v : h) sum += (int64_t)v;
+  *n = sum;
+  return PCGX_OK;
 }
 
 static int icp_knob(const char *name, int def, int lo, int hi) {
@@ -1129,7 +1318,8 @@ static pcgx_status enqueue_corr_patched(pcgx_icp_session *s, hipStream_t st) {
                        s->d_partials, s->d_match_id, (const float4 *)s->d_normals, guard);
   };
   const bool min_dist = s->kp.min_dist_sq > 0.0f;
-  if (s->plane) launch(icp_corr_xkernel<false, true>);
+  if (s->gicp) launch(icp_corr_xkernel<false, true, false>);  // (pairs and ids only: icp_gicp_sums_kernel follows)
+  else if (s->plane) launch(icp_corr_xkernel<false, true>);
   else if (min_dist && s->strict) launch(icp_corr_xkernel<true, false, false>);
   else if (min_dist) launch(icp_corr_xkernel<true, false>);
   else if (s->strict) launch(icp_corr_xkernel<false, false, false>);
@@ -1160,7 +1350,8 @@ static pcgx_status enqueue_corr(pcgx_icp_session *s, hipStream_t st, const StepP
                          (unsigned long long *)nullptr, orig_of, match_caller, cert, p.grid_has_caller_pairs ? 1 : 0,
                          p.no_walk ? 0 : 1, strict_grid ? k.test_force_walk : 0);
     };
-    if (s->plane) launch(icp_grid_kernel<true>, kIcpGridBlock);
+    if (s->gicp) launch(icp_grid_kernel<true, false, false>, kIcpGridBlock);  // (pairs and ids only)
+    else if (s->plane) launch(icp_grid_kernel<true>, kIcpGridBlock);
     else if (s->strict) launch(icp_grid_kernel<false, false, false>, kIcpStrictGridBlock);
     else launch(icp_grid_kernel<false>, kIcpGridBlock);
   }
@@ -1180,7 +1371,10 @@ static pcgx_status enqueue_corr(pcgx_icp_session *s, hipStream_t st, const StepP
                        (int32_t)(p.tile_sums ? 1 : 0), cert, s->base->grid.cert);
   };
   // (a strict session's kernels form no float64 sums: kSums false)
-  if (s->plane) {
+  if (s->gicp) {
+    if (grid) launch(icp_corr_kernel<false, true, true, false>);
+    else launch(icp_corr_kernel<false, true, false, false>);
+  } else if (s->plane) {
     if (grid) launch(icp_corr_kernel<false, true, true>);
     else launch(icp_corr_kernel<false, true, false>);
   } else if (s->kp.min_dist_sq > 0.0f) {
@@ -1237,6 +1431,13 @@ static pcgx_status enqueue_sums(pcgx_icp_session *s, hipStream_t st, const StepP
     }
     PCGX_TRY(strict_check_enqueue(s->d_xyz, s->nt, s->nt_pad, (const float4 *)s->d_match, (const uint32_t *)s->d_pos_of,
                                   s->d_state, s->kp, s->d_terms, s->d_valid, s->d_sums, kFuseUpdate, st));
+  } else if (s->gicp) {
+    const float *x = s->d_xyz, *y = s->d_xyz + s->nt, *z = s->d_xyz + 2 * s->nt;
+    hipLaunchKernelGGL(icp_gicp_sums_kernel, dim3(s->gicp_grid), dim3(kGicpBlock), 0, st, x, y, z, s->nt, s->d_state,
+                       (const float4 *)s->d_match, (const uint32_t *)s->d_match_id, (const float4 *)s->d_base_cov,
+                       (const float2 *)s->d_target_cov, s->d_partials, s->d_dropped);
+    hipLaunchKernelGGL((icp_final_reduce_kernel<kFuseUpdate, true>), dim3(1), dim3(1024), 0, st, s->d_partials,
+                       s->gicp_grid, s->d_state, s->d_sums, s->kp);
   } else if (s->plane)
     hipLaunchKernelGGL((icp_final_reduce_kernel<kFuseUpdate, true>), dim3(1), dim3(1024), 0, st, s->d_partials, s->grid,
                        s->d_state, s->d_sums, s->kp);
@@ -1669,6 +1870,7 @@ extern "C" pcgx_status pcgx_icp_fit_multi(int32_t n, const pcgx_kdtree *const *b
 }
 
 static pcgx_status result_of(const pcgx_icp_session *s, const IcpState &h, float trans16[16], pcgx_icp_stat *stat, int32_t *converged);
+static pcgx_status run_gauss_newton_fit(pcgx_icp_session *s, float trans16[16], pcgx_icp_stat *stat, float hessian36[36]);
 
 extern "C" pcgx_status pcgx_icp_session_result(pcgx_icp_session *s, void *stream, float trans16[16],
                                                pcgx_icp_stat *stat, int32_t *converged) {
@@ -1724,11 +1926,62 @@ extern "C" pcgx_status pcgx_icp_plane_fit(const pcgx_kdtree *base, const float *
   if (!base || !params || !trans16) return fail(PCGX_E_INVALID, "pcgx_icp_plane_fit: NULL argument");
   pcgx_icp_session *s = nullptr;
   PCGX_TRY(pcgx_icp_plane_session_create(base, base_normals, target, nt, 0, params, damping, nullptr, &s));
+  return run_gauss_newton_fit(s, trans16, stat, hessian36);
+}
+
+// The Fit loop of a plane or GICP session made by the caller: steps, result, Hessian; the session is freed.
+static pcgx_status run_gauss_newton_fit(pcgx_icp_session *s, float trans16[16], pcgx_icp_stat *stat, float hessian36[36]) {
   pcgx_status rc = PCGX_OK;
   for (int it = 0; it < s->max_iteration && rc == PCGX_OK; it++) rc = pcgx_icp_session_step(s, nullptr);
   if (rc == PCGX_OK) rc = pcgx_icp_session_result(s, nullptr, trans16, stat, nullptr);
   if (rc == PCGX_OK && hessian36) rc = pcgx_icp_session_hessian(s, nullptr, hessian36);
   pcgx_icp_session_free(s);
+  return rc;
+}
+
+extern "C" pcgx_status pcgx_icp_gicp_fit(const pcgx_kdtree *base, const float *base_cov6, const float *target,
+                                         const float *target_cov6, int64_t nt, const pcgx_icp_params *params,
+                                         float damping, float trans16[16], pcgx_icp_stat *stat, float hessian36[36]) {
+  PCGX_API_CALL();
+  if (!base || !params || !trans16) return fail(PCGX_E_INVALID, "pcgx_icp_gicp_fit: NULL argument");
+  pcgx_icp_session *s = nullptr;
+  PCGX_TRY(pcgx_icp_gicp_session_create(base, base_cov6, target, target_cov6, nt, 0, params, damping, nullptr, &s));
+  return run_gauss_newton_fit(s, trans16, stat, hessian36);
+}
+
+extern "C" pcgx_status pcgx_icp_gicp_fit_knn(const pcgx_kdtree *base, const float *target, int64_t nt, int32_t k,
+                                             float cov_max_range, float epsilon, const pcgx_icp_params *params,
+                                             float damping, float trans16[16], pcgx_icp_stat *stat,
+                                             float hessian36[36]) {
+  PCGX_API_CALL();
+  if (!base || !params || !trans16 || nt < 0 || (nt > 0 && !target))
+    return fail(PCGX_E_INVALID, "pcgx_icp_gicp_fit_knn: bad argument");
+  if (nt == 0) return fail(PCGX_E_NOT_ENOUGH_PAIRS, "not enough correspondence pairs (the target is empty)");
+  PCGX_TRY(ensure_init());
+  hipStream_t st = ctx().stream;
+  pcgx_kdtree *tt = nullptr;
+  float *d_t = nullptr, *d_bc = nullptr, *d_tc = nullptr;
+  pcgx_icp_session *s = nullptr;
+  const int64_t nb = base->n;
+  auto run = [&]() -> pcgx_status {
+    PCGX_TRY(pcgx_kdtree_build(target, nt, 12, 0, &tt));
+    PCGX_HIP_TRY(dev_cache_alloc((void **)&d_t, (size_t)nt * 12));
+    PCGX_HIP_TRY(dev_cache_alloc((void **)&d_bc, (size_t)(nb ? nb : 1) * 24));
+    PCGX_HIP_TRY(dev_cache_alloc((void **)&d_tc, (size_t)nt * 24));
+    PCGX_TRY(staged_upload(d_t, target, (size_t)nt * 12, st));
+    PCGX_TRY(pcgx_kdtree_covariances_dev(base, nullptr, nb, k, cov_max_range, PCGX_COV_PLANE, epsilon, nullptr, d_bc,
+                                         nullptr, nullptr, st));
+    PCGX_TRY(pcgx_kdtree_covariances_dev(tt, nullptr, nt, k, cov_max_range, PCGX_COV_PLANE, epsilon, nullptr, d_tc,
+                                         nullptr, nullptr, st));
+    return pcgx_icp_gicp_session_create(base, d_bc, d_t, d_tc, nt, 1, params, damping, nullptr, &s);
+  };
+  pcgx_status rc = run();
+  if (rc == PCGX_OK) rc = run_gauss_newton_fit(s, trans16, stat, hessian36);  // (frees the session behind its streams' work)
+  else (void)hipStreamSynchronize(st);
+  dev_cache_free(d_t);
+  dev_cache_free(d_bc);
+  dev_cache_free(d_tc);
+  if (tt) pcgx_kdtree_free(tt);
   return rc;
 }
 

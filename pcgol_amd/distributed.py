@@ -165,12 +165,14 @@ class ShardedIcp:
 
     def __init__(self, base_tree, target_tile, MaxDist, MinPairs=0, Weight=None, Threshold=None,
                  MaxIteration=0, group=None, force_exchange=False, BaseNormals=None, Damping=0.0, comm=None,
-                 SumsMode=None):
+                 SumsMode=None, BaseCov=None, TargetCov=None):
         """SumsMode: None = float64 sums wherever there is an exchange (one all-reduce per iteration), the reference's sums
         on one rank; icp.SumsReference with comm=...: the reference's sums over the ranks' tiles one after the other
         (the library's default for a sharded Fit: bit-identical to the Fit of the concatenated target).
         BaseNormals: point-to-plane / Gauss-Newton extension; the exchange is then the all-reduce
         of 30 doubles (sum r^2, J^T r, upper triangle of J^T J, sum w, pairs) instead of 10.
+        BaseCov / TargetCov: the Generalized ICP extension, the same 30-double exchange; TargetCov holds this tile's
+        covariances, computed over the WHOLE target before it was cut into tiles (include/pcgx.h, "Generalized ICP").
         comm: a Comm -- the exchange then runs inside libpcgx.so (pcgx_icp_session_step_sharded: what
         a Go host calls); without it the all-reduce is torch.distributed's on the sums tensor."""
         import torch
@@ -185,7 +187,8 @@ class ShardedIcp:
         # the partial sums and the update kernel after RCCL.  (torch's default stream has
         # handle 0, which the C ABI reads as "use the library's stream": never use it here.)
         self.stream = torch.cuda.Stream()
-        self.sums = torch.zeros(30 if BaseNormals is not None else 10, dtype=torch.float64, device="cuda")
+        gauss_newton = BaseNormals is not None or BaseCov is not None or TargetCov is not None  # (30 sums)
+        self.sums = torch.zeros(30 if gauss_newton else 10, dtype=torch.float64, device="cuda")
         torch.cuda.current_stream().synchronize()
         import torch.distributed as dist
         self.world = dist.get_world_size(group) if dist.is_initialized() else 1
@@ -197,6 +200,7 @@ class ShardedIcp:
         sharded = self.exchange or (comm is not None and comm.world > 1)
         self.sess = _icp.IcpSession(base_tree, target_tile, MaxDist, MinPairs, Weight, Threshold, MaxIteration,
                                     d_sums10=self.sums.data_ptr(), BaseNormals=BaseNormals, Damping=Damping,
+                                    BaseCov=BaseCov, TargetCov=TargetCov,
                                     SumsMode=SumsMode if SumsMode is not None else
                                     (_icp.SumsF64Tree if sharded else _icp.SumsReference))
         self.max_iteration = self.sess.max_iteration

@@ -12,6 +12,8 @@
 //   pcgx::sac::SAC          <- pc/sac.SAC over NewVoxelGridSurfaceModel (the plane model of a BucketVoxelGrid)
 //   pcgx::PointToPlaneICP   <- (extension, no counterpart in the reference) the same Fit shape with
 //                              the point-to-plane evaluator / Gauss-Newton updater, HasHessian() == true
+//   pcgx::GeneralizedICP    <- (extension, no counterpart in the reference) Generalized ICP over the k-NN
+//                              covariances of both clouds (KDTree::Covariances), the same Fit shape
 //   pcgx::StatisticalOutlierRemoval <- (extension, no counterpart) a filter.Filter on k-nearest distances
 //   pcgx::Comm              <- (no counterpart: the reference is one process) the exchange of the
 //                              several-GPU paths: PointToPointICP::FitSharded, VoxelGrid::FilterSharded
@@ -469,6 +471,62 @@ class PointToPlaneICP {
     ps.Evaluated = st.evaluated;
     ps.NumIteration = st.num_iteration;
     return {t, ps};
+  }
+};
+
+// Extension (no counterpart in the reference; include/pcgx.h "Generalized ICP"): the Fit loop with the Generalized ICP
+// evaluator -- r = p - b weighed by (C_b + R C_t R^T)^-1, the consumer of KDTree::Covariances -- and the Gauss-Newton
+// updater.  Pairs whose covariances cannot be inverted are dropped and are not counted as pairs.
+class GeneralizedICP {
+ public:
+  float MaxDist = 0.0f;
+  int MinPairs = 0;
+  std::array<float, 6> Threshold{};
+  int MaxIteration = 0;
+  float Damping = 0.0f;
+  bool HasGradient() const { return true; }
+  bool HasHessian() const { return true; }
+  // baseCov: xx, xy, xz, yy, yz, zz per base point in the tree's id order; targetCov: per target point, in the target's
+  // own frame (KDTree::Covariances(k).cov of a tree over each cloud).
+  std::pair<Mat4, PlaneStat> Fit(const KDTree &base, const std::vector<std::array<float, 6>> &baseCov,
+                                 const std::vector<Vec3> &target,
+                                 const std::vector<std::array<float, 6>> &targetCov) const {
+    if ((int64_t)baseCov.size() != base.Len()) throw Error(PCGX_E_INVALID, "one covariance per base point is required");
+    if (targetCov.size() != target.size()) throw Error(PCGX_E_INVALID, "one covariance per target point is required");
+    const pcgx_icp_params p = params();
+    Mat4 t;
+    PlaneStat ps{};
+    pcgx_icp_stat st{};
+    check(pcgx_icp_gicp_fit(base.handle(), baseCov.empty() ? nullptr : baseCov[0].data(),
+                            target.empty() ? nullptr : target[0].data(), targetCov.empty() ? nullptr : targetCov[0].data(),
+                            (int64_t)target.size(), &p, Damping, t.data(), &st, ps.Hessian.data()));
+    ps.Evaluated = st.evaluated;
+    ps.NumIteration = st.num_iteration;
+    return {t, ps};
+  }
+  // The one call: both clouds' PLANE covariances from their k nearest neighbours, on the device, then the Fit.
+  std::pair<Mat4, PlaneStat> FitKNN(const KDTree &base, const std::vector<Vec3> &target, int32_t k = 20,
+                                    float epsilon = 1e-3f,
+                                    float covMaxRange = std::numeric_limits<float>::infinity()) const {
+    const pcgx_icp_params p = params();
+    Mat4 t;
+    PlaneStat ps{};
+    pcgx_icp_stat st{};
+    check(pcgx_icp_gicp_fit_knn(base.handle(), target.empty() ? nullptr : target[0].data(), (int64_t)target.size(), k,
+                                covMaxRange, epsilon, &p, Damping, t.data(), &st, ps.Hessian.data()));
+    ps.Evaluated = st.evaluated;
+    ps.NumIteration = st.num_iteration;
+    return {t, ps};
+  }
+
+ private:
+  pcgx_icp_params params() const {
+    pcgx_icp_params p{};
+    p.max_dist = MaxDist;
+    p.min_pairs = MinPairs;
+    std::memcpy(p.threshold, Threshold.data(), sizeof p.threshold);
+    p.max_iteration = MaxIteration;
+    return p;
   }
 };
 

@@ -213,17 +213,23 @@ class IcpSession:
 
     def __init__(self, base, target, MaxDist, MinPairs=0, Weight=None, Threshold=None, MaxIteration=0,
                  d_sums10=0, target_on_device=False, nt=None, BaseNormals=None, Damping=0.0, WeightFn=None,
-                 SumsMode=SumsReference):
+                 SumsMode=SumsReference, BaseCov=None, TargetCov=None):
         """BaseNormals (unit normals per base point, id order; a device address or a tensor when
         target_on_device, e.g. KDTree.NormalsDev's output) selects the point-to-plane / Gauss-Newton extension: the exchange
         vector then has 30 doubles (d_sums10 must point to 30).  SumsMode: PCGX_SUMS_* (default: the
-        reference's sequential float32 sums; a session stepped through an exchange forms float64 sums)."""
+        reference's sequential float32 sums; a session stepped through an exchange forms float64 sums).
+        BaseCov / TargetCov (xx, xy, xz, yy, yz, zz per base id / per target, e.g. KDTree.Covariances' output; device
+        addresses or tensors when target_on_device) select the Generalized ICP extension instead: 30 doubles as well,
+        dropped() counts the pairs whose covariances could not be inverted (include/pcgx.h, "Generalized ICP")."""
         w = np.zeros(6, np.float32) if Weight is None else Weight
         th = np.zeros(6, np.float32) if Threshold is None else Threshold
         self.params = _params(MaxDist, base.MinDistSq, MinPairs, w, th, MaxIteration, WeightFn, SumsMode)
         self.max_iteration = MaxIteration or 20
         self.base = base
-        self.plane = BaseNormals is not None
+        self.gicp = BaseCov is not None or TargetCov is not None
+        if self.gicp and BaseNormals is not None:
+            raise ValueError("BaseNormals (point-to-plane) and BaseCov / TargetCov (GICP) select different sessions")
+        self.plane = BaseNormals is not None or self.gicp  # (30 sums, a Hessian)
         self.n_sums = 30 if self.plane else 10
         if target_on_device:
             tptr, n = L.ptr(int(target)), int(nt)
@@ -232,7 +238,22 @@ class IcpSession:
             tptr, n = L.ptr(self._t), len(self._t)
         h = C.c_void_p()
         sums = L.ptr(int(d_sums10)) if d_sums10 else None
-        if self.plane:
+        if self.gicp:
+            if target_on_device:
+                # (device buffers are held here: session creation reads them asynchronously)
+                self._c = (BaseCov, TargetCov)
+                bptr, cptr = (None if c is None else L.ptr(int(c.data_ptr()) if hasattr(c, "data_ptr") else int(c))
+                              for c in self._c)
+            else:
+                self._c = tuple(None if c is None else L.f32c(c).reshape(-1, 6) for c in (BaseCov, TargetCov))
+                if self._c[0] is not None and len(self._c[0]) != base.Len():
+                    raise ValueError("BaseCov must hold one covariance per base point")
+                if self._c[1] is not None and len(self._c[1]) != n:
+                    raise ValueError("TargetCov must hold one covariance per target point")
+                bptr, cptr = (None if c is None else L.ptr(c) for c in self._c)
+            L.check(L.lib().pcgx_icp_gicp_session_create(base._h, bptr, tptr, cptr, n, 1 if target_on_device else 0,
+                                                         C.byref(self.params), float(Damping), sums, C.byref(h)))
+        elif self.plane:
             if target_on_device:
                 # (a device buffer: an address, or an object with data_ptr() -- held here, because session
                 # creation reads the normals asynchronously, after this call has returned)
@@ -290,6 +311,12 @@ class IcpSession:
         L.check(L.lib().pcgx_icp_session_read_sums_n(self._h, L.ptr(out), self.n_sums,
                                                      L.ptr(stream) if stream else None))
         return out
+
+    def dropped(self, stream=0):
+        """GICP sessions: the pairs the last evaluation dropped because S = C_b + R C_t R^T was not positive definite."""
+        n = C.c_int64()
+        L.check(L.lib().pcgx_icp_gicp_session_dropped(self._h, L.ptr(stream) if stream else None, C.byref(n)))
+        return n.value
 
     def hessian(self, stream=0):
         out = np.empty(36, np.float32)
@@ -428,3 +455,99 @@ class PointToPlaneICP:
         stat = Stat(st)
         stat.Evaluated.Hessian = h
         return trans, stat
+
+
+# ---------------------------------------------------------------------------
+# Generalized ICP extension (include/pcgx.h "Generalized ICP").  NOT in the reference: the consumer of
+# KDTree.Covariances, behind the same Evaluator / Updater / Fit shapes as the point-to-plane extension.
+
+class GeneralizedICPEvaluator:
+    """Evaluator of Generalized ICP (Segal, Haehnel, Thrun 2009): residual r = p - b weighed by
+    M = (C_b + R C_t R^T)^-1.  BaseCov: (n, 6) xx, xy, xz, yy, yz, zz per base point in the tree's id order;
+    TargetCov: the same per target point, in the target's own frame (KDTree.Covariances' output for both)."""
+
+    def __init__(self, Corresponder, BaseCov, TargetCov, MinPairs=0):
+        if not isinstance(Corresponder, NearestPointCorresponder):
+            raise TypeError("the GPU evaluator fuses NearestPointCorresponder")
+        self.Corresponder = Corresponder
+        self.BaseCov = L.f32c(BaseCov).reshape(-1, 6)
+        self.TargetCov = L.f32c(TargetCov).reshape(-1, 6)
+        self.MinPairs = int(MinPairs)
+
+    def HasGradient(self):
+        return True
+
+    def HasHessian(self):
+        return True
+
+    def Sums(self, base, target, with_dropped=False):
+        """The 30 float64 sums of one evaluation (what N ranks all-reduce); with_dropped: (sums, pairs dropped)."""
+        s = IcpSession(base, target, self.Corresponder.MaxDist, self.MinPairs, BaseCov=self.BaseCov,
+                       TargetCov=self.TargetCov)
+        try:
+            s.partials()
+            sums = s.read_sums()
+            return (sums, s.dropped()) if with_dropped else sums
+        finally:
+            s.close()
+
+    def Evaluate(self, base, target):
+        return FinishEvaluatePlane(self.Sums(base, target), self.MinPairs)  # (the plane extension's tail: the same sums)
+
+
+def _gicp_fit(call, uf, max_dist, min_pairs):
+    """One whole-Fit C call (pcgx_icp_gicp_fit / _fit_knn): call(params, damping, trans, stat, hessian) -> status."""
+    uf = uf or GaussNewtonUpdaterFactory()
+    p = _params(max_dist, 0.0, min_pairs, uf.Weight, uf.Threshold, uf.MaxIteration)
+    trans = np.zeros(16, np.float32)
+    st = L.IcpStat()
+    h = np.zeros(36, np.float32)
+    rc = call(C.byref(p), uf.Damping, L.ptr(trans), C.byref(st), L.ptr(h))
+    if rc == L.PCGX_E_NOT_ENOUGH_PAIRS:
+        e = ErrNotEnoughPairs(rc, L.last_error())
+        e.trans, e.stat = trans, Stat(st)
+        raise e
+    L.check(rc)
+    stat = Stat(st)
+    stat.Evaluated.Hessian = h
+    return trans, stat
+
+
+class GeneralizedICP:
+    """Fit loop of icp.go:23-67 with GeneralizedICPEvaluator + GaussNewtonUpdaterFactory, on the device."""
+
+    def __init__(self, Evaluator, UpdaterFactory=None):
+        if not isinstance(Evaluator, GeneralizedICPEvaluator):
+            raise TypeError("GeneralizedICP needs a GeneralizedICPEvaluator")
+        self.Evaluator = Evaluator
+        self.UpdaterFactory = UpdaterFactory
+
+    def Fit(self, base, target):
+        ev = self.Evaluator
+        target = L.f32c(target).reshape(-1, 3)
+        if len(ev.BaseCov) != base.Len():
+            raise ValueError("BaseCov must hold one covariance per base point")
+        if len(ev.TargetCov) != len(target):
+            raise ValueError("TargetCov must hold one covariance per target point")
+        return _gicp_fit(lambda p, damping, trans, st, h: L.lib().pcgx_icp_gicp_fit(
+            base._h, L.ptr(ev.BaseCov), L.ptr(target), L.ptr(ev.TargetCov), len(target), p, damping, trans, st, h),
+            self.UpdaterFactory, ev.Corresponder.MaxDist, ev.MinPairs)
+
+    @staticmethod
+    def FromKNN(MaxDist, K=20, Epsilon=1e-3, CovMaxRange=np.inf, MinPairs=0, UpdaterFactory=None):
+        """The one call: Fit(base, target) computes both clouds' PLANE covariances from their K nearest neighbours on
+        the device (pcgx_icp_gicp_fit_knn) and registers; nothing but the result comes back to the host."""
+        return _GeneralizedICPFromKNN(MaxDist, K, Epsilon, CovMaxRange, MinPairs, UpdaterFactory)
+
+
+class _GeneralizedICPFromKNN:
+    def __init__(self, MaxDist, K, Epsilon, CovMaxRange, MinPairs, UpdaterFactory):
+        self.MaxDist, self.K, self.Epsilon, self.CovMaxRange = float(MaxDist), int(K), float(Epsilon), float(CovMaxRange)
+        self.MinPairs = int(MinPairs)
+        self.UpdaterFactory = UpdaterFactory
+
+    def Fit(self, base, target):
+        target = L.f32c(target).reshape(-1, 3)
+        return _gicp_fit(lambda p, damping, trans, st, h: L.lib().pcgx_icp_gicp_fit_knn(
+            base._h, L.ptr(target), len(target), self.K, self.CovMaxRange, self.Epsilon, p, damping, trans, st, h),
+            self.UpdaterFactory, self.MaxDist, self.MinPairs)
