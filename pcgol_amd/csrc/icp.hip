@@ -11,6 +11,7 @@
 // The reference has no such evaluator (only the Hessian slot): no reference parity.
 #include <string.h>
 
+#include <algorithm>
 #include <array>
 #include <chrono>
 #include <condition_variable>
@@ -830,7 +831,17 @@ static int icp_grid(int64_t nt, const TreeView &tv) {
 
 // Loop state of a fresh Fit (icp.go:47): identity transform, counters zero.  On the device, in
 // stream order: a reset between two Fits costs a launch, not a host synchronisation.
-__global__ void icp_reset_kernel(IcpState *__restrict__ state) {
+// ... and, behind steps that were enqueued on a speculation and never looked at, what they may have left in the walk
+// lists and in the strict sums' counters and arrival bits (IcpResetZero: up to three ranges of 32-bit words, zeroed by
+// all the launch's threads) -- one launch where a kernel and three fills were four dependent operations of ~4 us each.
+struct IcpResetZero {
+  uint32_t *p[3] = {nullptr, nullptr, nullptr};
+  uint32_t words[3] = {0u, 0u, 0u};
+};
+__global__ void icp_reset_kernel(IcpState *__restrict__ state, IcpResetZero z) {
+#pragma unroll
+  for (int r = 0; r < 3; r++)
+    for (uint32_t i = blockIdx.x * blockDim.x + threadIdx.x; i < z.words[r]; i += gridDim.x * blockDim.x) z.p[r][i] = 0u;
   if (threadIdx.x != 0 || blockIdx.x != 0) return;
   IcpState h;
   memset(&h, 0, sizeof h);
@@ -854,14 +865,28 @@ static pcgx_status general_prepare(pcgx_icp_session *s, hipStream_t st) {
 }
 
 static pcgx_status reset_state(pcgx_icp_session *s, hipStream_t st) {
-  hipLaunchKernelGGL(icp_reset_kernel, dim3(1), dim3(64), 0, st, s->d_state);
-  PCGX_HIP_TRY(hipGetLastError());
-  s->host_iter = 0;
+  IcpResetZero z;
+  size_t zero_words = 0;
   if (s->spec_pending) {  // (steps enqueued without the leftover walk and never looked at: whatever they left in the lists)
     s->spec_pending = false;
-    if (s->d_walk_count) PCGX_HIP_TRY(hipMemsetAsync(s->d_walk_count, 0, (size_t)s->grid * sizeof(uint32_t), st));
-    PCGX_TRY(strict_reset(s->strict_buf, st));  // (and a certified summary launch that met `done` 2 midway: its slot counters)
+    void *ptr[2];
+    size_t bytes[2];
+    strict_reset_ranges(s->strict_buf, ptr, bytes);  // (and a certified summary launch that met `done` 2 midway: its slot counters)
+    if (s->d_walk_count) {
+      z.p[0] = s->d_walk_count;
+      z.words[0] = (uint32_t)s->grid;
+    }
+    for (int r = 0; r < 2; r++) {
+      z.p[1 + r] = (uint32_t *)ptr[r];
+      z.words[1 + r] = (uint32_t)(bytes[r] / sizeof(uint32_t));
+    }
+    for (int r = 0; r < 3; r++) zero_words += z.words[r];
   }
+  // (a few workgroups for the few thousand words; one wave where there is only the loop state to write)
+  const unsigned blocks = zero_words ? (unsigned)std::min<size_t>((zero_words + 1023) / 1024, 64) : 1u;
+  hipLaunchKernelGGL(icp_reset_kernel, dim3(blocks), dim3(zero_words ? 256 : 64), 0, st, s->d_state, z);
+  PCGX_HIP_TRY(hipGetLastError());
+  s->host_iter = 0;
   if (s->shard_failed || s->steps_sharded > 0) {  // (a sharded Fit may have ended inside a launch: its counters)
     PCGX_TRY(strict_reset(s->strict_buf, st));
     s->shard_failed = false;

@@ -390,9 +390,13 @@ __device__ __forceinline__ uint32_t wave_incl_scan_u32(uint32_t v) {
 }
 // Evaluate tail (evaluator.go:92-105,156-186) + Update (updater.go:44-71) + the loop
 // bookkeeping of Fit (icp.go:49-60); one thread.
+// pose_in / count_in (strict_chain_kernel): the loop state as the launch found it -- trans[16], {iter, num_iteration} --
+// fetched in the launch's prologue: nothing else writes these words while the launch runs, and the update lane, the
+// last thing a step waits for, then starts from LDS instead of a round trip to memory.
 __device__ __forceinline__ void icp_update_step(IcpState *__restrict__ state, const double *__restrict__ sums10,
-                                                const IcpKernelParams &kp) {
-  state->num_iteration += 1;
+                                                const IcpKernelParams &kp, const float *pose_in = nullptr,
+                                                const int32_t *count_in = nullptr) {
+  state->num_iteration = (count_in ? count_in[1] : state->num_iteration) + 1;
   const int64_t npairs = (int64_t)sums10[S_PAIRS];
   if (npairs < (int64_t)kp.min_pairs) {
     state->ev.num_pairs = npairs;
@@ -404,8 +408,8 @@ __device__ __forceinline__ void icp_update_step(IcpState *__restrict__ state, co
   finish_evaluate(sums10, ev);
   state->ev = ev;
   Mat4 t;
-  for (int i = 0; i < 16; i++) t.m[i] = state->trans[i];
-  int32_t it = state->iter;
+  for (int i = 0; i < 16; i++) t.m[i] = pose_in ? pose_in[i] : state->trans[i];
+  int32_t it = count_in ? count_in[0] : state->iter;
   const bool converged = gradient_descent_update(kp.upd, it, ev.gradient, t);
   for (int i = 0; i < 16; i++) state->trans[i] = t.m[i];
   state->iter = it;
@@ -455,6 +459,7 @@ pcgx_status strict_enqueue_ring(StrictBuffers *b, const float4 *match, const uin
                                 const IcpKernelParams &kp, const RingView &ring, bool local_failed, bool first_iter, hipStream_t st);
 void ring_abort_from_host(const RingView &ring, uint32_t reason);
 pcgx_status strict_reset(StrictBuffers *b, hipStream_t st);
+void strict_reset_ranges(StrictBuffers *b, void *ptr[2], size_t bytes[2]);  // the two ranges strict_reset zeroes (multiples of 4 bytes)
 // icp_small.hip: a Fit's iterations in ONE persistent launch (small clouds: the tree's inner levels in LDS)
 bool small_fit_eligible(const TreeView &tv, int64_t nt, bool many_ties);
 size_t small_fit_sync_bytes();

@@ -433,70 +433,153 @@ enum { JOB_CROSSING = 1, JOB_NOWINDOW = 2 };
 // guesses depend on it.  No rank waits for anything that depends on ANOTHER rank's wait: the totals leave a rank
 // without row_base in them, so the ranks' launches do not chain up.
 constexpr long long kExchangeTicks = 200000;  // s_memrealtime runs at 100 MHz
-// kCertify's searches (strict_sum_kernel): the tile's targets whose certificate did not hold, a lane each.  What
-// icp_grid_kernel does for such a target, with the same operands: the bound is the DistSq to last iteration's partner
-// (+inf before the first one), the new pair goes to both orders and its partner's certificate along (session order:
-// what a later grid pass reads; caller order: in w, what the next certified step reads).  The pair's terms replace the
-// target's (-0.0f, no pair) in the staged tile.
-__device__ __forceinline__ void certified_search(const CertifiedTerms &C, const TermSrc &S, const IcpState *state, const StrictWork &W,
-                                                 int64_t tile, const uint16_t *list, int nl, float4 *terms /* [kStrictRows][kTile / 4] */,
-                                                 int *np_more) {
-  TermSrc S0 = S;
-  S0.project = false;  // (the targets below are moved already)
-  for (int j = threadIdx.x; j < nl; j += kSumBlock) {
-    const int q = list[j];
-    const int64_t c = tile * kTile + q;
-    float x = W.xyz_caller[3 * c], y = W.xyz_caller[3 * c + 1], z = W.xyz_caller[3 * c + 2];
-    float ub = __builtin_inff();
-    if (S.project) {
-      float px, py, pz;
-      mat4_transform(S.m, x, y, z, px, py, pz);
-      x = px; y = py; z = pz;
-      const float4 pm = C.match_caller[c];
-      const float dx = pm.x - x, dy = pm.y - y, dz = pm.z - z;
-      const float dm = (dx * dx + dy * dy) + dz * dz;
-      if (pm.w >= 0.0f && dm == dm) ub = dm;
+// the position of the n-th set bit (from 0) of m; n < popcount(m)
+__device__ __forceinline__ int nth_set_bit(unsigned long long m, int n) {
+  int pos = 0;
+#pragma unroll
+  for (int w = 32; w > 0; w >>= 1) {
+    const int cnt = __popcll(m & (((1ull << w) - 1ull) << pos));  // set bits in [pos, pos + w)
+    const bool up = n >= cnt;
+    n -= up ? cnt : 0;
+    pos += up ? w : 0;
+  }
+  return pos;
+}
+
+// A searched target's new records (CertifiedTerms: both orders and the partner's certificate), held in the searching
+// lane's registers until the tile's summaries are out: nothing in the launch reads them, and the certificate is a
+// gather of its own behind the search.
+struct CertifiedStore {
+  float4 best;
+  float best_d;
+  uint32_t pos;  // the target's session position
+  int32_t q;     // its index in the tile, bit 16: the partner has a certificate to fetch; < 0: nothing held
+};
+__device__ __forceinline__ void certified_store_flush(const CertifiedTerms &C, int64_t tile, CertifiedStore &D) {
+  if (D.q < 0) return;
+  const bool found = __float_as_int(D.best.w) >= 0;
+  const float cert = (D.q & 0x10000) ? C.grid.cert[__float_as_uint(D.best.w)] : 0.0f;
+  const int64_t c = tile * kTile + (D.q & 0xffff);
+  C.match[D.pos] = make_float4(D.best.x, D.best.y, D.best.z, found ? D.best_d : -1.0f);
+  C.match_cert[D.pos] = cert;
+  C.match_caller[c] = make_float4(D.best.x, D.best.y, D.best.z, found ? cert : -1.0f);
+  D.q = -1;
+}
+
+// kCertify's searches (strict_sum_kernel, phase 1): the targets whose certificate did not hold, wave by wave and out
+// of registers.  A wave numbers its failing (lane, slot) items -- a ballot per slot, slot by slot and lane by lane --
+// and searches them in rounds of 64, an item a lane: the searching lane takes the moved target and the bound from the
+// owner lane by shuffles, runs icp_grid_kernel's grid_nearest call with the same operands (the bound is the DistSq to
+// last iteration's partner, +inf before the first one: the same answer), and hands the new partner back the same way;
+// the owner's ordinary pair_terms then forms the terms and counts the pair (w = the DistSq; -1.0f: no pair).  The new
+// pair's records are left in D for certified_store_flush.  A search the grid cannot certify (GRID_WALK) leaves the
+// target's records as they are and sets `done` 2: the step is enqueued again with the walk (icp.hip, settle).
+// Returns the wave's items (the caller counts them in dbg[59], once per workgroup and behind everything else: an
+// atomic per wave on that one word, in front of the searches' loads, was served one after the other -- 30 us of a
+// launch in which every wave had something to search).
+// While a round's searches run, the lanes' own quads (pairs, targets) wait in `park`: the thread's nine slots of the
+// staged tile, which nobody has written yet -- next to grid_nearest's registers they do not fit the 128 of a wave.
+__device__ __forceinline__ int certified_wave_search(const CertifiedTerms &C, const IcpState *state, const StrictWork &W, int64_t tile,
+                                                      int lane, int wave, const bool (&fail)[4], float (&mx)[4], float (&my)[4],
+                                                      float (&mz)[4], const float (&ub)[4], float4 (&bp)[4], float4 *park,
+                                                      CertifiedStore &D) {
+  constexpr int kStride = kTile / 4;  // from a row of the staged tile to the next
+  unsigned long long m[4];
+  int base[5];
+  base[0] = 0;
+#pragma unroll
+  for (int c = 0; c < 4; c++) {
+    m[c] = __ballot(fail[c]);
+    base[c + 1] = base[c] + __popcll(m[c]);
+  }
+  const int n = base[4];  // uniform
+  if (n == 0) return 0;
+#pragma unroll 1
+  for (int r0 = 0; r0 < n; r0 += kLanes) {  // uniform
+    certified_store_flush(C, tile, D);  // (the round before this one: a wave with more than 64 items)
+    const bool on = r0 + lane < n;
+    const int k = on ? r0 + lane : r0;  // (a lane without an item goes through item r0's shuffles)
+    const int c = (k >= base[1] ? 1 : 0) + (k >= base[2] ? 1 : 0) + (k >= base[3] ? 1 : 0);
+    const unsigned long long mc = c == 0 ? m[0] : (c == 1 ? m[1] : (c == 2 ? m[2] : m[3]));
+    const int bc = c == 0 ? base[0] : (c == 1 ? base[1] : (c == 2 ? base[2] : base[3]));
+    const int owner = nth_set_bit(mc, k - bc);
+    float x = 0.0f, y = 0.0f, z = 0.0f, u = 0.0f;
+#pragma unroll
+    for (int cc = 0; cc < 4; cc++) {
+      const float gx = __shfl(mx[cc], owner), gy = __shfl(my[cc], owner), gz = __shfl(mz[cc], owner), gu = __shfl(ub[cc], owner);
+      x = c == cc ? gx : x;
+      y = c == cc ? gy : y;
+      z = c == cc ? gz : z;
+      u = c == cc ? gu : u;
     }
+#pragma unroll
+    for (int cc = 0; cc < 4; cc++) park[cc * kStride] = bp[cc];
+    park[4 * kStride] = make_float4(mx[0], mx[1], mx[2], mx[3]);
+    park[5 * kStride] = make_float4(my[0], my[1], my[2], my[3]);
+    park[6 * kStride] = make_float4(mz[0], mz[1], mz[2], mz[3]);
     float4 best = make_float4(0.0f, 0.0f, 0.0f, __int_as_float(-1));
     float best_d = C.max_dist_sq;
-    GridVerdict v = grid_nearest(C.grid, x, y, z, C.max_dist_sq, ub, best, best_d);
-    if (C.test_force_grid_walk && c % C.test_force_grid_walk == 0) v = GRID_WALK;  // (tests)
-    if (v == GRID_WALK) {  // the records stay as they are; the step is enqueued again with the walk (icp.hip, settle)
-      if (atomicCAS(&const_cast<IcpState *>(state)->done, 0, 2) == 0) atomicAdd(&W.dbg[47], 1ull << 32);
-      continue;
+    float w_new = -1.0f;  // what the owner's pair carries in w
+    // (a lane or two of one wave run a few hundred dependent instructions while the SIMD's other waves -- this
+    // workgroup's and the CU's other one's -- form and stage terms: first in line for the issue slots (what that was
+    // measured to be worth: DESIGN 3.1))
+    __builtin_amdgcn_s_setprio(3);
+    if (on) {
+      const int q = 4 * (wave * kLanes + owner) + c;
+      const int64_t cg = tile * kTile + q;
+      const uint32_t pos = C.pos_of[cg];  // (depends on nothing: on its way while the search runs)
+      GridVerdict v = grid_nearest(C.grid, x, y, z, C.max_dist_sq, u, best, best_d);
+      if (C.test_force_grid_walk && cg % C.test_force_grid_walk == 0) v = GRID_WALK;  // (tests)
+      if (v == GRID_WALK) {
+        if (atomicCAS(&const_cast<IcpState *>(state)->done, 0, 2) == 0) atomicAdd(&W.dbg[47], 1ull << 32);
+      } else {
+        const bool found = __float_as_int(best.w) >= 0;
+        w_new = found ? best_d : -1.0f;
+        D.best = best;
+        D.best_d = best_d;
+        D.pos = pos;
+        D.q = q | ((v == GRID_FOUND && found) ? 0x10000 : 0);
+      }
     }
-    const bool found = __float_as_int(best.w) >= 0;
-    const float cert = (v == GRID_FOUND && found) ? C.grid.cert[__float_as_uint(best.w)] : 0.0f;
-    const uint32_t pos = C.pos_of[c];
-    C.match[pos] = make_float4(best.x, best.y, best.z, found ? best_d : -1.0f);
-    C.match_cert[pos] = cert;
-    C.match_caller[c] = make_float4(best.x, best.y, best.z, found ? cert : -1.0f);
-    if (found) {
-      float t[kStrictRows];
-      (void)pair_terms(S0, x, y, z, make_float4(best.x, best.y, best.z, best_d), t);
-      const int l = q / kLeaf, vq = (q % kLeaf) / 4, cc = q % 4;
+    __builtin_amdgcn_s_setprio(0);
+    float4 *back = park;  // (opaque: loads, not the registers kept through the search)
+    asm volatile("" : "+v"(back));
 #pragma unroll
-      for (int k = 0; k < kStrictRows; k++) reinterpret_cast<float *>(&terms[k * (kTile / 4) + tile_quad(l, vq)])[cc] = t[k];
-      atomicAdd(np_more, 1);
+    for (int cc = 0; cc < 4; cc++) bp[cc] = back[cc * kStride];
+    const float4 px = back[4 * kStride], py = back[5 * kStride], pz = back[6 * kStride];
+    mx[0] = px.x; mx[1] = px.y; mx[2] = px.z; mx[3] = px.w;
+    my[0] = py.x; my[1] = py.y; my[2] = py.z; my[3] = py.w;
+    mz[0] = pz.x; mz[1] = pz.y; mz[2] = pz.z; mz[3] = pz.w;
+#pragma unroll
+    for (int cc = 0; cc < 4; cc++) {
+      const int src = base[cc] + __popcll(m[cc] & ((1ull << lane) - 1ull)) - r0;  // my slot's item, as a lane of this round
+      const bool got = ((m[cc] >> lane) & 1ull) && src >= 0 && src < kLanes;
+      const int sl = got ? src : lane;
+      const float rx = __shfl(best.x, sl), ry = __shfl(best.y, sl), rz = __shfl(best.z, sl), rw = __shfl(w_new, sl);
+      if (got) bp[cc] = make_float4(rx, ry, rz, rw);
     }
   }
+  return n;
 }
 
 // kCertify (CertifiedTerms, strict_terms.h; one GPU, with kExchange): this launch is also the step's correspondence pass.
 // A target keeps last iteration's partner when the pair's DistSq is below the partner's certificate (icp_grid_kernel's
-// test, verbatim); the others -- two or so a tile from a Fit's third iteration on -- go on an LDS list, and after the
-// tile's terms are staged the workgroup's first lanes search them with icp_grid_kernel's grid_nearest call (the same
-// bound: the same answer), write the new pairs in both orders and put their terms in place.  A search the grid cannot
-// certify (GRID_WALK) sets `done` 2, as the grid pass without the walk does: the host enqueues the step again (settle()).
+// test, verbatim); the others -- two or so a tile from a Fit's third iteration on -- are searched by their own wave
+// right behind the test (certified_wave_search: icp_grid_kernel's grid_nearest call, the same bound: the same answer)
+// before the terms are formed, while the other waves form and stage theirs; the new pairs are written in both orders at
+// the kernel's end.  A search the grid cannot certify (GRID_WALK) sets `done` 2, as the grid pass without the walk
+// does: the host enqueues the step again (settle()).
 template <bool kExchange, bool kSharded = false, bool kCertify = false>
 __global__ __launch_bounds__(kSumBlock) __attribute__((amdgpu_waves_per_eu(4, 4))) void strict_sum_kernel(
     const float4 *__restrict__ match, const uint32_t *__restrict__ pos_of, const IcpState *__restrict__ state, StrictWork W,
     CertifiedTerms C = CertifiedTerms()) {
   __shared__ float4 s_terms[kStrictRows][kTile / 4];
   __shared__ int s_np[kSumWaves];
+  // kCertify: targets the waves have searched -- lane 0 of every wave writes its word in phase 1, thread 0 adds them up
+  // at the kernel's end: the barrier behind phase 1 stands between the two (a path that leaves before that barrier
+  // must not be followed by the count)
+  __shared__ int s_ns[kCertify ? kSumWaves : 1];
   __shared__ double s_tot[16];
-  __shared__ uint16_t s_list[kCertify ? kTile : 1];  // kCertify: the tile's targets (index in the tile) to search for
-  __shared__ int s_nlist, s_np_more;
   static_assert(!kSharded || kExchange, "the ring form rides on the exchange");
   static_assert(!kCertify || (kExchange && !kSharded), "the certified terms: one GPU, with the exchange");
   const int done = state->done;  // (looked at behind phase 1, whose loads it would only hold up: nothing is written before)
@@ -505,6 +588,8 @@ __global__ __launch_bounds__(kSumBlock) __attribute__((amdgpu_waves_per_eu(4, 4)
   const int NR = W.nrows;
   const long long t_0 = trace_clock(W);
   long long t_x0 = 0;
+  CertifiedStore held;  // kCertify: what this lane's search found, written out behind phase 2
+  held.q = -1;
   // the float64 prefix of this wave's row (strict_tilesum_kernel's sums): its loads fly while phase 1 runs
   double P0 = (!kExchange && wave < NR) ? tile_prefix(W.tile_sum, W.ntiles, wave, tile, lane) : 0.0;
   // ---- phase 1: the tile's terms, every thread one quad
@@ -515,15 +600,13 @@ __global__ __launch_bounds__(kSumBlock) __attribute__((amdgpu_waves_per_eu(4, 4)
     float tx[4], ty[4], tz[4];
     const int64_t i0 = tile * kTile + (int64_t)l * kLeaf + 4 * v;
     load_quad(S, i0, bp, tx, ty, tz);
-    if (kCertify) {
-      if (threadIdx.x == 0) s_nlist = s_np_more = 0;
-      __syncthreads();
-    }
     float t[4][kStrictRows];
     int np = 0;
+    if (kCertify) {
+      bool fail[4];
+      float ub[4];
 #pragma unroll
-    for (int c = 0; c < 4; c++) {
-      if (kCertify) {
+      for (int c = 0; c < 4; c++) {
         // icp_grid_kernel's test: the moved target's DistSq to last iteration's partner (pair_terms forms the same
         // floats again) below the partner's certificate, which match_caller carries in w
         float x = tx[c], y = ty[c], z = tz[c];
@@ -533,12 +616,21 @@ __global__ __launch_bounds__(kSumBlock) __attribute__((amdgpu_waves_per_eu(4, 4)
         bool kept = S.project && bp[c].w >= 0.0f && dm < bp[c].w && dm < C.max_dist_sq;
         if ((C.test_force_walk && (i0 + c) % C.test_force_walk == 0) || (C.test_force_grid_walk && (i0 + c) % C.test_force_grid_walk == 0))
           kept = false;  // (tests: searched below, and with the second knob, handed back as GRID_WALK)
-        if (!kept && i0 + c < W.nt) {
-          s_list[atomicAdd(&s_nlist, 1)] = (uint16_t)(l * kLeaf + 4 * v + c);
-          bp[c].w = -1.0f;  // (its terms: searched for below; until then none)
-        }
+        fail[c] = !kept && i0 + c < W.nt;
+        ub[c] = (S.project && bp[c].w >= 0.0f && dm == dm) ? dm : __builtin_inff();  // (the search's bound)
+        if (fail[c]) bp[c].w = -1.0f;  // (no pair unless the search below finds one)
+        tx[c] = x; ty[c] = y; tz[c] = z;  // (moved: what the search and the terms start from)
       }
-      np += pair_terms(S, tx[c], ty[c], tz[c], bp[c], t[c]) ? 1 : 0;
+      int ns = 0;
+      if (!done) ns = certified_wave_search(C, state, W, tile, lane, wave, fail, tx, ty, tz, ub, bp, &s_terms[0][tile_quad(l, v)], held);  // (done: uniform)
+      if (lane == 0) s_ns[wave] = ns;
+      TermSrc S0 = S;
+      S0.project = false;  // (the targets are moved already)
+#pragma unroll
+      for (int c = 0; c < 4; c++) np += pair_terms(S0, tx[c], ty[c], tz[c], bp[c], t[c]) ? 1 : 0;
+    } else {
+#pragma unroll
+      for (int c = 0; c < 4; c++) np += pair_terms(S, tx[c], ty[c], tz[c], bp[c], t[c]) ? 1 : 0;
     }
 #pragma unroll
     for (int k = 0; k < kStrictRows; k++) s_terms[k][tile_quad(l, v)] = make_float4(t[0][k], t[1][k], t[2][k], t[3][k]);
@@ -547,20 +639,10 @@ __global__ __launch_bounds__(kSumBlock) __attribute__((amdgpu_waves_per_eu(4, 4)
     if (lane == 0) s_np[wave] = np;
   }
   __syncthreads();
+  const long long t_p1 = trace_clock(W);
   if (done) return;  // uniform
-  if (kCertify) {
-    const int nl = s_nlist;  // uniform
-    if (nl > 0) {
-      certified_search(C, make_term_src(match, pos_of, state, W), state, W, tile, s_list, nl, &s_terms[0][0], &s_np_more);
-      __syncthreads();
-    }
-    if (threadIdx.x == 0) {
-      if (tile == 0) atomicAdd(&W.dbg[47], 1ull);  // (fused steps; replayed ones in the high word: certified_search)
-      if (nl > 0) atomicAdd(&W.dbg[59], (unsigned long long)nl);
-    }
-  }
   if (threadIdx.x == 0) {
-    int np = kCertify ? s_np_more : 0;
+    int np = 0;
     for (int w = 0; w < kSumWaves; w++) np += s_np[w];
     W.tile_pairs[tile] = (uint32_t)np;
   }
@@ -817,10 +899,21 @@ __global__ __launch_bounds__(kSumBlock) __attribute__((amdgpu_waves_per_eu(4, 4)
 #pragma unroll
     for (int v = 0; v < kLeaf / 4; v++) dst[v * kLanes + lane_here] = s_terms[row][v * kLanes + lane_here];
   }
+  if (kCertify) {
+    certified_store_flush(C, tile, held);
+    // (the counters behind everything else: wave 0's look at its own stores in the exchange would wait for them too)
+    if (threadIdx.x == 0) {
+      if (tile == 0) atomicAdd(&W.dbg[47], 1ull);  // (fused steps; replayed ones in the high word: certified_wave_search)
+      int ns = 0;
+      for (int w = 0; w < kSumWaves; w++) ns += s_ns[w];
+      if (ns > 0) atomicAdd(&W.dbg[59], (unsigned long long)ns);
+    }
+  }
   if (threadIdx.x == 0 && (W.selfcheck & 2)) {  // measurement aid (PCGX_STRICT_TRACE), plain stores only
     W.stamps[tile * 16 + 0] = (unsigned long long)t_0;
     W.stamps[tile * 16 + 1] = (unsigned long long)t_1;
     W.stamps[tile * 16 + 2] = (unsigned long long)t_x0;
+    W.stamps[tile * 16 + 3] = (unsigned long long)t_p1;
     W.stamps[tile * 16 + 5] = (unsigned long long)trace_clock(W);
   }
 }
@@ -1552,6 +1645,8 @@ __global__ __launch_bounds__(kChainBlock) void strict_chain_kernel(const float4 
   __shared__ uint32_t s_stat[8];
   __shared__ unsigned long long s_wk[8];  // PCGX_STRICT_CLOCKS: where the walker's ticks go
   __shared__ unsigned long long s_stat_ticks[2];
+  __shared__ float s_pose[16];      // the loop state as the launch finds it, for the fused update (icp_update_step):
+  __shared__ int32_t s_pose_n[2];   // trans, {iter, num_iteration}
   const int done = state->done;  // (looked at behind the first chunk's loads, which it would only hold up)
   // (rfl: "which wave" is the same in all lanes, and the compiler has to know -- or the branch between walker and
   // helpers counts as divergent, the walker's state becomes a vector register, and every apply() of the walk runs
@@ -1605,6 +1700,15 @@ __global__ __launch_bounds__(kChainBlock) void strict_chain_kernel(const float4 
       s_np_ok = 0;
     }
     if (threadIdx.x < 8) s_wk[threadIdx.x] = 0ull;
+    // (threads 0 .. 17 are wave 0, a helper: the walker is wave kWalker = kChainSegs - 1.  The two __syncthreads() of
+    // this prologue -- behind the look at `done`, and behind the list of tiles that own a slot -- stand between these
+    // stores and the update lane's reads.  Every workgroup of the launch fetches the 18 words although only the one
+    // whose walker takes the last ticket uses them: which one that is, nobody knows here.)
+    static_assert(kWalker != 0, "wave 0 fetches the loop state: it must not be the walker");
+    if (fuse_update && threadIdx.x < 18) {
+      if (threadIdx.x < 16) s_pose[threadIdx.x] = state->trans[threadIdx.x];
+      else s_pose_n[threadIdx.x - 16] = threadIdx.x == 16 ? state->iter : state->num_iteration;
+    }
     // ---- helpers: runs of equal windows, segmented scan forwards inside each wave
     TileRec R;
     R.key = -2;
@@ -2561,7 +2665,7 @@ __global__ __launch_bounds__(kChainBlock) void strict_chain_kernel(const float4 
           sums10[S_WEIGHT] = sums[S_WEIGHT];
         }
         const long long t_u0 = trace_clock(W);
-        if (fuse_update) icp_update_step(state, sums, kp);
+        if (fuse_update) icp_update_step(state, sums, kp, s_pose, s_pose_n);
         if (W.selfcheck & 2) {  // (the launch's last steps, in the line behind the rows')
           __threadfence();
           W.stamps[kStrictRows * 16 + 14] = (unsigned long long)t_u0;
@@ -3024,6 +3128,14 @@ pcgx_status strict_reset(StrictBuffers *b, hipStream_t st) {
   PCGX_HIP_TRY(hipMemsetAsync(b->counters, 0, b->counters_bytes, st));
   PCGX_HIP_TRY(hipMemsetAsync(b->w.tile_arrived, 0, b->arrived_bytes, st));
   return PCGX_OK;
+}
+
+// what strict_reset zeroes, for a caller that has a kernel of its own in front of the next Fit (icp.hip, reset_state)
+void strict_reset_ranges(StrictBuffers *b, void *ptr[2], size_t bytes[2]) {
+  ptr[0] = b ? b->counters : nullptr;
+  bytes[0] = b ? b->counters_bytes : 0;
+  ptr[1] = b ? (void *)b->w.tile_arrived : nullptr;
+  bytes[1] = b ? b->arrived_bytes : 0;
 }
 
 pcgx_status strict_read_debug(StrictBuffers *b, unsigned long long out[64], hipStream_t st) {
