@@ -326,6 +326,36 @@ func (k *KDTree) NormalsAt(q []mat.Vec3, radius float32, viewpoint mat.Vec3, min
 	return normals, curvature, counts, nil
 }
 
+// FPFH returns the Fast Point Feature Histogram of every point of the tree over its radius neighbourhood (extension: no
+// reference parity; include/pcgx.h, pcgx_kdtree_fpfh): 33 numbers per point in id order, eleven bins for each of the
+// three pair features, each feature summing to 200 where the point has valid pairs.  normals: one per point in id
+// order, e.g. what Normals returns; a zero normal takes its point out of every pair.
+func (k *KDTree) FPFH(radius float32, normals []mat.Vec3) ([][33]float32, error) {
+	runtime.LockOSThread() // the error text is thread-local on the C side: call and pcgx_last_error on one OS thread
+	defer runtime.UnlockOSThread()
+	defer runtime.KeepAlive(k) // the finalizer must not free the handle while a call is in flight
+	var ln C.int64_t
+	if err := status(C.pcgx_kdtree_len(k.t.h, &ln)); err != nil {
+		return nil, err
+	}
+	n := int(ln)
+	if len(normals) != n {
+		return nil, errors.New("pcgx: one normal per point of the tree is required")
+	}
+	fpfh := make([][33]float32, n)
+	if n == 0 {
+		return fpfh, nil
+	}
+	rc := C.pcgx_kdtree_fpfh(k.t.h, (*C.float)(unsafe.Pointer(&normals[0])), C.float(radius),
+		(*C.float)(unsafe.Pointer(&fpfh[0])), nil, nil)
+	runtime.KeepAlive(normals)
+	runtime.KeepAlive(fpfh)
+	if err := status(rc); err != nil {
+		return nil, err
+	}
+	return fpfh, nil
+}
+
 // Covariance modes of KDTree.Covariances (include/pcgx.h, pcgx_kdtree_covariances).
 const (
 	CovRaw   = int(C.PCGX_COV_RAW)   // the covariance as it is

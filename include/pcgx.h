@@ -763,6 +763,47 @@ PCGX_API pcgx_status pcgx_kdtree_normals_dev(const pcgx_kdtree *t, const float *
                                              const float viewpoint[3], int32_t min_neighbors, float *d_normals,
                                              float *d_curvature, int32_t *d_counts, void *stream);
 
+/* ------------------------------------------- FPFH descriptors (extension: no reference parity)
+ * NOT in the reference.  The Fast Point Feature Histogram (Rusu, Blodow, Beetz 2009) of every point of the tree: 33
+ * numbers per point, the input of feature-based coarse alignment, which finds the starting pose every ICP here needs.
+ * Close to PCL's and Open3D's FPFH, pinned to neither: this comment is the contract, tests/fpfh_oracle.py restates it.
+ * Queries: the tree's own points only, deleted ids included (the q == NULL convention of pcgx_kdtree_normals, _knearest
+ * and _covariances); normals[3 Len()] is in id order -- what pcgx_kdtree_normals(q == NULL) writes -- and so is every
+ * output.
+ * Neighbourhood: N(q) = the points p of the tree with DistSq(p, q) < radius^2, DistSq the reference's float32
+ * expression: exactly the set pcgx_kdtree_range_count counts on that handle (grid, forced walk, after DeletePoint).
+ * Deleted points are nobody's neighbour.
+ * Pair features of query s (normal ns) and neighbour t (normal nt), in float64 from the float32 inputs widened:
+ *   d = pt - ps, f4 = |d|, a1 = ns . d / f4, a2 = nt . d / f4;
+ *   if |a1| < |a2| the roles swap: (n1, n2, d, f3) = (nt, ns, -d, -a2), else (n1, n2, d, f3) = (ns, nt, d, a1)
+ *   (no acos: comparing the magnitudes is the same decision);
+ *   v = d x n1, v /= |v|;  w = n1 x v;  f2 = v . n2;  f1 = atan2(w . n2, n1 . n2);
+ *   eleven bins per feature: b1 = clamp(floor(11 (f1 + pi) / 2 pi), 0, 10), b2 = clamp(floor(11 (f2 + 1) / 2), 0, 10),
+ *   b3 = clamp(floor(11 (f3 + 1) / 2), 0, 10).
+ *   Normals are used as given and are expected to be unit length.  A pair is invalid and contributes nothing when the
+ *   float32 DistSq == 0 (the point itself, exact duplicates), when either normal is zero or not finite (how degenerate
+ *   points come out of pcgx_kdtree_normals), or when |v| == 0.
+ * SPFH: c_q[f][b] = the number of valid pairs of q whose feature f falls in bin b (exact 32-bit integers), m_q = the
+ *   number of valid pairs; S_q = 100 c_q / m_q, and 0 where m_q == 0.  spfh_counts (may be NULL) returns c, feature
+ *   major 3 x 11 per point; pair_counts (may be NULL) returns m.
+ * FPFH: with w_i = 1 / DistSq(i, q), the float32 DistSq widened and the quotient taken in float64,
+ *   W_f[b] = sum over i in N(q) with DistSq > 0 of w_i S_i[f][b],   T_f = sum over b of W_f[b],
+ *   F_q[f][b] = S_q[f][b] + (T_f > 0 ? 100 W_f[b] / T_f : 0), rounded to float32; fpfh[33 q + 11 f + b].
+ *   The sums are float64, in any order (every term is >= 0: the order matters far below float32).  The result is
+ *   within 2^-22 relative of the real-number value; a bin whose real-number value is 0 is exactly 0; an isolated
+ *   point gives 33 zeros.  The same input gives the same bits on every call.
+ * PCGX_E_INVALID: a radius that is not finite and > 0, NULL normals or NULL fpfh with Len() > 0, a NULL tree.
+ * Len() == 0 is PCGX_OK and does nothing.  Always computed on the device; the cost is two enumerations of every
+ * neighbourhood (pcgx_kdtree_normals' cost, twice) plus an atan2 and a 12-byte read by id per pair in the first and a
+ * 144-byte read by id per pair in the second.  144 Len() bytes of temporaries. */
+PCGX_API pcgx_status pcgx_kdtree_fpfh(const pcgx_kdtree *t, const float *normals /* [3 Len()], id order */,
+                                      float radius, float *fpfh /* [33 Len()] */,
+                                      int32_t *spfh_counts /* [33 Len()], may be NULL */,
+                                      int32_t *pair_counts /* [Len()], may be NULL */);
+/* Same, every array device resident, enqueued on `stream` (NULL: the library's); returns without waiting. */
+PCGX_API pcgx_status pcgx_kdtree_fpfh_dev(const pcgx_kdtree *t, const float *d_normals, float radius, float *d_fpfh,
+                                          int32_t *d_spfh_counts, int32_t *d_pair_counts, void *stream);
+
 /* ------------------------------------------- k nearest neighbours (extension: no reference parity)
  * NOT in the reference: pcgol's KD-tree answers Nearest (k = 1) and Range (a fixed radius).  For each query i: the k
  * points p of the tree with the smallest (DistSq(p, q[i]), id) in lexicographic order, among those with

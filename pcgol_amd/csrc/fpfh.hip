@@ -1,0 +1,300 @@
+// fpfh.hip -- Fast Point Feature Histograms (Rusu, Blodow, Beetz 2009) of a tree's own points over radius
+// neighbourhoods and caller-given normals (extension: no reference parity; include/pcgx.h, "FPFH descriptors").
+//
+// The input of feature-based coarse alignment, the step before every ICP here.  Two kernels over the enumeration that
+// Range, normals and region growing share (range_enum.h), one query per lane, the queries the tree's own points as
+// query_source lays them out, on each of the three kinds of handle (grid, forced walk, patched tree after DeletePoint):
+//   spfh_kernel  per neighbour: its normal by id, the pair's three bins (fpfh_terms.h), three 32-bit counters of the
+//                lane's column of an LDS table [34][64] (the bin index is dynamic: registers indexed by it would go to
+//                scratch; row 33 counts the valid pairs).  Writes one record per point: {c[33], m, 0, 0}, 36 uint32.
+//   fpfh_kernel  the same enumeration again; per neighbour with DistSq > 0: its record by id as nine uint4 and
+//                (1 / DistSq) / m_i times its counts into 33 float64 accumulators (constant indices: registers).  Then
+//                F = 100 c_q / m_q + 100 W / T_f per feature, rounded to float32.
+// The record keeps the COUNTS, not 100 c / m rounded to float32: the same 144 bytes, one division per neighbour
+// instead of none, and the sums are then those of the contract's real numbers to float64 rounding -- a bin nobody
+// counted is exactly 0, and the factor 100 cancels in W / T.
+// A fat row (kRangeFatRow) is the whole wave's work in both kernels, as in normals_kernel: every lane takes every 64th
+// record of the owner's row; the counts go into the owner's LDS column by LDS atomics (integers: any order gives the
+// same bits), the float64 partials are summed by shuffles.
+#include <math.h>
+#include <stdlib.h>
+
+#include "fpfh_terms.h"
+#include "knn_grid.h"
+#include "knn_xwalk.h"
+#include "range_walk.h"
+
+namespace pcgx {
+
+constexpr int kFpfhBlock = kRangeWalkBlock;  // one wave per workgroup: the walks' LDS frame stacks are [level][64]
+constexpr int kFpfhRows = kFpfhLen + 1;      // the LDS table's rows: 33 bins and the valid pairs
+constexpr int kFpfhRec = 36;                 // uint32 per record: c[33], m, 0, 0 -- nine uint4
+static_assert(kFpfhBlock == 64, "one wave: a lane's LDS column is [row][lane]");
+static_assert(kFpfhRec % 4 == 0 && kFpfhRec >= kFpfhRows, "whole uint4s");
+
+struct SpfhOut {
+  const float *normals;  // [3 n], id order
+  uint4 *rec;            // [9 n]
+  int32_t *counts;       // [33 n] or nullptr
+  int32_t *pairs;        // [n] or nullptr
+};
+
+// the pair (query s of column col, neighbour p) into the column's counters
+__device__ __forceinline__ void spfh_pair(uint32_t *cnt, const int col, const float *normals, const float4 &p,
+                                          const float sx, const float sy, const float sz, const float nx,
+                                          const float ny, const float nz) {
+  const size_t id = (size_t)__float_as_uint(p.w);
+  int b1, b2, b3;
+  if (!fpfh_terms(sx, sy, sz, nx, ny, nz, p.x, p.y, p.z, normals[3 * id], normals[3 * id + 1], normals[3 * id + 2], b1,
+                  b2, b3))
+    return;
+  atomicAdd(&cnt[b1 * kFpfhBlock + col], 1u);
+  atomicAdd(&cnt[(kFpfhBins + b2) * kFpfhBlock + col], 1u);
+  atomicAdd(&cnt[(2 * kFpfhBins + b3) * kFpfhBlock + col], 1u);
+  atomicAdd(&cnt[kFpfhLen * kFpfhBlock + col], 1u);
+}
+
+template <int kSrc>
+__global__ __launch_bounds__(kFpfhBlock) void spfh_kernel(GridView g, TreeView tv, XTreeView xv, QuerySource Q,
+                                                          float bound, SpfhOut O, int64_t guard) {
+  extern __shared__ uint32_t s_stack[];
+  __shared__ uint32_t s_cnt[kFpfhRows * kFpfhBlock];
+  const uint32_t n_tiles = (uint32_t)((Q.nq + kFpfhBlock - 1) / kFpfhBlock);
+  const int64_t pos = (int64_t)xcd_tile(blockIdx.x, n_tiles) * kFpfhBlock + threadIdx.x;
+  const int lane = (int)threadIdx.x;
+#pragma unroll
+  for (int k = 0; k < kFpfhRows; k++) s_cnt[k * kFpfhBlock + lane] = 0u;
+  // (the grid path keeps every lane of the wave to the end: the fat rows are scanned by all 64)
+  const bool live = pos < Q.nq;
+  if (kSrc != kRangeGrid && !live) return;
+  int64_t i = 0;
+  float qx = 0.0f, qy = 0.0f, qz = 0.0f, nx = 0.0f, ny = 0.0f, nz = 0.0f;
+  if (live) {
+    read_query(Q, pos, i, qx, qy, qz);
+    nx = O.normals[3 * i];
+    ny = O.normals[3 * i + 1];
+    nz = O.normals[3 * i + 2];
+  }
+  auto take = [&](const float4 &p) {
+    if (ref_dist_sq(p.x, p.y, p.z, qx, qy, qz) < bound) spfh_pair(s_cnt, lane, O.normals, p, qx, qy, qz, nx, ny, nz);
+  };
+  if constexpr (kSrc == kRangeGrid) {
+    __syncthreads();  // (one wave: the zeroes are in place before another lane's atomics land in this column)
+    grid_radius_scan(g, qx, qy, qz, bound, live, take, [&](int owner, uint32_t rf, uint32_t re, float ox, float oy, float oz) {
+      const float onx = __shfl(nx, owner), ony = __shfl(ny, owner), onz = __shfl(nz, owner);
+      for (uint32_t r = rf + (uint32_t)lane; r < re; r += 64u) {
+        const float4 p = g.pts[r];
+        if (ref_dist_sq(p.x, p.y, p.z, ox, oy, oz) < bound) spfh_pair(s_cnt, owner, O.normals, p, ox, oy, oz, onx, ony, onz);
+      }
+    });
+    __syncthreads();  // the other lanes' atomics before the owner reads its column
+    if (!live) return;
+  } else if constexpr (kSrc == kRangeWalk) {
+    range_walk_nodes<false>(tv, s_stack + threadIdx.x, kFpfhBlock, qx, qy, qz, bound, [=]() { return bound; },
+                            [&](const float4 &nd, float) {  // (range_walk_nodes reports only DistSq < bound)
+                              spfh_pair(s_cnt, lane, O.normals, nd, qx, qy, qz, nx, ny, nz);
+                            });
+  } else {
+    auto hit = [&](const float4 &nd, float) {
+      take(nd);
+      return true;
+    };
+    xwalk(xv, s_stack + threadIdx.x, kFpfhBlock, qx, qy, qz, guard, [&]() { return bound; }, hit, hit);
+  }
+  uint32_t c[kFpfhRec];
+#pragma unroll
+  for (int k = 0; k < kFpfhRec; k++) c[k] = k < kFpfhRows ? s_cnt[k * kFpfhBlock + lane] : 0u;
+#pragma unroll
+  for (int k = 0; k < kFpfhRec / 4; k++) O.rec[(kFpfhRec / 4) * i + k] = make_uint4(c[4 * k], c[4 * k + 1], c[4 * k + 2], c[4 * k + 3]);
+  if (O.counts) {
+#pragma unroll
+    for (int k = 0; k < kFpfhLen; k++) O.counts[kFpfhLen * i + k] = (int32_t)c[k];
+  }
+  if (O.pairs) O.pairs[i] = (int32_t)c[kFpfhLen];
+}
+
+// sum over the neighbours of (1 / DistSq) c_i / m_i, bin by bin
+struct FpfhAcc {
+  double a[kFpfhLen];
+
+  __device__ __forceinline__ void clear() {
+#pragma unroll
+    for (int k = 0; k < kFpfhLen; k++) a[k] = 0.0;
+  }
+  // neighbour p at float32 DistSq d of the query
+  __device__ __forceinline__ void add(const uint4 *rec, const float4 &p, const float d) {
+    if (d == 0.0f) return;  // the point itself and its duplicates
+    const uint4 *r = rec + (size_t)(kFpfhRec / 4) * (size_t)__float_as_uint(p.w);
+    uint4 q[kFpfhRec / 4];
+#pragma unroll
+    for (int k = 0; k < kFpfhRec / 4; k++) q[k] = r[k];
+    const uint32_t m = q[kFpfhLen / 4].y;  // word 33
+    if (m == 0u) return;                   // S_i = 0
+    const double wm = (1.0 / (double)d) / (double)m;
+#pragma unroll
+    for (int k = 0; k < kFpfhLen; k++) {
+      const uint4 &u = q[k / 4];
+      const uint32_t ck = k % 4 == 0 ? u.x : (k % 4 == 1 ? u.y : (k % 4 == 2 ? u.z : u.w));
+      a[k] = fma(wm, (double)ck, a[k]);
+    }
+  }
+  // the whole wave's partials into every lane (all 64 lanes must be here)
+  __device__ __forceinline__ void wave_sum() {
+#pragma unroll
+    for (int m = 1; m < 64; m <<= 1) {
+#pragma unroll
+      for (int k = 0; k < kFpfhLen; k++) a[k] += __shfl_xor(a[k], m);
+    }
+  }
+  __device__ __forceinline__ void merge(const FpfhAcc &o) {
+#pragma unroll
+    for (int k = 0; k < kFpfhLen; k++) a[k] += o.a[k];
+  }
+};
+
+template <int kSrc>
+__global__ __launch_bounds__(kFpfhBlock) void fpfh_kernel(GridView g, TreeView tv, XTreeView xv, QuerySource Q,
+                                                          float bound, const uint4 *rec, float *fpfh, int64_t guard) {
+  extern __shared__ uint32_t s_stack[];
+  const uint32_t n_tiles = (uint32_t)((Q.nq + kFpfhBlock - 1) / kFpfhBlock);
+  const int64_t pos = (int64_t)xcd_tile(blockIdx.x, n_tiles) * kFpfhBlock + threadIdx.x;
+  const bool live = pos < Q.nq;
+  if (kSrc != kRangeGrid && !live) return;
+  int64_t i = 0;
+  float qx = 0.0f, qy = 0.0f, qz = 0.0f;
+  if (live) read_query(Q, pos, i, qx, qy, qz);
+  FpfhAcc acc;
+  acc.clear();
+  auto take = [&](const float4 &p) {
+    const float d = ref_dist_sq(p.x, p.y, p.z, qx, qy, qz);
+    if (d < bound) acc.add(rec, p, d);
+  };
+  if constexpr (kSrc == kRangeGrid) {
+    const int lane = (int)(threadIdx.x & 63u);
+    grid_radius_scan(g, qx, qy, qz, bound, live, take, [&](int owner, uint32_t rf, uint32_t re, float ox, float oy, float oz) {
+      FpfhAcc part;
+      part.clear();
+      for (uint32_t r = rf + (uint32_t)lane; r < re; r += 64u) {
+        const float4 p = g.pts[r];
+        const float d = ref_dist_sq(p.x, p.y, p.z, ox, oy, oz);
+        if (d < bound) part.add(rec, p, d);
+      }
+      part.wave_sum();
+      if (lane == owner) acc.merge(part);
+    });
+    if (!live) return;
+  } else if constexpr (kSrc == kRangeWalk) {
+    range_walk_nodes<false>(tv, s_stack + threadIdx.x, kFpfhBlock, qx, qy, qz, bound, [=]() { return bound; },
+                            [&](const float4 &nd, float d) {  // (range_walk_nodes reports only DistSq < bound)
+                              acc.add(rec, nd, d);
+                            });
+  } else {
+    auto hit = [&](const float4 &nd, float) {
+      take(nd);
+      return true;
+    };
+    xwalk(xv, s_stack + threadIdx.x, kFpfhBlock, qx, qy, qz, guard, [&]() { return bound; }, hit, hit);
+  }
+  // F = S_q + 100 W / T per feature
+  const uint4 *own = rec + (size_t)(kFpfhRec / 4) * (size_t)i;
+  uint4 q[kFpfhRec / 4];
+#pragma unroll
+  for (int k = 0; k < kFpfhRec / 4; k++) q[k] = own[k];
+  const uint32_t m = q[kFpfhLen / 4].y;
+  const double sq = m ? 100.0 / (double)m : 0.0;
+#pragma unroll
+  for (int f = 0; f < 3; f++) {
+    double T = 0.0;
+#pragma unroll
+    for (int b = 0; b < kFpfhBins; b++) T += acc.a[f * kFpfhBins + b];
+    const double sc = T > 0.0 ? 100.0 / T : 0.0;
+#pragma unroll
+    for (int b = 0; b < kFpfhBins; b++) {
+      const int k = f * kFpfhBins + b;
+      const uint4 &u = q[k / 4];
+      const uint32_t ck = k % 4 == 0 ? u.x : (k % 4 == 1 ? u.y : (k % 4 == 2 ? u.z : u.w));
+      fpfh[(size_t)kFpfhLen * (size_t)i + k] = (float)((double)ck * sq + acc.a[k] * sc);
+    }
+  }
+}
+
+}  // namespace pcgx
+
+using namespace pcgx;
+
+namespace {
+
+pcgx_status fpfh_check(const char *fn, const pcgx_kdtree *t, const float *normals, float radius, const float *fpfh) {
+  if (!t) return fail(PCGX_E_INVALID, "%s: bad argument", fn);
+  if (!(radius > 0.0f) || !(radius < __builtin_inff())) return fail(PCGX_E_INVALID, "%s: radius must be finite and > 0", fn);
+  if (t->n > 0 && !normals) return fail(PCGX_E_INVALID, "%s: NULL normals", fn);
+  if (t->n > 0 && !fpfh) return fail(PCGX_E_INVALID, "%s: NULL fpfh", fn);
+  return PCGX_OK;
+}
+
+template <int kSrc>
+void fpfh_launch(const pcgx_kdtree *t, const TreeView &tv, const XTreeView &xv, const QuerySource &Q, float bound,
+                 const SpfhOut &O, float *d_fpfh, size_t stack_bytes, hipStream_t st) {
+  const dim3 grid(xcd_grid((unsigned)((Q.nq + kFpfhBlock - 1) / kFpfhBlock))), block(kFpfhBlock);
+  const int64_t guard = xwalk_guard(t->n);
+  const GridView g = kSrc == kRangeGrid ? t->grid : GridView{};
+  hipLaunchKernelGGL(spfh_kernel<kSrc>, grid, block, stack_bytes, st, g, tv, xv, Q, bound, O, guard);
+  hipLaunchKernelGGL(fpfh_kernel<kSrc>, grid, block, stack_bytes, st, g, tv, xv, Q, bound, (const uint4 *)O.rec, d_fpfh,
+                     guard);
+}
+
+// everything device resident; the SPFH records and the queries from ctx().arena
+pcgx_status fpfh_enqueue(const pcgx_kdtree *t, const float *d_normals, float radius, float *d_fpfh, int32_t *d_counts,
+                         int32_t *d_pairs, hipStream_t st) {
+  PCGX_TRY(ctx().arena.begin(st));
+  const RangeSrc src = range_source(t);  // as pcgx_kdtree_range_count takes it
+  XTreeView xv{};
+  if (src == kRangeXWalk) PCGX_TRY(xtree_view(t, &xv, st));
+  const TreeView tv = t->view();
+  QuerySource Q;
+  PCGX_TRY(query_source(t, src, nullptr, t->n, &Q, st));
+  SpfhOut O{d_normals, nullptr, d_counts, d_pairs};
+  PCGX_TRY(ctx().arena.alloc_n((size_t)t->n * (kFpfhRec / 4), &O.rec));
+  const float bound = radius * radius;
+  if (src == kRangeXWalk) fpfh_launch<kRangeXWalk>(t, tv, xv, Q, bound, O, d_fpfh, xwalk_stack_bytes(xv, kFpfhBlock), st);
+  else if (src == kRangeGrid) fpfh_launch<kRangeGrid>(t, tv, xv, Q, bound, O, d_fpfh, 0, st);
+  else fpfh_launch<kRangeWalk>(t, tv, xv, Q, bound, O, d_fpfh, walk_stack_bytes(tv, kFpfhBlock), st);
+  PCGX_HIP_TRY(hipGetLastError());
+  return PCGX_OK;
+}
+
+}  // namespace
+
+extern "C" pcgx_status pcgx_kdtree_fpfh_dev(const pcgx_kdtree *t, const float *d_normals, float radius, float *d_fpfh,
+                                            int32_t *d_spfh_counts, int32_t *d_pair_counts, void *stream) {
+  PCGX_API_LOCK();
+  PCGX_TRY(fpfh_check("pcgx_kdtree_fpfh_dev", t, d_normals, radius, d_fpfh));
+  if (t->n == 0) return PCGX_OK;
+  PCGX_TRY(ensure_init());
+  return fpfh_enqueue(t, d_normals, radius, d_fpfh, d_spfh_counts, d_pair_counts, pick_stream(stream));
+}
+
+extern "C" pcgx_status pcgx_kdtree_fpfh(const pcgx_kdtree *t, const float *normals, float radius, float *fpfh,
+                                        int32_t *spfh_counts, int32_t *pair_counts) {
+  PCGX_API_CALL();
+  PCGX_TRY(fpfh_check("pcgx_kdtree_fpfh", t, normals, radius, fpfh));
+  const int64_t n = t->n;
+  if (n == 0) return PCGX_OK;
+  PCGX_TRY(ensure_init());
+  // always on the device: the bins and the sums are the kernels', not a host restatement
+  hipStream_t st = ctx().stream;
+  Arena &ha = ctx().host_arena;
+  PCGX_TRY(ha.begin(st));
+  float *d_n = nullptr, *d_f = nullptr;
+  int32_t *d_c = nullptr, *d_m = nullptr;
+  PCGX_TRY(ha.alloc_n((size_t)n * 3, &d_n));
+  PCGX_TRY(staged_upload(d_n, normals, (size_t)n * 12, st));
+  PCGX_TRY(ha.alloc_n((size_t)n * kFpfhLen, &d_f));
+  if (spfh_counts) PCGX_TRY(ha.alloc_n((size_t)n * kFpfhLen, &d_c));
+  if (pair_counts) PCGX_TRY(ha.alloc_n((size_t)n, &d_m));
+  PCGX_TRY(pcgx_kdtree_fpfh_dev(t, d_n, radius, d_f, d_c, d_m, st));
+  PCGX_TRY(staged_download(fpfh, d_f, (size_t)n * kFpfhLen * 4, st));
+  if (spfh_counts) PCGX_TRY(staged_download(spfh_counts, d_c, (size_t)n * kFpfhLen * 4, st));
+  if (pair_counts) PCGX_TRY(staged_download(pair_counts, d_m, (size_t)n * 4, st));
+  return PCGX_OK;
+}

@@ -168,6 +168,25 @@ class KDTree {  // pc/storage/kdtree/kdtree.go:14-23
                               n ? r.normals[0].data() : nullptr, r.curvature.data(), r.counts.data()));
     return r;
   }
+  // FPFH descriptors of the tree's own points over radius neighbourhoods (extension: no reference parity;
+  // include/pcgx.h, pcgx_kdtree_fpfh).  `normals`: one per point in id order, e.g. Normals(radius).normals.  counts:
+  // the valid pairs per feature and bin (3 x 11, feature major), pairs: how many there are.  All in id order.
+  struct FPFHResult {
+    std::vector<std::array<float, 33>> fpfh;
+    std::vector<std::array<int32_t, 33>> counts;
+    std::vector<int32_t> pairs;
+  };
+  FPFHResult FPFH(float radius, const std::vector<Vec3> &normals) const {
+    const int64_t n = Len();
+    if ((int64_t)normals.size() != n) throw Error(PCGX_E_INVALID, "one normal per point of the tree is required");
+    FPFHResult r;
+    r.fpfh.resize((size_t)n);
+    r.counts.resize((size_t)n);
+    r.pairs.resize((size_t)n);
+    check(pcgx_kdtree_fpfh(h_.get(), n ? normals[0].data() : nullptr, radius, n ? r.fpfh[0].data() : nullptr,
+                           n ? r.counts[0].data() : nullptr, r.pairs.data()));
+    return r;
+  }
   // The k points with the smallest (DistSq, ID) among those with DistSq < maxRange^2, ascending (extension: no
   // reference parity; include/pcgx.h, pcgx_kdtree_knearest: ties go by ID).
   std::vector<Neighbor> KNearest(const Vec3 &p, int32_t k, float maxRange) const {

@@ -1,7 +1,7 @@
 """pc/storage/kdtree mirror: KDTree on the GPU behind the storage.Search shape
 (pc/storage/search.go:13-17): Vec3At / Len / Nearest, plus batched NearestBatch, and extensions with no
-reference counterpart: surface normals (Normals), k nearest neighbours (KNearest) and their covariances
-(Covariances)."""
+reference counterpart: surface normals (Normals), FPFH descriptors (FPFH), k nearest neighbours (KNearest) and
+their covariances (Covariances)."""
 import ctypes as C
 
 import numpy as np
@@ -172,6 +172,33 @@ class KDTree:
             self._h, L.ptr(int(d_q)) if d_q else None, int(nq), float(radius), L.ptr(vp), int(MinNeighbors),
             L.ptr(int(d_normals)), L.ptr(int(d_curvature)) if d_curvature else None,
             L.ptr(int(d_counts)) if d_counts else None, L.ptr(stream) if stream else None))
+
+    # -- extension (no reference parity): FPFH descriptors, the input of feature-based coarse alignment
+    def FPFH(self, radius, Normals):
+        """Fast Point Feature Histogram of every point of the tree over its radius neighbourhood (DistSq < radius^2,
+        Range's set) -> (fpfh (n,33) float32, counts (n,3,11) int32, pairs (n,) int32), in id order.  Normals: (n,3)
+        float32 unit normals in id order, e.g. Normals(radius)[0]; a zero or non-finite normal takes its point out of
+        every pair.  counts: the valid pairs of a point per feature and bin (the SPFH before scaling), pairs: how
+        many there are; fpfh = 100 counts / pairs + the 1 / DistSq weighted mean of the neighbours' SPFH, scaled to 100
+        per feature (include/pcgx.h, pcgx_kdtree_fpfh)."""
+        n = self.Len()
+        nrm = L.f32c(Normals).reshape(-1, 3)
+        if len(nrm) != n:
+            raise ValueError("one normal per point of the tree is required")
+        fpfh = np.empty((n, 33), np.float32)
+        counts = np.empty((n, 3, 11), np.int32)
+        pairs = np.empty(n, np.int32)
+        L.check(L.lib().pcgx_kdtree_fpfh(self._h, L.ptr(nrm), float(radius), L.ptr(fpfh), L.ptr(counts), L.ptr(pairs)))
+        return fpfh, counts, pairs
+
+    def FPFHDev(self, radius, d_normals, d_fpfh, d_counts=0, d_pairs=0, stream=0):
+        """Device-resident FPFH: raw device addresses (e.g. torch .data_ptr()); d_normals float32 [3 Len()] (what
+        NormalsDev writes for the tree's own points), d_fpfh float32 [33 Len()], d_counts int32 [33 Len()], d_pairs
+        int32 [Len()].  Enqueued on `stream`, returns without waiting."""
+        L.check(L.lib().pcgx_kdtree_fpfh_dev(
+            self._h, L.ptr(int(d_normals)), float(radius), L.ptr(int(d_fpfh)),
+            L.ptr(int(d_counts)) if d_counts else None, L.ptr(int(d_pairs)) if d_pairs else None,
+            L.ptr(stream) if stream else None))
 
     # -- extension (no reference parity): k nearest neighbours
     def KNearest(self, p, k, maxRange):
