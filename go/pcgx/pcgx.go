@@ -356,6 +356,71 @@ func (k *KDTree) FPFH(radius float32, normals []mat.Vec3) ([][33]float32, error)
 	return fpfh, nil
 }
 
+// FPFHMatch finds, for every row of a, the nearest usable row of b and the runner-up's distance (extension: no
+// reference parity; include/pcgx.h, "FPFH matching"): float32 squared distances over the 33 values, summed left to
+// right, ties to the smaller id.  ids[i] is -1 and both distances are +Inf where a's row is unusable (not finite, or
+// all zero) or b has no candidate; secondDistSq[i] is +Inf with a single candidate.  Rows as FPFH returns them.
+func FPFHMatch(a, b [][33]float32) (ids []int64, distSq, secondDistSq []float32, err error) {
+	runtime.LockOSThread() // the error text is thread-local on the C side: call and pcgx_last_error on one OS thread
+	defer runtime.UnlockOSThread()
+	na, nb := len(a), len(b)
+	ids = make([]int64, na)
+	distSq = make([]float32, na)
+	secondDistSq = make([]float32, na)
+	if na == 0 {
+		return ids, distSq, secondDistSq, nil
+	}
+	var pb *C.float
+	if nb > 0 {
+		pb = (*C.float)(unsafe.Pointer(&b[0]))
+	}
+	rc := C.pcgx_fpfh_match((*C.float)(unsafe.Pointer(&a[0])), C.int64_t(na), pb, C.int64_t(nb),
+		(*C.int64_t)(unsafe.Pointer(&ids[0])), (*C.float)(unsafe.Pointer(&distSq[0])),
+		(*C.float)(unsafe.Pointer(&secondDistSq[0])))
+	runtime.KeepAlive(a)
+	runtime.KeepAlive(b)
+	if err := status(rc); err != nil {
+		return nil, nil, nil, err
+	}
+	return ids, distSq, secondDistSq, nil
+}
+
+// FPFHCorrespondences returns the matches of a in b as {row of a, row of b}, ascending in the row of a, that pass
+// Lowe's ratio test distSq <= maxRatio^2 * secondDistSq (maxRatio in (0, 1]; 1 keeps every match) and, with mutual,
+// whose row of b matches back to the same row of a (include/pcgx.h, "FPFH matching"): what feature-based coarse
+// alignment estimates its pose from.
+func FPFHCorrespondences(a, b [][33]float32, maxRatio float32, mutual bool) ([][2]int64, error) {
+	runtime.LockOSThread()
+	defer runtime.UnlockOSThread()
+	na, nb := len(a), len(b)
+	if na == 0 {
+		return nil, nil
+	}
+	var pb *C.float
+	if nb > 0 {
+		pb = (*C.float)(unsafe.Pointer(&b[0]))
+	}
+	src := make([]int64, na)
+	dst := make([]int64, na)
+	var m C.int64_t
+	mu := C.int32_t(0)
+	if mutual {
+		mu = 1
+	}
+	rc := C.pcgx_fpfh_correspondences((*C.float)(unsafe.Pointer(&a[0])), C.int64_t(na), pb, C.int64_t(nb),
+		C.float(maxRatio*maxRatio), mu, (*C.int64_t)(unsafe.Pointer(&src[0])), (*C.int64_t)(unsafe.Pointer(&dst[0])), &m)
+	runtime.KeepAlive(a)
+	runtime.KeepAlive(b)
+	if err := status(rc); err != nil {
+		return nil, err
+	}
+	out := make([][2]int64, int(m))
+	for i := range out {
+		out[i] = [2]int64{src[i], dst[i]}
+	}
+	return out, nil
+}
+
 // Covariance modes of KDTree.Covariances (include/pcgx.h, pcgx_kdtree_covariances).
 const (
 	CovRaw   = int(C.PCGX_COV_RAW)   // the covariance as it is

@@ -804,6 +804,48 @@ PCGX_API pcgx_status pcgx_kdtree_fpfh(const pcgx_kdtree *t, const float *normals
 PCGX_API pcgx_status pcgx_kdtree_fpfh_dev(const pcgx_kdtree *t, const float *d_normals, float radius, float *d_fpfh,
                                           int32_t *d_spfh_counts, int32_t *d_pair_counts, void *stream);
 
+/* ------------------------------------------- FPFH matching (extension: no reference parity)
+ * NOT in the reference.  For every row of one descriptor array, the nearest and the second nearest row of another,
+ * brute force over all pairs, and the correspondence list made from them: what feature-based coarse alignment
+ * estimates its pose from.  This comment is the contract, tests/match_oracle.py restates it.
+ * A descriptor array is float32 [33 n], row i at 33 i: what pcgx_kdtree_fpfh writes.
+ * Usable row: all 33 values finite and at least one not zero (-0.0 is zero).  An all-zero row is how FPFH says "no
+ *   descriptor" (an isolated point, a degenerate normal).  Unusable rows are never candidates and find nothing as
+ *   queries; a caller who wants a point left out (a deleted id) zeroes its row.
+ * Distance: float32, left to right, nothing fused (the rule of DistSq):
+ *     acc = 0;  for k = 0 .. 32:  d = a[k] - b[k];  acc = acc + d * d;     D(a, b) = acc
+ *   every operation rounded to float32.  Between usable rows D is never NaN; it can be +inf, and a candidate at
+ *   D == +inf is not a match.  D(a, b) and D(b, a) have the same bits.
+ * Match: for query row i of A, over the usable rows j of B with finite D(i, j): ids[i] = the j with the smallest
+ *   (D, j) in lexicographic order (ties go to the smaller id, as in pcgx_kdtree_knearest), dist_sq[i] = that D,
+ *   second_dist_sq[i] = the D of the runner-up in the same order (another j; it may equal dist_sq[i]), +inf with one
+ *   such candidate.  With none, or an unusable query: {-1, +inf, +inf}.
+ * Correspondences: i is kept when ids[i] >= 0, and dist_sq[i] <= max_ratio_sq * second_dist_sq[i] (a float32 product:
+ *   Lowe's ratio test on squared distances, 1.0f keeps every match), and, if mutual != 0, the match of B's row ids[i]
+ *   in A is i (the same rule, roles swapped).  src_ids[] / dst_ids[] hold the kept pairs (i, ids[i]) in ascending i,
+ *   *n_pairs their number, the slots from n_pairs to na are -1.  0 < max_ratio_sq <= 1, else PCGX_E_INVALID.
+ * All four: na == 0 is PCGX_OK and writes nothing except *n_pairs = 0; nb == 0 is PCGX_OK with every query unmatched.
+ *   PCGX_E_INVALID: NULL a with na > 0, NULL b with nb > 0, NULL ids / dist_sq / src_ids / dst_ids / n_pairs with
+ *   na > 0, a negative count, more than 2^31 - 1 rows.  The same input gives the same bits on every call.  Always
+ *   computed on the device: 99 na nb float32 operations (twice that with mutual: two passes); 12 S na + 4 (na + nb)
+ *   bytes of temporaries, S the number of chunks B is split into to fill the chip (the library's choice; PCGX_MATCH_SPLIT=<n>
+ *   in the environment, read per call, forces it -- any n gives the same bits). */
+PCGX_API pcgx_status pcgx_fpfh_match(const float *a /* [33 na] */, int64_t na, const float *b /* [33 nb] */, int64_t nb,
+                                     int64_t *ids /* [na] */, float *dist_sq /* [na] */,
+                                     float *second_dist_sq /* [na], may be NULL */);
+/* Same, every array device resident (ids and counts are int32 there), enqueued on `stream` (NULL: the library's);
+ * returns without waiting. */
+PCGX_API pcgx_status pcgx_fpfh_match_dev(const float *d_a, int64_t na, const float *d_b, int64_t nb, int32_t *d_ids,
+                                         float *d_dist_sq, float *d_second_dist_sq /* may be NULL */, void *stream);
+PCGX_API pcgx_status pcgx_fpfh_correspondences(const float *a, int64_t na, const float *b, int64_t nb,
+                                               float max_ratio_sq, int32_t mutual, int64_t *src_ids /* [na] */,
+                                               int64_t *dst_ids /* [na] */, int64_t *n_pairs);
+PCGX_API pcgx_status pcgx_fpfh_correspondences_dev(const float *d_a, int64_t na, const float *d_b, int64_t nb,
+                                                   float max_ratio_sq, int32_t mutual, int32_t *d_src_ids /* [na] */,
+                                                   int32_t *d_dst_ids /* [na] */, int32_t *d_n_pairs, void *stream);
+/* Queries per workgroup of the match kernel (a wave, two queries per lane): the boundary the tests put rows across. */
+PCGX_API int32_t pcgx_fpfh_match_tile(void);
+
 /* ------------------------------------------- k nearest neighbours (extension: no reference parity)
  * NOT in the reference: pcgol's KD-tree answers Nearest (k = 1) and Range (a fixed radius).  For each query i: the k
  * points p of the tree with the smallest (DistSq(p, q[i]), id) in lexicographic order, among those with

@@ -253,6 +253,11 @@ SIGNATURES = {
     "pcgx_kdtree_normals_dev": (_i32, [_vp, _vp, _i64, _f32, _vp, _i32, _vp, _vp, _vp, _vp]),
     "pcgx_kdtree_fpfh": (_i32, [_vp, _vp, _f32, _vp, _vp, _vp]),
     "pcgx_kdtree_fpfh_dev": (_i32, [_vp, _vp, _f32, _vp, _vp, _vp, _vp]),
+    "pcgx_fpfh_match": (_i32, [_vp, _i64, _vp, _i64, _vp, _vp, _vp]),
+    "pcgx_fpfh_match_dev": (_i32, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "pcgx_fpfh_correspondences": (_i32, [_vp, _i64, _vp, _i64, _f32, _i32, _vp, _vp, _vp]),
+    "pcgx_fpfh_correspondences_dev": (_i32, [_vp, _i64, _vp, _i64, _f32, _i32, _vp, _vp, _vp, _vp]),
+    "pcgx_fpfh_match_tile": (_i32, []),
     "pcgx_kdtree_knearest": (_i32, [_vp, _vp, _i64, _i32, _f32, _vp, _vp, _vp]),
     "pcgx_kdtree_knearest_dev": (_i32, [_vp, _vp, _i64, _i32, _f32, _vp, _vp, _vp, _vp]),
     "pcgx_kdtree_covariances": (_i32, [_vp, _vp, _i64, _i32, _f32, _i32, _f32, _vp, _vp, _vp, _vp]),

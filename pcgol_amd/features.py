@@ -1,0 +1,68 @@
+"""Matching of FPFH descriptors (extension: no reference counterpart; include/pcgx.h, "FPFH matching"): for every row
+of one descriptor array the nearest and second nearest row of another, brute force on the GPU, and the correspondence
+list feature-based coarse alignment starts from.  Descriptors are (n, 33) float32, what KDTree.FPFH returns first."""
+import numpy as np
+
+from . import _lib as L
+
+LEN = 33
+
+
+def MatchTile():
+    """Queries per workgroup of the match kernel (the boundary the tests put rows across)."""
+    return int(L.lib().pcgx_fpfh_match_tile())
+
+
+def _rows(a, what):
+    a = L.f32c(a)
+    if a.ndim != 2 or a.shape[1] != LEN:
+        raise ValueError("%s: an (n, 33) array of descriptors is required" % what)
+    return a
+
+
+def Match(A, B):
+    """-> (ids (na,) int64, distSq (na,) float32, secondDistSq (na,) float32): for every row of A the usable row of B
+    at the smallest float32 squared distance (ties: the smaller id) and the runner-up's distance; -1, inf, inf where
+    there is none or the row of A is unusable (not finite, or all zero)."""
+    a, b = _rows(A, "A"), _rows(B, "B")
+    na = len(a)
+    ids = np.empty(na, np.int64)
+    d1 = np.empty(na, np.float32)
+    d2 = np.empty(na, np.float32)
+    L.check(L.lib().pcgx_fpfh_match(L.ptr(a), na, L.ptr(b), len(b), L.ptr(ids), L.ptr(d1), L.ptr(d2)))
+    return ids, d1, d2
+
+
+def Correspondences(A, B, MaxRatio=1.0, Mutual=True):
+    """-> (m, 2) int64 pairs (row of A, row of B) in ascending row of A: the matches of A in B that pass Lowe's ratio
+    test distSq <= float32(MaxRatio)^2 * secondDistSq and, with Mutual, whose row of B matches back to the same row
+    of A."""
+    a, b = _rows(A, "A"), _rows(B, "B")
+    na = len(a)
+    r = np.float32(MaxRatio)
+    src = np.empty(na, np.int64)
+    dst = np.empty(na, np.int64)
+    n = np.zeros(1, np.int64)
+    L.check(L.lib().pcgx_fpfh_correspondences(L.ptr(a), na, L.ptr(b), len(b), float(r * r), 1 if Mutual else 0,
+                                              L.ptr(src), L.ptr(dst), L.ptr(n)))
+    m = int(n[0])
+    return np.stack([src[:m], dst[:m]], axis=1)
+
+
+def MatchDev(d_a, na, d_b, nb, d_ids, d_dist_sq, d_second_dist_sq=0, stream=0):
+    """Device-resident Match: raw device addresses (e.g. torch .data_ptr()); d_a float32 [33 na], d_b float32 [33 nb],
+    d_ids int32 [na], d_dist_sq and d_second_dist_sq float32 [na].  Enqueued on `stream`, returns without waiting."""
+    L.check(L.lib().pcgx_fpfh_match_dev(
+        L.ptr(int(d_a)) if d_a else None, int(na), L.ptr(int(d_b)) if d_b else None, int(nb), L.ptr(int(d_ids)),
+        L.ptr(int(d_dist_sq)), L.ptr(int(d_second_dist_sq)) if d_second_dist_sq else None,
+        L.ptr(stream) if stream else None))
+
+
+def CorrespondencesDev(d_a, na, d_b, nb, d_src_ids, d_dst_ids, d_n_pairs, MaxRatio=1.0, Mutual=True, stream=0):
+    """Device-resident Correspondences: d_src_ids and d_dst_ids int32 [na] (-1 behind the pairs), d_n_pairs int32 [1].
+    Enqueued on `stream`, returns without waiting."""
+    r = np.float32(MaxRatio)
+    L.check(L.lib().pcgx_fpfh_correspondences_dev(
+        L.ptr(int(d_a)) if d_a else None, int(na), L.ptr(int(d_b)) if d_b else None, int(nb), float(r * r),
+        1 if Mutual else 0, L.ptr(int(d_src_ids)), L.ptr(int(d_dst_ids)), L.ptr(int(d_n_pairs)),
+        L.ptr(stream) if stream else None))

@@ -237,6 +237,39 @@ class KDTree {  // pc/storage/kdtree/kdtree.go:14-23
   std::shared_ptr<pcgx_kdtree> h_;
 };
 
+// Matching of FPFH descriptors (extension: no reference parity; include/pcgx.h, "FPFH matching").  Rows as
+// KDTree::FPFH returns them.  ids: the nearest usable row of b per row of a (-1: none), distSq its float32 squared
+// distance, secondDistSq the runner-up's (+inf: none).
+using FPFHRow = std::array<float, 33>;
+struct FPFHMatchResult {
+  std::vector<int64_t> ids;
+  std::vector<float> distSq, secondDistSq;
+};
+inline FPFHMatchResult fpfh_match(const std::vector<FPFHRow> &a, const std::vector<FPFHRow> &b) {
+  const int64_t na = (int64_t)a.size(), nb = (int64_t)b.size();
+  FPFHMatchResult r;
+  r.ids.resize((size_t)na);
+  r.distSq.resize((size_t)na);
+  r.secondDistSq.resize((size_t)na);
+  check(pcgx_fpfh_match(na ? a[0].data() : nullptr, na, nb ? b[0].data() : nullptr, nb, r.ids.data(), r.distSq.data(),
+                        r.secondDistSq.data()));
+  return r;
+}
+// The matches of a in b that pass the ratio test distSq <= maxRatio^2 secondDistSq (maxRatio in (0, 1], 1 keeps all)
+// and, with mutual, whose row of b matches back to the same row of a: {row of a, row of b}, ascending in the first.
+inline std::vector<std::array<int64_t, 2>> fpfh_correspondences(const std::vector<FPFHRow> &a,
+                                                               const std::vector<FPFHRow> &b, float maxRatio = 1.0f,
+                                                               bool mutual = true) {
+  const int64_t na = (int64_t)a.size(), nb = (int64_t)b.size();
+  std::vector<int64_t> src((size_t)na), dst((size_t)na);
+  int64_t m = 0;
+  check(pcgx_fpfh_correspondences(na ? a[0].data() : nullptr, na, nb ? b[0].data() : nullptr, nb, maxRatio * maxRatio,
+                                  mutual ? 1 : 0, src.data(), dst.data(), &m));
+  std::vector<std::array<int64_t, 2>> out((size_t)m);
+  for (size_t i = 0; i < (size_t)m; i++) out[i] = {src[i], dst[i]};
+  return out;
+}
+
 class VoxelGrid {  // pc/filter/voxelgrid/voxelgrid.go:23-33 + option.go:14-18
  public:
   Vec3 LeafSize;
