@@ -421,6 +421,66 @@ func FPFHCorrespondences(a, b [][33]float32, maxRatio float32, mutual bool) ([][
 	return out, nil
 }
 
+// PoseResult is what PoseFromCorrespondences returns: the pose (column-major, it takes src onto dst) of the best
+// hypothesis or, where Refined, the least-squares pose over its inliers; Inliers are the pairs within maxDist under it.
+type PoseResult struct {
+	Found, Refined  bool
+	Best, BestCount int64
+	Pose            [16]float32
+	Inliers         []int64
+}
+
+// PoseFromCorrespondences estimates the rigid pose most pairs agree on by sample consensus on the GPU (extension: no
+// reference parity; include/pcgx.h, "pose from correspondences"): pairs are {index into src, index into dst}, e.g. what
+// FPFHCorrespondences returns; samples holds three random 32-bit words per hypothesis, drawn by the caller (word u
+// names pair (u * m) >> 32).  edgeSimilarity in [0, 1] (0: no edge test); Found is false when no hypothesis agrees with
+// three pairs.
+func PoseFromCorrespondences(src, dst [][3]float32, pairs [][2]int64, samples [][3]uint32, maxDist, edgeSimilarity float32,
+	refine bool) (PoseResult, error) {
+	runtime.LockOSThread()
+	defer runtime.UnlockOSThread()
+	var r PoseResult
+	r.Best = -1
+	m, n := len(pairs), len(samples)
+	s := make([]int64, m+1)
+	d := make([]int64, m+1)
+	ids := make([]int64, m+1)
+	for k, p := range pairs {
+		s[k], d[k] = p[0], p[1]
+	}
+	var ps, pd *C.float
+	var pu *C.uint32_t
+	if len(src) > 0 {
+		ps = (*C.float)(unsafe.Pointer(&src[0]))
+	}
+	if len(dst) > 0 {
+		pd = (*C.float)(unsafe.Pointer(&dst[0]))
+	}
+	if n > 0 {
+		pu = (*C.uint32_t)(unsafe.Pointer(&samples[0]))
+	}
+	var found, refined C.int32_t
+	var best, bestCount, nIn C.int64_t
+	rf := C.int32_t(0)
+	if refine {
+		rf = 1
+	}
+	rc := C.pcgx_pose_from_correspondences(ps, C.int64_t(len(src)), pd, C.int64_t(len(dst)),
+		(*C.int64_t)(unsafe.Pointer(&s[0])), (*C.int64_t)(unsafe.Pointer(&d[0])), C.int64_t(m), pu, C.int64_t(n),
+		C.float(maxDist*maxDist), C.float(edgeSimilarity), rf, &found, &best, &bestCount,
+		(*C.float)(unsafe.Pointer(&r.Pose[0])), &refined, &nIn, (*C.int64_t)(unsafe.Pointer(&ids[0])), nil, nil, nil)
+	runtime.KeepAlive(src)
+	runtime.KeepAlive(dst)
+	runtime.KeepAlive(samples)
+	if err := status(rc); err != nil {
+		return PoseResult{}, err
+	}
+	r.Found, r.Refined = found != 0, refined != 0
+	r.Best, r.BestCount = int64(best), int64(bestCount)
+	r.Inliers = ids[:int(nIn)]
+	return r, nil
+}
+
 // Covariance modes of KDTree.Covariances (include/pcgx.h, pcgx_kdtree_covariances).
 const (
 	CovRaw   = int(C.PCGX_COV_RAW)   // the covariance as it is

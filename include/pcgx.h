@@ -846,6 +846,79 @@ PCGX_API pcgx_status pcgx_fpfh_correspondences_dev(const float *d_a, int64_t na,
 /* Queries per workgroup of the match kernel (a wave, two queries per lane): the boundary the tests put rows across. */
 PCGX_API int32_t pcgx_fpfh_match_tile(void);
 
+/* ------------------------------------------- pose from correspondences (extension: no reference parity)
+ * NOT in the reference.  The rigid motion (a proper rotation and a translation, no scale) that most pairs of a
+ * correspondence list agree on, by sample consensus: the starting pose every Fit here needs, from what
+ * pcgx_fpfh_correspondences returns.  As in pcgx_sac_plane_compute the caller draws every random number first; one call
+ * fits and scores all hypotheses and returns the first best.  This comment is the contract, tests/pose_oracle.py
+ * restates it.
+ * Pairs: pair k < m is (point src_ids[k] of src_xyz, point dst_ids[k] of dst_xyz); p_k and q_k are its two points.
+ * Samples: a sample is a random 32-bit word u; the pair it names is (uint64(u) * m) >> 32, computed on the device, so one
+ *   sample array serves the host form and the device form, where m is not known to the host.  Hypothesis h uses
+ *   samples[3h], [3h + 1], [3h + 2]: pairs i0, i1, i2.
+ * Hypothesis h, in this order:
+ *   status 1 (bad sample): m < 3, or two of i0, i1, i2 are equal, or one of the three pairs names an id outside
+ *     [0, ns) / [0, nd).
+ *   status 2 (degenerate): the source triangle or the target triangle is degenerate.  With e1 = x1 - x0, e2 = x2 - x0 in
+ *     float64 from the float32 points, c = e1 x e2, norms as (x x + y y) + z z: degenerate unless
+ *     |c|^2 > (1e-12 * |e1|^2) * |e2|^2 (a comparison that fails on a NaN counts as degenerate).
+ *   status 3 (edge): edge_similarity s > 0 and, for one of the edges (0,1), (0,2), (1,2), the source length ls and the
+ *     target length ld (float64, a correctly rounded sqrt) fail ls >= s * ld or ld >= s * ls.  s = 0 switches the test off.
+ *   status 0 otherwise.  Its pose is the proper rotation R and the translation t that minimise sum |R p_i + t - q_i|^2
+ *     over the three pairs, computed in float64 from the float32 inputs, each of the twelve numbers rounded once to
+ *     float32 into a column-major 4 x 4 (m[4 col + row], the layout of pcgx_mat4_transform), bottom row 0 0 0 1.
+ *     count[h] = the number of pairs k < m with both ids in range and DistSq < max_dist_sq, where
+ *     x' = pcgx_mat4_transform(pose, p_k), d = q_k - x', DistSq = (dx dx + dy dy) + dz dz: all float32, nothing fused;
+ *     given the pose's bits the count has no tolerance.  A NaN is not an inlier.
+ *   A rejected hypothesis (status != 0) has count 0 and an all-zero pose.
+ * Best: the status-0 hypothesis with the largest count, the smallest h among equals; best = -1 when there is none.
+ *   found = (that count >= 3).  pose, n_inliers and inlier_ids describe the pose that is kept (the best's, or its
+ *   refinement): the inliers' k in ascending order, -1 from n_inliers to m.  With best = -1 the pose is all zero.
+ * Refinement (refine != 0 and found): I = the best's inliers in ascending k.  The refined pose is the same minimiser over
+ *   I, from float64 moments {n, sum p, sum q, sum p q^T} taken about the first inlier's two points (small cancellation)
+ *   and summed in a fixed order without float atomics: the same input gives the same bits on every call.  The pairs are
+ *   counted again under the refined pose; it replaces the best's when its count is >= best_count (then refined = 1 and
+ *   n_inliers, inlier_ids are its own; best and best_count keep describing the hypothesis).
+ *   Too degenerate to refit (refined = 0, the hypothesis's pose is kept): fewer than three inliers, or l1 - l2 <=
+ *   1e-9 * l1, where l1 >= l2 are the two largest eigenvalues of the symmetric 4 x 4 matrix N of Horn's closed form
+ *   whose top eigenvector is the rotation (the solve has them).  In terms of the singular values s1 >= s2 >= s3 of the
+ *   centred sum p q^T and d = the sign of its determinant: l1 = s1 + s2 + d s3 and l1 - l2 = 2 (s2 + d s3), which is
+ *   zero when the inliers of either cloud lie on a line: the rotation about the line is then free.
+ * Arguments: PCGX_E_INVALID for a NULL array with a positive count, a NULL scalar output, a negative count, more than
+ *   2^31 - 1 points, pairs or hypotheses, max_dist_sq not finite or not > 0, edge_similarity outside [0, 1] or NaN, and
+ *   -- on the host path only, where the list can be read -- a pair that names an id out of range.  On the device path
+ *   such a pair is never an inlier and a hypothesis that draws it has status 1.  n_hyp == 0 or m == 0 is PCGX_OK with
+ *   found = 0, best = -1 (every status 1).  inlier_ids [m], status [n_hyp], counts [n_hyp] and poses [16 n_hyp] may be
+ *   NULL.  Always computed on the device: about 30 m n_hyp float32 operations; 32 m + 72 n_hyp bytes of temporaries at
+ *   most.  The pairs are split into S chunks to fill the chip (the library's choice; PCGX_POSE_SPLIT=<n> in the
+ *   environment, read per call, forces it -- any n gives the same bits). */
+PCGX_API pcgx_status pcgx_pose_from_correspondences(const float *src_xyz /* [3 ns] */, int64_t ns,
+                                                    const float *dst_xyz /* [3 nd] */, int64_t nd,
+                                                    const int64_t *src_ids /* [m] */, const int64_t *dst_ids /* [m] */,
+                                                    int64_t m, const uint32_t *samples /* [3 n_hyp] */, int64_t n_hyp,
+                                                    float max_dist_sq, float edge_similarity, int32_t refine,
+                                                    int32_t *found, int64_t *best, int64_t *best_count, float pose16[16],
+                                                    int32_t *refined, int64_t *n_inliers, int64_t *inlier_ids,
+                                                    int32_t *status, int64_t *counts, float *poses);
+/* Same, every array device resident, enqueued on `stream` (NULL: the library's); returns without waiting.  Ids, status
+ * and counts are int32.  The list is the first *d_n_pairs (held to [0, m_cap]) of d_src_ids / d_dst_ids [m_cap], read on
+ * the device -- pcgx_fpfh_correspondences_dev's outputs feed it with nothing read back; d_n_pairs == NULL: m_cap pairs.
+ * d_inlier_ids is [m_cap].  The scalar outputs go to d_result, PCGX_POSE_RESULT_WORDS 4-byte words: int32 found, best,
+ * best_count, refined, n_inliers, m (the list's length as used), 0, 0, then the float32 pose in words 8..23. */
+#define PCGX_POSE_RESULT_WORDS 24
+PCGX_API pcgx_status pcgx_pose_from_correspondences_dev(const float *d_src_xyz, int64_t ns, const float *d_dst_xyz,
+                                                        int64_t nd, const int32_t *d_src_ids, const int32_t *d_dst_ids,
+                                                        int64_t m_cap, const int32_t *d_n_pairs,
+                                                        const uint32_t *d_samples, int64_t n_hyp, float max_dist_sq,
+                                                        float edge_similarity, int32_t refine, void *d_result,
+                                                        int32_t *d_inlier_ids /* may be NULL */,
+                                                        int32_t *d_status /* may be NULL */,
+                                                        int32_t *d_counts /* may be NULL */,
+                                                        float *d_poses /* may be NULL */, void *stream);
+/* Hypotheses per workgroup of the count kernel (a wave, two hypotheses per lane): the boundary the tests put n_hyp
+ * across. */
+PCGX_API int32_t pcgx_pose_tile(void);
+
 /* ------------------------------------------- k nearest neighbours (extension: no reference parity)
  * NOT in the reference: pcgol's KD-tree answers Nearest (k = 1) and Range (a fixed radius).  For each query i: the k
  * points p of the tree with the smallest (DistSq(p, q[i]), id) in lexicographic order, among those with

@@ -270,6 +270,41 @@ inline std::vector<std::array<int64_t, 2>> fpfh_correspondences(const std::vecto
   return out;
 }
 
+// The rigid pose most pairs of a correspondence list agree on, by sample consensus (extension: no reference parity;
+// include/pcgx.h, "pose from correspondences").  pairs: {index into src, index into dst}, e.g. fpfh_correspondences';
+// samples: three random 32-bit words per hypothesis, drawn by the caller (word u names pair (u * m) >> 32).  pose takes
+// src onto dst: the best hypothesis's, or with refine the least-squares pose over its inliers where that keeps at least
+// as many.  inliers: the pairs within maxDist under it, ascending.
+struct PoseResult {
+  bool found = false, refined = false;
+  int64_t best = -1, bestCount = 0;
+  Mat4 pose{};
+  std::vector<int64_t> inliers;
+};
+inline PoseResult pose_from_correspondences(const std::vector<Vec3> &src, const std::vector<Vec3> &dst,
+                                            const std::vector<std::array<int64_t, 2>> &pairs,
+                                            const std::vector<std::array<uint32_t, 3>> &samples, float maxDist,
+                                            float edgeSimilarity = 0.9f, bool refine = true) {
+  const int64_t m = (int64_t)pairs.size(), n = (int64_t)samples.size();
+  std::vector<int64_t> s((size_t)m), d((size_t)m), ids((size_t)m);
+  for (size_t k = 0; k < (size_t)m; k++) {
+    s[k] = pairs[k][0];
+    d[k] = pairs[k][1];
+  }
+  PoseResult r;
+  int32_t found = 0, refined = 0;
+  int64_t nIn = 0;
+  check(pcgx_pose_from_correspondences(src.empty() ? nullptr : src[0].data(), (int64_t)src.size(),
+                                       dst.empty() ? nullptr : dst[0].data(), (int64_t)dst.size(), s.data(), d.data(), m,
+                                       n ? samples[0].data() : nullptr, n, maxDist * maxDist, edgeSimilarity,
+                                       refine ? 1 : 0, &found, &r.best, &r.bestCount, r.pose.data(), &refined, &nIn,
+                                       ids.data(), nullptr, nullptr, nullptr));
+  r.found = found != 0;
+  r.refined = refined != 0;
+  r.inliers.assign(ids.begin(), ids.begin() + nIn);
+  return r;
+}
+
 class VoxelGrid {  // pc/filter/voxelgrid/voxelgrid.go:23-33 + option.go:14-18
  public:
   Vec3 LeafSize;
