@@ -356,6 +356,69 @@ func (k *KDTree) FPFH(radius float32, normals []mat.Vec3) ([][33]float32, error)
 	return fpfh, nil
 }
 
+// LocalMaxima returns, in ascending order, the ids of the points whose score is the largest of their radius
+// neighbourhood (extension: no reference parity; include/pcgx.h, pcgx_kdtree_local_maxima).  score: one per point in id
+// order; only a score > 0 qualifies (NaN never, +Inf does), ties go to the smaller id, a deleted id is never a maximum.
+func (k *KDTree) LocalMaxima(radius float32, score []float32) ([]int64, error) {
+	runtime.LockOSThread() // the error text is thread-local on the C side: call and pcgx_last_error on one OS thread
+	defer runtime.UnlockOSThread()
+	defer runtime.KeepAlive(k) // the finalizer must not free the handle while a call is in flight
+	var ln C.int64_t
+	if err := status(C.pcgx_kdtree_len(k.t.h, &ln)); err != nil {
+		return nil, err
+	}
+	n := int(ln)
+	if len(score) != n {
+		return nil, errors.New("pcgx: one score per point of the tree is required")
+	}
+	ids := make([]int64, n)
+	if n == 0 {
+		return ids, nil
+	}
+	var m C.int64_t
+	rc := C.pcgx_kdtree_local_maxima(k.t.h, C.float(radius), (*C.float)(unsafe.Pointer(&score[0])),
+		(*C.int64_t)(unsafe.Pointer(&ids[0])), &m)
+	runtime.KeepAlive(score)
+	runtime.KeepAlive(ids)
+	if err := status(rc); err != nil {
+		return nil, err
+	}
+	return ids[:int(m)], nil
+}
+
+// ISSKeypoints returns the ISS keypoints of the tree's points (Zhong 2009, Open3D's form; extension: no reference
+// parity; include/pcgx.h, pcgx_kdtree_iss_keypoints): ids ascending, and per point in id order the eigenvalues of
+// Normals' covariance at salientRadius (ascending, zero where Normals answers "degenerate") and the saliency (the
+// smallest eigenvalue where l1 < gamma21 l2 and l0 < gamma32 l1, else 0).  The keypoints are LocalMaxima(nonMaxRadius,
+// saliency).  The usual parameters: gamma21 = gamma32 = 0.975, minNeighbors = 5.
+func (k *KDTree) ISSKeypoints(salientRadius, nonMaxRadius, gamma21, gamma32 float32, minNeighbors int) (ids []int64, eigenvalues []mat.Vec3, saliency []float32, err error) {
+	runtime.LockOSThread() // the error text is thread-local on the C side: call and pcgx_last_error on one OS thread
+	defer runtime.UnlockOSThread()
+	defer runtime.KeepAlive(k) // the finalizer must not free the handle while a call is in flight
+	var ln C.int64_t
+	if err := status(C.pcgx_kdtree_len(k.t.h, &ln)); err != nil {
+		return nil, nil, nil, err
+	}
+	n := int(ln)
+	ids = make([]int64, n)
+	eigenvalues = make([]mat.Vec3, n)
+	saliency = make([]float32, n)
+	if n == 0 {
+		return ids, eigenvalues, saliency, nil
+	}
+	var m C.int64_t
+	rc := C.pcgx_kdtree_iss_keypoints(k.t.h, C.float(salientRadius), C.float(nonMaxRadius), C.float(gamma21),
+		C.float(gamma32), C.int32_t(minNeighbors), (*C.float)(unsafe.Pointer(&eigenvalues[0])),
+		(*C.float)(unsafe.Pointer(&saliency[0])), (*C.int64_t)(unsafe.Pointer(&ids[0])), &m)
+	runtime.KeepAlive(ids)
+	runtime.KeepAlive(eigenvalues)
+	runtime.KeepAlive(saliency)
+	if err := status(rc); err != nil {
+		return nil, nil, nil, err
+	}
+	return ids[:int(m)], eigenvalues, saliency, nil
+}
+
 // FPFHMatch finds, for every row of a, the nearest usable row of b and the runner-up's distance (extension: no
 // reference parity; include/pcgx.h, "FPFH matching"): float32 squared distances over the 33 values, summed left to
 // right, ties to the smaller id.  ids[i] is -1 and both distances are +Inf where a's row is unusable (not finite, or

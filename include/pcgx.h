@@ -846,6 +846,54 @@ PCGX_API pcgx_status pcgx_fpfh_correspondences_dev(const float *d_a, int64_t na,
 /* Queries per workgroup of the match kernel (a wave, two queries per lane): the boundary the tests put rows across. */
 PCGX_API int32_t pcgx_fpfh_match_tile(void);
 
+/* ------------------------------------------- keypoints (extension: no reference parity)
+ * NOT in the reference.  The matcher above is brute force over all pairs, so coarse alignment of large clouds describes
+ * and matches a few thousand keypoints instead of every point.  Two operations, both over the tree's own points only
+ * (the q == NULL convention of pcgx_kdtree_normals, _fpfh and _knearest), every array in id order, deleted ids
+ * included.  This comment is the contract, tests/keypoints_oracle.py restates it.
+ * Neighbourhood: N(i) = the points p of the tree with DistSq(p, point i) < radius^2, DistSq the reference's float32
+ *   expression: exactly the set pcgx_kdtree_range_count counts on that handle (grid, forced walk, after DeletePoint).
+ *   Deleted points are nobody's neighbour.
+ * Local maxima of score[Len()] at `radius`: id i is a maximum iff
+ *   score[i] > 0 (a NaN, zero or negative score never qualifies; +inf does), and
+ *   i is in N(i) (so a deleted id, or a point with a NaN coordinate, is never a maximum), and
+ *   no other j in N(i) has score[j] > score[i], or score[j] == score[i] with j < i (ties go to the smaller id, as in
+ *   pcgx_kdtree_knearest; a NaN neighbour beats nobody; coincident points with equal scores leave one maximum, the
+ *   smallest id).
+ *   ids[Len()] holds the maxima in ascending id, then -1 in every remaining slot (the convention of
+ *   pcgx_fpfh_correspondences); *n_ids their number.
+ * ISS keypoints (Zhong 2009), in Open3D's form: for every id, C = pcgx_kdtree_normals' covariance over N(i) at
+ *   salient_radius (float64, centred on the query, about the mean, a tree point counting itself);
+ *   (l0, l1, l2) = C's eigenvalues in ascending order, unscaled, l0 clamped at 0, each rounded to float32;
+ *   (0, 0, 0) when count < max(min_neighbors, 3), when all neighbours coincide, or when the float64 trace is <= 0 (the
+ *   three cases in which normals answer "degenerate").  eigenvalues[3 i ..] holds them.
+ *   Salient iff l0 > 0 and l1 < gamma_21 * l2 and l0 < gamma_32 * l1, decided on the float32 values with float32
+ *   products rounded once each (as max_ratio_sq is applied above).  saliency[i] = l0 if salient, else 0.
+ *   Keypoints = the local maxima of saliency at non_max_radius, by the rule above exactly.
+ *   eigenvalues and saliency may each be NULL.
+ *   Not Open3D's or PCL's bits: Open3D breaks a tie by dropping both points and also asks for a minimum count in the
+ *   suppression neighbourhood; PCL scatters about the query point instead of the mean.
+ * PCGX_E_INVALID: a radius, or a gamma, that is not finite and > 0; a NULL tree; NULL score, ids or n_ids with
+ *   Len() > 0.  Len() == 0 is PCGX_OK and writes nothing except *n_ids = 0.  The same input gives the same bits on every
+ *   call.  Always computed on the device: one enumeration of every neighbourhood whose own score is > 0 plus a 4-byte
+ *   read by id per neighbour, and for ISS pcgx_kdtree_normals' cost before it.  Temporaries: Len() bytes of flags and
+ *   4 ceil(Len() / 2048) bytes of tile counts; ISS adds 4 Len() bytes when saliency is NULL. */
+PCGX_API pcgx_status pcgx_kdtree_local_maxima(const pcgx_kdtree *t, float radius, const float *score /* [Len()] */,
+                                              int64_t *ids /* [Len()] */, int64_t *n_ids);
+/* Same, every array device resident (ids and the count are int32 there), enqueued on `stream` (NULL: the library's);
+ * returns without waiting. */
+PCGX_API pcgx_status pcgx_kdtree_local_maxima_dev(const pcgx_kdtree *t, float radius, const float *d_score,
+                                                  int32_t *d_ids /* [Len()] */, int32_t *d_n_ids, void *stream);
+PCGX_API pcgx_status pcgx_kdtree_iss_keypoints(const pcgx_kdtree *t, float salient_radius, float non_max_radius,
+                                               float gamma_21, float gamma_32, int32_t min_neighbors,
+                                               float *eigenvalues /* [3 Len()], may be NULL */,
+                                               float *saliency /* [Len()], may be NULL */, int64_t *ids /* [Len()] */,
+                                               int64_t *n_ids);
+PCGX_API pcgx_status pcgx_kdtree_iss_keypoints_dev(const pcgx_kdtree *t, float salient_radius, float non_max_radius,
+                                                   float gamma_21, float gamma_32, int32_t min_neighbors,
+                                                   float *d_eigenvalues, float *d_saliency, int32_t *d_ids /* [Len()] */,
+                                                   int32_t *d_n_ids, void *stream);
+
 /* ------------------------------------------- pose from correspondences (extension: no reference parity)
  * NOT in the reference.  The rigid motion (a proper rotation and a translation, no scale) that most pairs of a
  * correspondence list agree on, by sample consensus: the starting pose every Fit here needs, from what

@@ -258,6 +258,10 @@ SIGNATURES = {
     "pcgx_fpfh_correspondences": (_i32, [_vp, _i64, _vp, _i64, _f32, _i32, _vp, _vp, _vp]),
     "pcgx_fpfh_correspondences_dev": (_i32, [_vp, _i64, _vp, _i64, _f32, _i32, _vp, _vp, _vp, _vp]),
     "pcgx_fpfh_match_tile": (_i32, []),
+    "pcgx_kdtree_local_maxima": (_i32, [_vp, _f32, _vp, _vp, C.POINTER(_i64)]),
+    "pcgx_kdtree_local_maxima_dev": (_i32, [_vp, _f32, _vp, _vp, _vp, _vp]),
+    "pcgx_kdtree_iss_keypoints": (_i32, [_vp, _f32, _f32, _f32, _f32, _i32, _vp, _vp, _vp, C.POINTER(_i64)]),
+    "pcgx_kdtree_iss_keypoints_dev": (_i32, [_vp, _f32, _f32, _f32, _f32, _i32, _vp, _vp, _vp, _vp, _vp]),
     "pcgx_pose_from_correspondences": (_i32, [_vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _f32, _f32, _i32,
                                               C.POINTER(_i32), C.POINTER(_i64), C.POINTER(_i64), _vp, C.POINTER(_i32),
                                               C.POINTER(_i64), _vp, _vp, _vp, _vp]),

@@ -18,10 +18,14 @@
 //   walk  (kRangeWalk: no grid, PCGX_RANGE_WALK=1): range_walk_nodes over the implicit tree;
 //   xwalk (kRangeXWalk: a handle that has seen DeletePoint): the patched tree's walk of knn_xwalk.h.
 // Queries: the caller's, or the tree's own points (q == NULL), as query_source (range_enum.h) lays them out.
+// ISS keypoints (keypoints.hip, pcgx_kdtree_iss_keypoints) take their eigenvalues from this kernel: the same moments and
+// the same solve, the eigenvalues scaled back by the trace and rounded to float32, and the saliency decided on them
+// (keypoint_terms.h) -- two more nullable outputs of normals_finish, the normal itself nullable for that caller.
 #include <math.h>
 #include <stdlib.h>
 
 #include "cov3.h"
+#include "keypoint_terms.h"
 #include "knn_grid.h"
 #include "knn_xwalk.h"
 #include "range_walk.h"
@@ -31,17 +35,23 @@ namespace pcgx {
 constexpr int kNormBlock = kRangeWalkBlock;     // one wave per workgroup: the walks' LDS frame stacks are [level][64]
 
 struct NormOut {
-  float *normals;    // [3 nq]
+  float *normals;    // [3 nq] or nullptr (ISS)
   float *curvature;  // [nq] or nullptr
   int32_t *counts;   // [nq] or nullptr
   float vx, vy, vz;  // viewpoint
   int32_t min_nb;    // >= 3
+  // ISS (nullptr for pcgx_kdtree_normals): l0 <= l1 <= l2 of C, unscaled, l0 clamped at 0, float32; (0, 0, 0) where
+  // the normal would be 0.  saliency: iss_saliency of them under the two thresholds.
+  float *eigenvalues;  // [3 nq] or nullptr
+  float *saliency;     // [nq] or nullptr
+  float gamma_21, gamma_32;
 };
 
 // count, moments -> normal, curvature of query i (the contract in the file's head)
 __device__ __forceinline__ void normals_finish(const NormAcc &a, const float qx, const float qy, const float qz,
                                                const NormOut &O, const int64_t i) {
   float nx = 0.0f, ny = 0.0f, nz = 0.0f, cv = __builtin_nanf("");
+  float l0f = 0.0f, l1f = 0.0f, l2f = 0.0f;
   const bool spread = !(a.lox == a.hix && a.loy == a.hiy && a.loz == a.hiz);
   if (a.n >= O.min_nb && spread) {
     double A[3][3], V[3][3];
@@ -55,13 +65,27 @@ __device__ __forceinline__ void normals_finish(const NormAcc &a, const float qx,
       ny = (float)uy;
       nz = (float)uz;
       cv = (float)(fmax(l0, 0.0) / (e0 + e1 + e2));
+      if (O.eigenvalues || O.saliency) {  // (the solve works at unit trace: back by the trace)
+        const double lo = fmin(e0, e1), hi = fmax(e0, e1);
+        l0f = (float)(fmax(l0, 0.0) * tr);
+        l1f = (float)(fmax(lo, fmin(hi, e2)) * tr);
+        l2f = (float)(fmax(hi, e2) * tr);
+      }
     }
   }
-  O.normals[3 * i] = nx;
-  O.normals[3 * i + 1] = ny;
-  O.normals[3 * i + 2] = nz;
+  if (O.normals) {
+    O.normals[3 * i] = nx;
+    O.normals[3 * i + 1] = ny;
+    O.normals[3 * i + 2] = nz;
+  }
   if (O.curvature) O.curvature[i] = cv;
   if (O.counts) O.counts[i] = a.n;
+  if (O.eigenvalues) {
+    O.eigenvalues[3 * i] = l0f;
+    O.eigenvalues[3 * i + 1] = l1f;
+    O.eigenvalues[3 * i + 2] = l2f;
+  }
+  if (O.saliency) O.saliency[i] = iss_saliency(l0f, l1f, l2f, O.gamma_21, O.gamma_32);
 }
 
 template <int kSrc>
@@ -126,23 +150,19 @@ pcgx_status normals_check(const char *fn, const pcgx_kdtree *t, const float *q, 
   return PCGX_OK;
 }
 
-// everything device resident; temporaries from ctx().arena
-pcgx_status normals_enqueue(const pcgx_kdtree *t, const float *d_q, int64_t nq, float radius, const float viewpoint[3],
-                            int32_t min_neighbors, float *d_normals, float *d_curvature, int32_t *d_counts,
-                            hipStream_t st) {
-  PCGX_TRY(ctx().arena.begin(st));
+}  // namespace
+
+namespace pcgx {
+
+// everything device resident; temporaries from ctx().arena, which the caller has begun
+pcgx_status normals_enqueue(const pcgx_kdtree *t, const float *d_q, int64_t nq, float radius, NormOut O, hipStream_t st) {
   const RangeSrc src = range_source(t);  // as pcgx_kdtree_range_count takes it
   XTreeView xv{};
   if (src == kRangeXWalk) PCGX_TRY(xtree_view(t, &xv, st));
   const TreeView tv = t->view();
   QuerySource Q;
   PCGX_TRY(query_source(t, src, d_q, nq, &Q, st));
-  NormOut O{d_normals, d_curvature, d_counts, 0.0f, 0.0f, 0.0f, min_neighbors < 3 ? 3 : min_neighbors};
-  if (viewpoint) {
-    O.vx = viewpoint[0];
-    O.vy = viewpoint[1];
-    O.vz = viewpoint[2];
-  }
+  if (O.min_nb < 3) O.min_nb = 3;
   const float bound = radius * radius;
   const dim3 grid(xcd_grid((unsigned)((nq + kNormBlock - 1) / kNormBlock))), block(kNormBlock);
   const int64_t guard = xwalk_guard(t->n);
@@ -159,7 +179,20 @@ pcgx_status normals_enqueue(const pcgx_kdtree *t, const float *d_q, int64_t nq, 
   return PCGX_OK;
 }
 
-}  // namespace
+// The eigenvalue stage of ISS keypoints (keypoints.hip): the tree's own points, eigenvalues [3 Len()] (may be nullptr)
+// and saliency [Len()] in id order.  The caller has begun ctx().arena.
+pcgx_status normals_iss_enqueue(const pcgx_kdtree *t, float radius, int32_t min_neighbors, float gamma_21, float gamma_32,
+                                float *d_eigenvalues, float *d_saliency, hipStream_t st) {
+  NormOut O{};
+  O.min_nb = min_neighbors;
+  O.eigenvalues = d_eigenvalues;
+  O.saliency = d_saliency;
+  O.gamma_21 = gamma_21;
+  O.gamma_32 = gamma_32;
+  return normals_enqueue(t, nullptr, t->n, radius, O, st);
+}
+
+}  // namespace pcgx
 
 extern "C" pcgx_status pcgx_kdtree_normals_dev(const pcgx_kdtree *t, const float *d_q, int64_t nq, float radius,
                                                const float viewpoint[3], int32_t min_neighbors, float *d_normals,
@@ -168,8 +201,19 @@ extern "C" pcgx_status pcgx_kdtree_normals_dev(const pcgx_kdtree *t, const float
   PCGX_TRY(normals_check("pcgx_kdtree_normals_dev", t, d_q, nq, radius, d_normals));
   if (nq == 0) return PCGX_OK;
   PCGX_TRY(ensure_init());
-  return normals_enqueue(t, d_q, nq, radius, viewpoint, min_neighbors, d_normals, d_curvature, d_counts,
-                         pick_stream(stream));
+  hipStream_t st = pick_stream(stream);
+  PCGX_TRY(ctx().arena.begin(st));
+  NormOut O{};
+  O.normals = d_normals;
+  O.curvature = d_curvature;
+  O.counts = d_counts;
+  O.min_nb = min_neighbors;
+  if (viewpoint) {
+    O.vx = viewpoint[0];
+    O.vy = viewpoint[1];
+    O.vz = viewpoint[2];
+  }
+  return normals_enqueue(t, d_q, nq, radius, O, st);
 }
 
 extern "C" pcgx_status pcgx_kdtree_normals(const pcgx_kdtree *t, const float *q, int64_t nq, float radius,

@@ -187,6 +187,39 @@ class KDTree {  // pc/storage/kdtree/kdtree.go:14-23
                            n ? r.counts[0].data() : nullptr, r.pairs.data()));
     return r;
   }
+  // The points whose score is the largest of their radius neighbourhood, ascending ids (extension: no reference
+  // parity; include/pcgx.h, pcgx_kdtree_local_maxima).  `score`: one per point in id order; only a score > 0
+  // qualifies, ties go to the smaller id.
+  std::vector<int64_t> LocalMaxima(float radius, const std::vector<float> &score) const {
+    const int64_t n = Len();
+    if ((int64_t)score.size() != n) throw Error(PCGX_E_INVALID, "one score per point of the tree is required");
+    std::vector<int64_t> ids((size_t)n);
+    int64_t m = 0;
+    check(pcgx_kdtree_local_maxima(h_.get(), radius, score.data(), ids.data(), &m));
+    ids.resize((size_t)m);
+    return ids;
+  }
+  // ISS keypoints (extension: no reference parity; include/pcgx.h, pcgx_kdtree_iss_keypoints).  eigenvalues: of
+  // Normals' covariance at salientRadius, ascending, {0, 0, 0} where Normals answers "degenerate"; saliency: the
+  // smallest eigenvalue of a salient point, else 0; ids: LocalMaxima(nonMaxRadius, saliency).  All in id order.
+  struct ISSResult {
+    std::vector<int64_t> ids;
+    std::vector<Vec3> eigenvalues;
+    std::vector<float> saliency;
+  };
+  ISSResult ISSKeypoints(float salientRadius, float nonMaxRadius, float gamma21 = 0.975f, float gamma32 = 0.975f,
+                         int32_t minNeighbors = 5) const {
+    const int64_t n = Len();
+    ISSResult r;
+    r.ids.resize((size_t)n);
+    r.eigenvalues.resize((size_t)n);
+    r.saliency.resize((size_t)n);
+    int64_t m = 0;
+    check(pcgx_kdtree_iss_keypoints(h_.get(), salientRadius, nonMaxRadius, gamma21, gamma32, minNeighbors,
+                                    n ? r.eigenvalues[0].data() : nullptr, r.saliency.data(), r.ids.data(), &m));
+    r.ids.resize((size_t)m);
+    return r;
+  }
   // The k points with the smallest (DistSq, ID) among those with DistSq < maxRange^2, ascending (extension: no
   // reference parity; include/pcgx.h, pcgx_kdtree_knearest: ties go by ID).
   std::vector<Neighbor> KNearest(const Vec3 &p, int32_t k, float maxRange) const {

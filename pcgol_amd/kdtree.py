@@ -1,7 +1,7 @@
 """pc/storage/kdtree mirror: KDTree on the GPU behind the storage.Search shape
 (pc/storage/search.go:13-17): Vec3At / Len / Nearest, plus batched NearestBatch, and extensions with no
-reference counterpart: surface normals (Normals), FPFH descriptors (FPFH), k nearest neighbours (KNearest) and
-their covariances (Covariances)."""
+reference counterpart: surface normals (Normals), FPFH descriptors (FPFH), keypoints (LocalMaxima, ISSKeypoints), k
+nearest neighbours (KNearest) and their covariances (Covariances)."""
 import ctypes as C
 
 import numpy as np
@@ -199,6 +199,54 @@ class KDTree:
             self._h, L.ptr(int(d_normals)), float(radius), L.ptr(int(d_fpfh)),
             L.ptr(int(d_counts)) if d_counts else None, L.ptr(int(d_pairs)) if d_pairs else None,
             L.ptr(stream) if stream else None))
+
+    # -- extension (no reference parity): keypoints, what a large cloud is described and matched at
+    def LocalMaxima(self, radius, Score):
+        """The points whose score is the largest of their radius neighbourhood (DistSq < radius^2, Range's set) -> ids
+        int64, ascending.  Score: (n,) float32 in id order.  Only a score > 0 qualifies (NaN never, +inf does); ties go
+        to the smaller id; a deleted id or a point with a NaN coordinate is never a maximum (include/pcgx.h,
+        pcgx_kdtree_local_maxima)."""
+        n = self.Len()
+        score = L.f32c(Score).reshape(-1)
+        if len(score) != n:
+            raise ValueError("one score per point of the tree is required")
+        ids = np.empty(n, np.int64)
+        cnt = C.c_int64()
+        L.check(L.lib().pcgx_kdtree_local_maxima(self._h, float(radius), L.ptr(score), L.ptr(ids), C.byref(cnt)))
+        return ids[:cnt.value]
+
+    def LocalMaximaDev(self, radius, d_score, d_ids, d_n_ids, stream=0):
+        """Device-resident LocalMaxima: raw device addresses (e.g. torch .data_ptr()); d_score float32 [Len()], d_ids
+        int32 [Len()] (the maxima ascending, then -1), d_n_ids one int32.  Enqueued on `stream`, returns without
+        waiting."""
+        L.check(L.lib().pcgx_kdtree_local_maxima_dev(
+            self._h, float(radius), L.ptr(int(d_score)), L.ptr(int(d_ids)), L.ptr(int(d_n_ids)),
+            L.ptr(stream) if stream else None))
+
+    def ISSKeypoints(self, SalientRadius, NonMaxRadius, Gamma21=0.975, Gamma32=0.975, MinNeighbors=5):
+        """ISS keypoints (Zhong 2009, Open3D's form) -> (ids int64 ascending, eigenvalues (n,3) float32 ascending,
+        saliency (n,) float32).  eigenvalues: of Normals' covariance at SalientRadius, (0, 0, 0) where Normals answers
+        "degenerate"; saliency: l0 where l0 > 0, l1 < Gamma21 l2 and l0 < Gamma32 l1, else 0; ids: LocalMaxima of the
+        saliency at NonMaxRadius (include/pcgx.h, pcgx_kdtree_iss_keypoints)."""
+        n = self.Len()
+        eig = np.empty((n, 3), np.float32)
+        sal = np.empty(n, np.float32)
+        ids = np.empty(n, np.int64)
+        cnt = C.c_int64()
+        L.check(L.lib().pcgx_kdtree_iss_keypoints(self._h, float(SalientRadius), float(NonMaxRadius), float(Gamma21),
+                                                  float(Gamma32), int(MinNeighbors), L.ptr(eig), L.ptr(sal), L.ptr(ids),
+                                                  C.byref(cnt)))
+        return ids[:cnt.value], eig, sal
+
+    def ISSKeypointsDev(self, SalientRadius, NonMaxRadius, d_ids, d_n_ids, d_eigenvalues=0, d_saliency=0, Gamma21=0.975,
+                        Gamma32=0.975, MinNeighbors=5, stream=0):
+        """Device-resident ISSKeypoints: raw device addresses (e.g. torch .data_ptr()); d_ids int32 [Len()] (the
+        keypoints ascending, then -1), d_n_ids one int32, d_eigenvalues float32 [3 Len()], d_saliency float32 [Len()].
+        Enqueued on `stream`, returns without waiting."""
+        L.check(L.lib().pcgx_kdtree_iss_keypoints_dev(
+            self._h, float(SalientRadius), float(NonMaxRadius), float(Gamma21), float(Gamma32), int(MinNeighbors),
+            L.ptr(int(d_eigenvalues)) if d_eigenvalues else None, L.ptr(int(d_saliency)) if d_saliency else None,
+            L.ptr(int(d_ids)), L.ptr(int(d_n_ids)), L.ptr(stream) if stream else None))
 
     # -- extension (no reference parity): k nearest neighbours
     def KNearest(self, p, k, maxRange):
