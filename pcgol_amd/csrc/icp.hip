@@ -23,6 +23,7 @@
 
 #include "knn_grid.h"
 #include "knn_xwalk.h"
+#include "icp_session_plan.h"
 #include "icp_step_plan.h"
 #include "strict_terms.h"
 #include "gicp_terms.h"
@@ -147,7 +148,6 @@ __device__ __forceinline__ void reduce_block_range(uint32_t *s_scratch, const fl
 // kGrid (exact mode only): icp_grid_kernel ran before and answered every target the uniform grid
 // could certify (knn_grid.h); only the rest (walk_list, this workgroup's segment, walk_count[slot]
 // entries) is walked here.
-constexpr int kIcpGridBlock = 256;
 constexpr int kIcpStrictGridBlock = 64;  // strict sessions: no workgroup reduction in the grid pass, one wave per workgroup
 
 template <bool kMinDist, bool kPlane, bool kGrid, bool kSums = true>
@@ -640,8 +640,6 @@ __global__ __launch_bounds__(256) void gather_target_cov_kernel(const float *__r
 // icp_final_reduce_kernel<., true> follows.  A pair whose S is not positive definite is in none of the sums;
 // dropped[b] counts this workgroup's.  Algorithmic bytes per target: point 12, covariance 24, pair 16 + 4, partner's
 // covariance 32.
-constexpr int kGicpBlock = 256;
-
 __global__ __launch_bounds__(kGicpBlock) void icp_gicp_sums_kernel(
     const float *__restrict__ tx, const float *__restrict__ ty, const float *__restrict__ tz, int64_t nt,
     const IcpState *__restrict__ state, const float4 *__restrict__ match, const uint32_t *__restrict__ match_id,
@@ -740,6 +738,7 @@ using namespace pcgx;
 
 struct pcgx_icp_session {
   const pcgx_kdtree *base = nullptr;
+  OwnedBlocks owned;  // every buffer below that is the session's own, the lazily made ones too: pcgx_icp_session_free
   bool patched = false;  // base had deletions at creation: walk its patched explicit tree (icp_corr_xkernel)
   int64_t nt = 0;
   float *d_xyz = nullptr;  // SoA: x[nt] | y[nt] | z[nt], Morton order of the original target
@@ -762,7 +761,6 @@ struct pcgx_icp_session {
   uint32_t *d_walk_list = nullptr;   // [nt] per workgroup segment: targets the grid pass left to the walk
   uint32_t *d_walk_count = nullptr;  // [grid] entries in each segment (zero between iterations)
   double *d_sums = nullptr;  // caller's buffer, or own
-  bool own_sums = false;
   double *d_xchg = nullptr;  // sharded float64 steps: the sums + the ranks' error flag, what the all-reduce carries
   int32_t steps_sharded = 0; // sharded steps enqueued (fault injection of the tests counts them)
   int32_t host_iter = 0;     // Evaluates enqueued since the device's loop state was last WRITTEN (session made, reset, set_pose):
@@ -806,6 +804,24 @@ struct pcgx_icp_session {
 
 static pcgx_status settle(pcgx_icp_session *s, hipStream_t st);
 static int icp_knob(const char *name, int def, int lo, int hi);
+
+// How an entry point that reads or writes a session's state begins: its stream, noted on the session (touch), and the
+// steps enqueued without the leftover walk (enqueue_corr) looked at
+static pcgx_status enter(pcgx_icp_session *s, void *stream, hipStream_t *st) {
+  *st = pick_stream(stream);
+  s->touch(*st);
+  return settle(s, *st);
+}
+
+// A block of the cache that the session owns from here on
+template <class T>
+static hipError_t session_alloc(pcgx_icp_session *s, T **p, size_t bytes) {
+  const hipError_t e = dev_cache_alloc((void **)p, bytes);
+  if (e == hipSuccess) s->owned.adopt(*p, dev_cache_free);
+  return e;
+}
+
+static double now_us() { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
 
 static IcpKernelParams make_kernel_params(const pcgx_icp_params *p) {
   IcpKernelParams kp;
@@ -906,9 +922,8 @@ extern "C" pcgx_status pcgx_icp_session_set_pose(pcgx_icp_session *s, const floa
                                                  int32_t iter, void *stream) {
   PCGX_API_LOCK();
   if (!s || !trans16 || iter < 0) return fail(PCGX_E_INVALID, "pcgx_icp_session_set_pose: bad argument");
-  hipStream_t st = pick_stream(stream);
-  s->touch(st);
-  PCGX_TRY(settle(s, st));  // (steps enqueued without the leftover walk: enqueue_corr)
+  hipStream_t st;
+  PCGX_TRY(enter(s, stream, &st));
   IcpState h;
   memset(&h, 0, sizeof h);
   memcpy(h.trans, trans16, sizeof h.trans);
@@ -923,9 +938,8 @@ extern "C" pcgx_status pcgx_icp_session_read_sums(pcgx_icp_session *s, double su
   PCGX_API_LOCK();
   if (!s || !sums10) return fail(PCGX_E_INVALID, "pcgx_icp_session_read_sums: bad argument");
   if (s->plane) return fail(PCGX_E_INVALID, "pcgx_icp_session_read_sums: plane session (30 sums): use pcgx_icp_session_read_sums_n");
-  hipStream_t st = pick_stream(stream);
-  s->touch(st);
-  PCGX_TRY(settle(s, st));  // (steps enqueued without the leftover walk: enqueue_corr)
+  hipStream_t st;
+  PCGX_TRY(enter(s, stream, &st));
   PCGX_HIP_TRY(hipMemcpyAsync(sums10, s->d_sums, S_COUNT * sizeof(double), hipMemcpyDeviceToHost, st));
   PCGX_HIP_TRY(hipStreamSynchronize(st));
   return PCGX_OK;
@@ -953,9 +967,8 @@ extern "C" pcgx_status pcgx_icp_session_sums_count(const pcgx_icp_session *s, in
 extern "C" pcgx_status pcgx_icp_session_read_sums_n(pcgx_icp_session *s, double *sums, int32_t cap, void *stream) {
   PCGX_API_LOCK();
   if (!s || !sums || cap < s->n_sums()) return fail(PCGX_E_INVALID, "pcgx_icp_session_read_sums_n: bad argument");
-  hipStream_t st = pick_stream(stream);
-  s->touch(st);
-  PCGX_TRY(settle(s, st));  // (steps enqueued without the leftover walk: enqueue_corr)
+  hipStream_t st;
+  PCGX_TRY(enter(s, stream, &st));
   PCGX_HIP_TRY(hipMemcpyAsync(sums, s->d_sums, (size_t)s->n_sums() * sizeof(double), hipMemcpyDeviceToHost, st));
   PCGX_HIP_TRY(hipStreamSynchronize(st));
   return PCGX_OK;
@@ -971,37 +984,145 @@ extern "C" pcgx_status pcgx_icp_session_free(pcgx_icp_session *s) {
   if (s->n_used > 4) (void)hipDeviceSynchronize();
   else
     for (int k = 0; k < s->n_used; k++) (void)hipStreamSynchronize(s->used[k]);
-  dev_cache_free(s->d_xyz);
-  dev_cache_free(s->d_state);
-  dev_cache_free(s->d_partials);
-  dev_cache_free(s->d_pos_of);
-  dev_cache_free(s->d_orig_of);
-  dev_cache_free(s->d_match_caller);
-  dev_cache_free(s->d_terms);
-  dev_cache_free(s->d_valid);
-  strict_destroy(s->strict_buf);
-  dev_cache_free(s->d_match);
-  dev_cache_free(s->d_match_cert);
-  dev_cache_free(s->d_first_leaf);
-  dev_cache_free(s->d_walk_list);
-  dev_cache_free(s->d_walk_count);
-  dev_cache_free(s->d_match_id);
-  dev_cache_free(s->d_normals);
-  dev_cache_free(s->d_base_cov);
-  dev_cache_free(s->d_target_cov);
-  dev_cache_free(s->d_dropped);
-  if (s->own_sums) dev_cache_free(s->d_sums);
-  dev_cache_free(s->d_xchg);
-  dev_cache_free(s->d_small_sync);
-  dev_cache_free(s->d_small_perm);
+  s->owned.release_all();
   delete s;
   return PCGX_OK;
+}
+
+// A device copy of an input that may be on the host: arena space (behind Arena::begin) and a staged upload on `st`.
+// t_space: when the space was taken (PCGX_FIT_TRACE)
+static pcgx_status device_input(const float *src, size_t count, bool on_device, hipStream_t st, const float **d_out,
+                                double *t_space = nullptr) {
+  *d_out = src;
+  if (on_device) return PCGX_OK;
+  float *stage = nullptr;
+  PCGX_TRY(ctx().arena.alloc_n(count, &stage));
+  if (t_space) *t_space = now_us();
+  PCGX_TRY(staged_upload(stage, src, count * sizeof(float), st));
+  *d_out = stage;
+  return PCGX_OK;
+}
+
+static pcgx_status setup_failed(hipError_t e) { return fail(PCGX_E_HIP, "icp session setup failed: %s", hipGetErrorString(e)); }
+
+// The session's buffers as the plan sizes them (0: none), in SessionBuffer's order; the caller's d_sums where it gave one.
+static pcgx_status session_allocate(pcgx_icp_session *s, const SessionPlan &p, double *d_sums) {
+  void **const slot[kSessionBuffers] = {
+      (void **)&s->d_xyz,        (void **)&s->d_state,      (void **)&s->d_partials,   (void **)&s->d_pos_of,
+      (void **)&s->d_match,      (void **)&s->d_match_cert, (void **)&s->d_first_leaf, (void **)&s->d_walk_list,
+      (void **)&s->d_walk_count, (void **)&s->d_sums,       (void **)&s->d_match_id,   (void **)&s->d_normals,
+      (void **)&s->d_base_cov,   (void **)&s->d_target_cov, (void **)&s->d_dropped,    (void **)&s->d_valid,
+      (void **)&s->d_small_perm};
+  hipError_t e = hipSuccess;
+  for (int b = 0; b < kSessionBuffers && e == hipSuccess; b++)
+    if (p.bytes[b]) e = session_alloc(s, slot[b], p.bytes[b]);
+  if (e == hipSuccess && p.small_buffers) e = session_alloc(s, &s->d_terms, small_fit_terms_bytes(s->nt));
+  if (e == hipSuccess && p.small_buffers) e = session_alloc(s, &s->d_small_sync, small_fit_sync_bytes());
+  if (e != hipSuccess) return fail(PCGX_E_OOM, "icp session allocation failed: %s", hipGetErrorString(e));
+  if (d_sums) s->d_sums = d_sums;
+  return PCGX_OK;
+}
+
+// A plane session's normals or a GICP session's base covariances, packed per base id.  The stream is waited for: the
+// arena space taken here is taken again for the target (order_target's Arena::begin), and host arrays of the caller's
+// have been read when this returns.
+static pcgx_status stage_side_inputs(pcgx_icp_session *s, const float *normals, const float *base_cov6, bool on_device,
+                                     hipStream_t st) {
+  if (!s->plane) return PCGX_OK;
+  const int64_t nb = s->base->n;  // normals and covariances are indexed by the original ids
+  hipError_t e;
+  if (s->gicp && (e = hipMemsetAsync(s->d_dropped, 0, (size_t)s->gicp_grid * sizeof(uint32_t), st)) != hipSuccess)
+    return setup_failed(e);
+  PCGX_TRY(ctx().arena.begin(st));
+  const float *d_in = nullptr;
+  PCGX_TRY(device_input(s->gicp ? base_cov6 : normals, (size_t)nb * (s->gicp ? 6 : 3), on_device, st, &d_in));
+  const dim3 blocks((unsigned)((nb + 255) / 256));
+  if (s->gicp) hipLaunchKernelGGL(pack_base_cov_kernel, blocks, dim3(256), 0, st, d_in, nb, s->d_base_cov);
+  else hipLaunchKernelGGL(pack_normals_kernel, blocks, dim3(256), 0, st, d_in, nb, s->d_normals);
+  if ((e = hipStreamSynchronize(st)) != hipSuccess) return setup_failed(e);
+  return PCGX_OK;
+}
+
+// The target into the session's order: upload, Morton order and gather (a small session: small_fit_prepare, the
+// caller's order or its own grouping), and a GICP session's target covariances behind it through the same `perm`.
+// Such a small session's start values, its words' zeroes and its target's coordinates are ONE launch's work
+// (small_prepare_kernel) behind the upload: a host-pointer Fit is then upload, that launch, the Fit's, the result -- it
+// was ten operations on the stream, 5 us apart.
+static pcgx_status order_target(pcgx_icp_session *s, const float *target, const float *target_cov6, bool on_device,
+                                hipStream_t st, bool trace, double *t_phase) {
+  const int64_t nt = s->nt;
+  const pcgx_kdtree *base = s->base;
+  Arena &ar = ctx().arena;
+  PCGX_TRY(ar.begin(st));
+  const float *d_q = nullptr;
+  const void *up = nullptr;
+  // (a small target: read by small_prepare_kernel out of the context's pinned memory)
+  if (!on_device && s->small && (up = small_upload(target, (size_t)nt * 12)) != nullptr) {
+    d_q = static_cast<const float *>(up);
+    t_phase[2] = t_phase[3] = trace ? now_us() : 0.0;
+  } else {
+    PCGX_TRY(device_input(target, (size_t)nt * 3, on_device, st, &d_q, trace ? &t_phase[2] : nullptr));  // [2]: memsets, arena
+    if (!on_device) t_phase[3] = trace ? now_us() : 0.0;  // upload enqueued (pageable memory: staged by the runtime)
+  }
+  int32_t *perm = nullptr;
+  if (s->small) {
+    PCGX_TRY(small_fit_prepare(d_q, nt, base->bbox_lo, base->bbox_hi, s->d_small_perm, s->d_xyz, s->d_pos_of, s->d_state, s->d_terms,
+                               s->d_small_sync, st));
+    if (up) small_upload_read(st);
+  } else {
+    if (nt > 1) {
+      PCGX_TRY(ar.alloc_n((size_t)nt, &perm));
+      PCGX_TRY(morton_order(d_q, nt, base->bbox_lo, base->bbox_hi, perm, st));
+    }
+    hipLaunchKernelGGL(gather_soa_kernel, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, st, d_q, perm, nt,
+                       s->d_xyz, s->d_xyz + nt, s->d_xyz + 2 * nt, s->d_pos_of);
+  }
+  if (s->gicp) {  // the target's covariances, into the same order
+    const float *d_c6 = nullptr;
+    PCGX_TRY(device_input(target_cov6, (size_t)nt * 6, on_device, st, &d_c6));
+    hipLaunchKernelGGL(gather_target_cov_kernel, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, st, d_c6,
+                       (const int32_t *)perm, nt, s->d_target_cov);
+  }
+  t_phase[4] = trace ? now_us() : 0.0;  // order + gather enqueued
+  // No wait here: what follows on this session is enqueued on this stream, behind the gather, or on another stream
+  // through an entry point that names it -- those wait for this one first (touch(): a session's first use on a stream
+  // that is not the one it was made on).  The host's twenty step enqueues (0.3 ms) used to start only when upload,
+  // order and gather had drained (0.25 ms of idle host and, behind it, idle GPU per host-pointer Fit).
+  const hipError_t e = hipGetLastError();
+  return e == hipSuccess ? PCGX_OK : setup_failed(e);
+}
+
+// What plan_session() decides on: the arguments, the base, the environment (PCGX_ICP_STRICT, experiments: overrides
+// sums_mode; PCGX_ICP_SMALL), icp_small.hip's and icp_grid's answers
+static SessionFacts session_facts(const pcgx_kdtree *base, bool normals, bool covariances, const pcgx_icp_params *params,
+                                  int64_t nt, bool caller_sums) {
+  static_assert(PCGX_SUMS_REFERENCE == 0 && PCGX_SUMS_F64_TREE == 1 && S_COUNT == 10 && P_COUNT == 30,
+                "SessionFacts::sums_mode, SessionPlan::n_sums");
+  static const bool small_on = icp_knob("PCGX_ICP_SMALL", 1, 0, 1) != 0;
+  SessionFacts f;
+  f.normals = normals;
+  f.covariances = covariances;
+  f.sums_mode = params->sums_mode;
+  if (const char *e = getenv("PCGX_ICP_STRICT")) f.strict_override = e[0] == '1' ? 1 : (e[0] == '2' ? 2 : 0);
+  f.nt = nt;
+  f.n_base = base->n;
+  f.patched = base->n_deleted > 0;
+  f.has_nan = base->has_nan;
+  f.small_on = small_on;
+  f.small_eligible = small_fit_eligible(base->view(), nt, base->many_ties);
+  f.small_wants_order = small_fit_wants_order(nt);
+  f.grid = icp_grid(nt, base->view());
+  f.num_cu = ctx().num_cu;
+  f.caller_sums = caller_sums;
+  f.state_bytes = sizeof(IcpState);
+  return f;
 }
 
 // normals == nullptr: the reference's point-to-point session; else a plane session (normals:
 // packed xyz per base point in id order, host or device memory like the target).
 // base_cov6 != nullptr: a GICP session (base_cov6 per base id, target_cov6 per target in the caller's order; where the
 // target is).
+// Check, plan (icp_session_plan.h), allocate from the plan, stage the side inputs, start values, order the target.
 static pcgx_status session_create(const pcgx_kdtree *base, const float *normals, float damping,
                                   const float *target, int64_t nt, int32_t target_on_device,
                                   const pcgx_icp_params *params, double *d_sums,
@@ -1022,180 +1143,46 @@ static pcgx_status session_create(const pcgx_kdtree *base, const float *normals,
     return fail(PCGX_E_INVALID, "pcgx_icp_session_create: sums_mode %d is none of PCGX_SUMS_*", params->sums_mode);
   PCGX_TRY(ensure_init());
   hipStream_t st = ctx().stream;
-  const int64_t n_base_ids = base->n;  // normals are indexed by the original ids
   // after DeletePoint the handle holds the reference's patched tree: the session walks that one
   // (knn_explicit.hip); no node left: Pairs() finds nothing (correspondence.go:27-29, kdtree.go:84-86)
   const bool patched = base->n_deleted > 0;
   if (patched && base->n_deleted >= base->n)
     return fail(PCGX_E_NOT_ENOUGH_PAIRS, "not enough correspondence pairs (every base point was deleted)");
   static const bool trace = getenv("PCGX_FIT_TRACE") != nullptr;  // (where a session's set-up time goes, per phase)
-  auto now_us = []() { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
   double t_phase[6] = {0, 0, 0, 0, 0, 0};
   t_phase[0] = trace ? now_us() : 0.0;
+
+  const SessionFacts f = session_facts(base, normals != nullptr, base_cov6 != nullptr, params, nt, d_sums != nullptr);
+  const SessionPlan p = plan_session(f);
+
   pcgx_icp_session *s = new pcgx_icp_session();
   s->base = base;
   s->touch(st);
-  s->patched = patched;
+  s->patched = f.patched;
   const_cast<pcgx_kdtree *>(base)->sessions.fetch_add(1);
   s->nt = nt;
-  s->gicp = base_cov6 != nullptr;
-  s->plane = normals != nullptr || s->gicp;
-  // the reference's own sums unless the caller asks otherwise (include/pcgx.h, PCGX_SUMS_*); the
-  // point-to-plane extension has no reference sums to reproduce
-  s->strict = s->plane ? 0 : (params->sums_mode == PCGX_SUMS_REFERENCE ? 1 : (params->sums_mode == PCGX_SUMS_F64_TREE ? 0 : 2));
-  s->strict_explicit = s->strict == 2;
-  if (const char *e = getenv("PCGX_ICP_STRICT")) {  // experiments: overrides sums_mode
-    s->strict = s->plane ? 0 : (e[0] == '1' ? 1 : (e[0] == '2' ? 2 : 0));
-    s->strict_explicit = s->strict != 0;
-  }
+  s->nt_pad = p.nt_pad;
+  s->gicp = p.gicp;
+  s->plane = p.plane;
+  s->strict = p.strict;
+  s->strict_explicit = p.strict_explicit;
+  s->small = p.small;
+  s->grid = f.grid;
+  s->gicp_grid = p.gicp_grid;
   s->kp = make_kernel_params(params);
   s->kp.gn.damping = damping;
   s->max_iteration = s->kp.upd.max_iteration;
-  s->grid = icp_grid(nt, base->view());
-  if (s->gicp) {
-    const int64_t g = (nt + kGicpBlock - 1) / kGicpBlock, cap = (int64_t)ctx().num_cu * 8;
-    s->gicp_grid = (int)(g < 1 ? 1 : (g > cap ? cap : g));
-  }
-  pcgx_status rc = PCGX_OK;
-  auto bail = [&](pcgx_status code) {
-    pcgx_icp_session_free(s);
-    return code;
-  };
-  hipError_t e;
-  if ((e = dev_cache_alloc((void **)&s->d_xyz, (size_t)(nt ? nt : 1) * 12)) != hipSuccess ||
-      (e = dev_cache_alloc((void **)&s->d_state, sizeof(IcpState))) != hipSuccess ||
-      (e = dev_cache_alloc((void **)&s->d_partials,
-                           ((size_t)s->grid + (size_t)(nt / kIcpGridBlock) + 1 + (size_t)(s->gicp ? s->gicp_grid : 0)) *
-                               s->n_sums() * sizeof(double))) != hipSuccess ||
-      (e = dev_cache_alloc((void **)&s->d_pos_of, (size_t)(nt ? nt : 1) * sizeof(uint32_t))) != hipSuccess ||
-      (e = dev_cache_alloc((void **)&s->d_match, (size_t)(nt ? nt : 1) * sizeof(float4))) != hipSuccess ||
-      (e = dev_cache_alloc((void **)&s->d_match_cert, (size_t)(nt ? nt : 1) * sizeof(float))) != hipSuccess ||
-      (e = dev_cache_alloc((void **)&s->d_first_leaf, (size_t)(nt ? nt : 1) * sizeof(uint32_t))) != hipSuccess ||
-      (e = dev_cache_alloc((void **)&s->d_walk_list, (size_t)(nt ? nt : 1) * sizeof(uint32_t))) != hipSuccess ||
-      (e = dev_cache_alloc((void **)&s->d_walk_count, (size_t)s->grid * sizeof(uint32_t))) != hipSuccess)
-    return bail(fail(PCGX_E_OOM, "icp session allocation failed: %s", hipGetErrorString(e)));
-  if (d_sums) {
-    s->d_sums = d_sums;
-  } else {
-    if ((e = dev_cache_alloc((void **)&s->d_sums, (size_t)s->n_sums() * sizeof(double))) != hipSuccess)
-      return bail(fail(PCGX_E_OOM, "icp session allocation failed: %s", hipGetErrorString(e)));
-    s->own_sums = true;
-  }
-  if (s->gicp) {
-    const int64_t nb = n_base_ids;
-    if ((e = dev_cache_alloc((void **)&s->d_match_id, (size_t)(nt ? nt : 1) * sizeof(uint32_t))) != hipSuccess ||
-        (e = dev_cache_alloc((void **)&s->d_base_cov, (size_t)nb * 2 * sizeof(float4))) != hipSuccess ||
-        (e = dev_cache_alloc((void **)&s->d_target_cov, (size_t)(nt ? nt : 1) * 3 * sizeof(float2))) != hipSuccess ||
-        (e = dev_cache_alloc((void **)&s->d_dropped, (size_t)s->gicp_grid * sizeof(uint32_t))) != hipSuccess)
-      return bail(fail(PCGX_E_OOM, "icp session allocation failed: %s", hipGetErrorString(e)));
-    if ((e = hipMemsetAsync(s->d_dropped, 0, (size_t)s->gicp_grid * sizeof(uint32_t), st)) != hipSuccess)
-      return bail(fail(PCGX_E_HIP, "icp session setup failed: %s", hipGetErrorString(e)));
-    Arena &ar = ctx().arena;
-    if ((rc = ar.begin(st)) != PCGX_OK) return bail(rc);
-    const float *d_c6 = base_cov6;
-    if (!target_on_device) {
-      float *stage = nullptr;
-      if ((rc = ar.alloc_n((size_t)nb * 6, &stage)) != PCGX_OK) return bail(rc);
-      if ((rc = staged_upload(stage, base_cov6, (size_t)nb * 24, st)) != PCGX_OK) return bail(rc);
-      d_c6 = stage;
-    }
-    hipLaunchKernelGGL(pack_base_cov_kernel, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, st, d_c6, nb,
-                       s->d_base_cov);
-    if ((e = hipStreamSynchronize(st)) != hipSuccess)
-      return bail(fail(PCGX_E_HIP, "icp session setup failed: %s", hipGetErrorString(e)));
-  } else if (s->plane) {
-    const int64_t nb = n_base_ids;
-    if ((e = dev_cache_alloc((void **)&s->d_match_id, (size_t)(nt ? nt : 1) * sizeof(uint32_t))) != hipSuccess ||
-        (e = dev_cache_alloc((void **)&s->d_normals, (size_t)nb * sizeof(float4))) != hipSuccess)
-      return bail(fail(PCGX_E_OOM, "icp session allocation failed: %s", hipGetErrorString(e)));
-    Arena &ar = ctx().arena;
-    if ((rc = ar.begin(st)) != PCGX_OK) return bail(rc);
-    const float *d_n3 = normals;
-    if (!target_on_device) {
-      float *stage = nullptr;
-      if ((rc = ar.alloc_n((size_t)nb * 3, &stage)) != PCGX_OK) return bail(rc);
-      if ((rc = staged_upload(stage, normals, (size_t)nb * 12, st)) != PCGX_OK) return bail(rc);
-      d_n3 = stage;
-    }
-    hipLaunchKernelGGL(pack_normals_kernel, dim3((unsigned)((nb + 255) / 256)), dim3(256), 0, st, d_n3, nb,
-                       s->d_normals);
-    if ((e = hipStreamSynchronize(st)) != hipSuccess)
-      return bail(fail(PCGX_E_HIP, "icp session setup failed: %s", hipGetErrorString(e)));
-  }
+  s->general_ready = false;
+
+  pcgx_status rc = session_allocate(s, p, d_sums);
+  if (rc == PCGX_OK) rc = stage_side_inputs(s, normals, base_cov6, target_on_device != 0, st);
   t_phase[1] = trace ? now_us() : 0.0;  // buffers
-  // Small clouds (the reference's own benchmark shapes, icp_test.go:100-142): the whole Fit in one launch
-  // (icp_small.hip), the target in the caller's order -- the sums run in that order.  Such a session's start values,
-  // its words' zeroes and its target's coordinates are ONE launch's work (small_prepare_kernel) behind the upload: a
-  // host-pointer Fit is then upload, that launch, the Fit's, the result -- it was ten operations on the stream, 5 us apart.
-  static const bool small_on = icp_knob("PCGX_ICP_SMALL", 1, 0, 1) != 0;
-  s->small = small_on && nt > 0 && !s->plane && !patched && s->strict == 1 && !base->has_nan && small_fit_eligible(base->view(), nt, base->many_ties);
-  if (s->small) {
-    s->general_ready = false;
-    s->host_iter = 0;
-  } else {
-    if ((rc = reset_state(s, st)) != PCGX_OK) return bail(rc);
-    s->general_ready = false;
-    if ((rc = general_prepare(s, st)) != PCGX_OK) return bail(rc);
-  }
-  if (nt > 0) {
-    Arena &ar = ctx().arena;
-    if ((rc = ar.begin(st)) != PCGX_OK) return bail(rc);
-    const float *d_q = target;
-    bool from_pinned = false;
-    if (!target_on_device && s->small) {  // (a small target: read by small_prepare_kernel out of the context's pinned memory)
-      if (const void *up = small_upload(target, (size_t)nt * 12)) {
-        d_q = static_cast<const float *>(up);
-        from_pinned = true;
-        t_phase[2] = t_phase[3] = trace ? now_us() : 0.0;
-      }
-    }
-    if (!target_on_device && !from_pinned) {
-      float *stage = nullptr;
-      if ((rc = ar.alloc_n((size_t)nt * 3, &stage)) != PCGX_OK) return bail(rc);
-      t_phase[2] = trace ? now_us() : 0.0;  // memsets, arena
-      if ((rc = staged_upload(stage, target, (size_t)nt * 12, st)) != PCGX_OK) return bail(rc);
-      d_q = stage;
-      t_phase[3] = trace ? now_us() : 0.0;  // upload enqueued (pageable memory: staged by the runtime)
-    }
-    if (s->small) {
-      s->nt_pad = (nt + 63) & ~(int64_t)63;
-      if ((e = dev_cache_alloc((void **)&s->d_terms, small_fit_terms_bytes(nt))) != hipSuccess ||
-          (e = dev_cache_alloc((void **)&s->d_valid, (size_t)(s->nt_pad / 64) * sizeof(unsigned long long))) != hipSuccess ||
-          (e = dev_cache_alloc(&s->d_small_sync, small_fit_sync_bytes())) != hipSuccess)
-        return bail(fail(PCGX_E_OOM, "icp session allocation failed: %s", hipGetErrorString(e)));
-      if (small_fit_wants_order(nt) && (e = dev_cache_alloc((void **)&s->d_small_perm, (size_t)nt * sizeof(int32_t))) != hipSuccess)
-        return bail(fail(PCGX_E_OOM, "icp session allocation failed: %s", hipGetErrorString(e)));
-      if ((rc = small_fit_prepare(d_q, nt, base->bbox_lo, base->bbox_hi, s->d_small_perm, s->d_xyz, s->d_pos_of, s->d_state, s->d_terms,
-                                  s->d_small_sync, st)) != PCGX_OK)
-        return bail(rc);
-      if (from_pinned) small_upload_read(st);
-    }
-    int32_t *perm = nullptr;
-    if (nt > 1 && !s->small) {
-      if ((rc = ar.alloc_n((size_t)nt, &perm)) != PCGX_OK) return bail(rc);
-      if ((rc = morton_order(d_q, nt, base->bbox_lo, base->bbox_hi, perm, st)) != PCGX_OK) return bail(rc);
-    }
-    if (!s->small)
-      hipLaunchKernelGGL(gather_soa_kernel, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, st, d_q, perm, nt,
-                         s->d_xyz, s->d_xyz + nt, s->d_xyz + 2 * nt, s->d_pos_of);
-    if (s->gicp) {  // the target's covariances, into the same order
-      const float *d_c6 = target_cov6;
-      if (!target_on_device) {
-        float *stage = nullptr;
-        if ((rc = ar.alloc_n((size_t)nt * 6, &stage)) != PCGX_OK) return bail(rc);
-        if ((rc = staged_upload(stage, target_cov6, (size_t)nt * 24, st)) != PCGX_OK) return bail(rc);
-        d_c6 = stage;
-      }
-      hipLaunchKernelGGL(gather_target_cov_kernel, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, st, d_c6,
-                         (const int32_t *)perm, nt, s->d_target_cov);
-    }
-    t_phase[4] = trace ? now_us() : 0.0;  // order + gather enqueued
-    // No wait here: what follows on this session is enqueued on this stream, behind the gather, or on another stream
-    // through an entry point that names it -- those wait for this one first (touch(): a session's first use on a stream
-    // that is not the one it was made on).  The host's twenty step enqueues (0.3 ms) used to start only when upload,
-    // order and gather had drained (0.25 ms of idle host and, behind it, idle GPU per host-pointer Fit).
-    if ((e = hipGetLastError()) != hipSuccess)
-      return bail(fail(PCGX_E_HIP, "icp session setup failed: %s", hipGetErrorString(e)));
+  if (rc == PCGX_OK && p.start_values) rc = reset_state(s, st);
+  if (rc == PCGX_OK && p.start_values) rc = general_prepare(s, st);
+  if (rc == PCGX_OK && nt > 0) rc = order_target(s, target, target_cov6, target_on_device != 0, st, trace, t_phase);
+  if (rc != PCGX_OK) {
+    pcgx_icp_session_free(s);
+    return rc;
   }
   if (trace)
     fprintf(stderr, "pcgx session trace: buffers %.0f us, memsets + arena %.0f, upload %.0f, order + gather enqueued %.0f\n",
@@ -1241,9 +1228,8 @@ extern "C" pcgx_status pcgx_icp_gicp_session_dropped(pcgx_icp_session *s, void *
   PCGX_API_LOCK();
   if (!s || !n) return fail(PCGX_E_INVALID, "pcgx_icp_gicp_session_dropped: bad argument");
   if (!s->gicp) return fail(PCGX_E_INVALID, "pcgx_icp_gicp_session_dropped: not a GICP session");
-  hipStream_t st = pick_stream(stream);
-  s->touch(st);
-  PCGX_TRY(settle(s, st));
+  hipStream_t st;
+  PCGX_TRY(enter(s, stream, &st));
   std::vector<uint32_t> h((size_t)s->gicp_grid);
   PCGX_HIP_TRY(hipMemcpyAsync(h.data(), s->d_dropped, h.size() * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
   PCGX_HIP_TRY(hipStreamSynchronize(st));
@@ -1279,6 +1265,14 @@ static const StepKnobs &step_knobs() {
   return knobs;
 }
 
+// The strict sums' buffers (strict.hip), made at the session's first strict 1 step and its own from then on
+static pcgx_status ensure_strict_buf(pcgx_icp_session *s, hipStream_t st) {
+  if (s->strict_buf) return PCGX_OK;
+  PCGX_TRY(strict_create(s->nt, s->d_xyz, s->d_xyz + s->nt, s->d_xyz + 2 * s->nt, (const uint32_t *)s->d_pos_of, &s->strict_buf, st));
+  s->owned.adopt(s->strict_buf, [](void *p) { strict_destroy(static_cast<StrictBuffers *>(p)); });
+  return PCGX_OK;
+}
+
 // What the step that begins here launches: the resources it may need (each may fail softly), the session's facts,
 // plan_step().  The one place that writes what a step leaves for the next one.
 static pcgx_status decide_step(pcgx_icp_session *s, hipStream_t st, bool may_speculate, StepPlan *plan) {
@@ -1292,12 +1286,12 @@ static pcgx_status decide_step(pcgx_icp_session *s, hipStream_t st, bool may_spe
   if (!s->patched && s->strict == 1 && !s->plane && s->nt > 0) {
     // the strict sums run in the caller's target order: the correspondence kernels also leave every pair there
     if (!s->d_match_caller) {
-      hipError_t e = dev_cache_alloc((void **)&s->d_orig_of, (size_t)s->nt * sizeof(uint32_t));
-      if (e == hipSuccess) e = dev_cache_alloc((void **)&s->d_match_caller, (size_t)s->nt * sizeof(float4));
+      hipError_t e = session_alloc(s, &s->d_orig_of, (size_t)s->nt * sizeof(uint32_t));
+      if (e == hipSuccess) e = session_alloc(s, &s->d_match_caller, (size_t)s->nt * sizeof(float4));
       if (e != hipSuccess) {  // not required: strict.hip then gathers through pos_of
         (void)hipGetLastError();
-        dev_cache_free(s->d_orig_of);
-        dev_cache_free(s->d_match_caller);
+        s->owned.give_up(s->d_orig_of);
+        s->owned.give_up(s->d_match_caller);
         s->d_orig_of = nullptr;
         s->d_match_caller = nullptr;
       } else {
@@ -1305,9 +1299,7 @@ static pcgx_status decide_step(pcgx_icp_session *s, hipStream_t st, bool may_spe
                            (const uint32_t *)s->d_pos_of, s->nt, s->d_orig_of);
       }
     }
-    if (!s->strict_buf)
-      PCGX_TRY(strict_create(s->nt, s->d_xyz, s->d_xyz + s->nt, s->d_xyz + 2 * s->nt, (const uint32_t *)s->d_pos_of,
-                             &s->strict_buf, st));
+    PCGX_TRY(ensure_strict_buf(s, st));
     f.exchange = strict_work(s->strict_buf, s->kp)->exchange;
   }
   f.patched = s->patched;
@@ -1429,9 +1421,7 @@ static StrictPairs strict_pairs(const pcgx_icp_session *s, bool caller_order) {
 template <bool kFuseUpdate>
 static pcgx_status enqueue_sums(pcgx_icp_session *s, hipStream_t st, const StepPlan &p) {
   if (s->strict == 1) {  // the whole GPU: strict.hip
-    if (!s->strict_buf)
-      PCGX_TRY(strict_create(s->nt, s->d_xyz, s->d_xyz + s->nt, s->d_xyz + 2 * s->nt, (const uint32_t *)s->d_pos_of,
-                             &s->strict_buf, st));
+    PCGX_TRY(ensure_strict_buf(s, st));
     s->host_iter++;
     CertifiedTerms C;
     if (p.certify) {  // the step's correspondence in the summary kernel
@@ -1451,8 +1441,8 @@ static pcgx_status enqueue_sums(pcgx_icp_session *s, hipStream_t st, const StepP
     if (!s->d_terms) {  // first strict launch of the session
       s->nt_pad = (s->nt + 63) & ~(int64_t)63;
       const size_t np = (size_t)(s->nt_pad ? s->nt_pad : 64);
-      PCGX_HIP_TRY(dev_cache_alloc((void **)&s->d_terms, 9 * np * sizeof(float)));
-      PCGX_HIP_TRY(dev_cache_alloc((void **)&s->d_valid, (np / 64) * sizeof(unsigned long long)));
+      PCGX_HIP_TRY(session_alloc(s, &s->d_terms, 9 * np * sizeof(float)));
+      PCGX_HIP_TRY(session_alloc(s, &s->d_valid, (np / 64) * sizeof(unsigned long long)));
     }
     PCGX_TRY(strict_check_enqueue(s->d_xyz, s->nt, s->nt_pad, (const float4 *)s->d_match, (const uint32_t *)s->d_pos_of,
                                   s->d_state, s->kp, s->d_terms, s->d_valid, s->d_sums, kFuseUpdate, st));
@@ -1525,18 +1515,16 @@ extern "C" pcgx_status pcgx_debug_icp_strict_stats(pcgx_icp_session *s, void *st
 extern "C" pcgx_status pcgx_icp_session_partials(pcgx_icp_session *s, void *stream) {
   PCGX_API_LOCK();
   if (!s) return fail(PCGX_E_INVALID, "pcgx_icp_session_partials: NULL session");
-  hipStream_t st = pick_stream(stream);
-  s->touch(st);
-  PCGX_TRY(settle(s, st));  // (steps enqueued without the leftover walk: enqueue_corr)
+  hipStream_t st;
+  PCGX_TRY(enter(s, stream, &st));
   return enqueue_step<false>(s, st, false);
 }
 
 extern "C" pcgx_status pcgx_icp_session_update(pcgx_icp_session *s, void *stream) {
   PCGX_API_LOCK();
   if (!s) return fail(PCGX_E_INVALID, "pcgx_icp_session_update: NULL session");
-  hipStream_t st = pick_stream(stream);
-  s->touch(st);
-  PCGX_TRY(settle(s, st));  // (steps enqueued without the leftover walk: enqueue_corr)
+  hipStream_t st;
+  PCGX_TRY(enter(s, stream, &st));
   if (s->plane)
     hipLaunchKernelGGL(icp_update_kernel<true>, dim3(1), dim3(64), 0, st, s->d_state, s->d_sums, s->kp);
   else
@@ -1605,9 +1593,8 @@ extern "C" pcgx_status pcgx_icp_session_step(pcgx_icp_session *s, void *stream) 
 static pcgx_status step_sharded_impl(pcgx_icp_session *s, pcgx_comm *c, void *stream, pcgx_status *local_rc) {
   int32_t rank = 0, world = 1;
   PCGX_TRY(pcgx_comm_rank(c, &rank, &world));
-  hipStream_t st = pick_stream(stream);
-  s->touch(st);
-  PCGX_TRY(settle(s, st));  // (steps enqueued without the leftover walk: enqueue_corr)
+  hipStream_t st;
+  PCGX_TRY(enter(s, stream, &st));
   const int step = s->steps_sharded++;
   // the first sharded step since the session was made or reset: a Fit begins on the communicator -- whatever an earlier
   // Fit left in the ring's abort words is not this one's business (every rank gets here at the same point of its calls)
@@ -1635,11 +1622,7 @@ static pcgx_status step_sharded_impl(pcgx_icp_session *s, pcgx_comm *c, void *st
         s->shard_failed = true;
       }
     }
-    if (!s->strict_buf) {
-      const pcgx_status rc = strict_create(s->nt, s->d_xyz, s->d_xyz + s->nt, s->d_xyz + 2 * s->nt, (const uint32_t *)s->d_pos_of,
-                                           &s->strict_buf, st);
-      if (rc != PCGX_OK) return rc;  // (no buffers at all: this rank cannot even raise its flag)
-    }
+    PCGX_TRY(ensure_strict_buf(s, st));  // (no buffers at all: this rank cannot even raise its flag)
     // (a rank that failed enqueued no correspondence: what the session last left, as the plan of a step that was made)
     const StrictPairs pairs = strict_pairs(s, s->caller_order_fresh);
     if (have_ring) {
@@ -1652,7 +1635,7 @@ static pcgx_status step_sharded_impl(pcgx_icp_session *s, pcgx_comm *c, void *st
   }
   const int n = s->n_sums();
   if (!s->d_xchg) {
-    if (dev_cache_alloc((void **)&s->d_xchg, (size_t)(n + 2) * sizeof(double)) != hipSuccess)
+    if (session_alloc(s, &s->d_xchg, (size_t)(n + 2) * sizeof(double)) != hipSuccess)
       return fail(PCGX_E_OOM, "pcgx_icp_session_step_sharded: no memory for the exchange");
   }
   PCGX_HIP_TRY(hipMemsetAsync(s->d_xchg, 0, (size_t)(n + 2) * sizeof(double), st));
@@ -1901,9 +1884,8 @@ extern "C" pcgx_status pcgx_icp_session_result(pcgx_icp_session *s, void *stream
                                                pcgx_icp_stat *stat, int32_t *converged) {
   PCGX_API_LOCK();
   if (!s) return fail(PCGX_E_INVALID, "pcgx_icp_session_result: NULL session");
-  hipStream_t st = pick_stream(stream);
-  s->touch(st);
-  PCGX_TRY(settle(s, st));  // (steps enqueued without the leftover walk: enqueue_corr)
+  hipStream_t st;
+  PCGX_TRY(enter(s, stream, &st));
   IcpState h;
   PCGX_TRY(read_back_small(s->d_state, sizeof h, &h, st));  // (the stream is not waited for: a word from behind its last kernel is)
   return result_of(s, h, trans16, stat, converged);
@@ -1934,9 +1916,8 @@ extern "C" pcgx_status pcgx_icp_session_hessian(pcgx_icp_session *s, void *strea
   PCGX_API_LOCK();
   if (!s || !hessian36) return fail(PCGX_E_INVALID, "pcgx_icp_session_hessian: bad argument");
   if (!s->plane) return fail(PCGX_E_INVALID, "pcgx_icp_session_hessian: not a plane session (HasHessian() == false)");
-  hipStream_t st = pick_stream(stream);
-  s->touch(st);
-  PCGX_TRY(settle(s, st));  // (steps enqueued without the leftover walk: enqueue_corr)
+  hipStream_t st;
+  PCGX_TRY(enter(s, stream, &st));
   IcpState h;
   PCGX_HIP_TRY(hipMemcpyAsync(&h, s->d_state, sizeof h, hipMemcpyDeviceToHost, st));
   PCGX_HIP_TRY(hipStreamSynchronize(st));
@@ -2025,7 +2006,6 @@ extern "C" pcgx_status pcgx_icp_fit(const pcgx_kdtree *base, const float *target
   }
   // (PCGX_FIT_TRACE: where a host-pointer Fit's wall time goes, per thread -- tools/conc4_probe.py)
   static const bool trace = getenv("PCGX_FIT_TRACE") != nullptr;
-  auto now_us = []() { return std::chrono::duration<double, std::micro>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
   const double t0 = trace ? now_us() : 0.0;
   pcgx_icp_session *s = nullptr;
   PCGX_TRY(pcgx_icp_session_create(base, target, nt, 0, params, nullptr, &s));
@@ -2112,9 +2092,8 @@ extern "C" pcgx_status pcgx_debug_icp_grid_stats(pcgx_icp_session *s, void *stre
   out[0] = s->nt;
   out[1] = out[2] = out[3] = out[4] = out[5] = 0;
   if (s->patched || !grid_enabled(s->base) || s->kp.min_dist_sq > 0.0f || s->nt == 0) return PCGX_OK;
-  hipStream_t st = pick_stream(stream);
-  s->touch(st);
-  PCGX_TRY(settle(s, st));  // (steps enqueued without the leftover walk: enqueue_corr)
+  hipStream_t st;
+  PCGX_TRY(enter(s, stream, &st));
   PCGX_TRY(general_prepare(s, st));
   unsigned long long *d_trace = nullptr;
   PCGX_HIP_TRY(dev_cache_alloc((void **)&d_trace, 40 * sizeof(unsigned long long)));
