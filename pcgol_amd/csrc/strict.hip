@@ -23,6 +23,7 @@
 #include <stddef.h>
 
 #include "knn_grid.h"
+#include "strict_plan.h"
 #include "strict_terms.h"
 
 namespace pcgx {
@@ -2678,102 +2679,96 @@ __global__ __launch_bounds__(kChainBlock) void strict_chain_kernel(const float4 
 
 // ---- host side ---------------------------------------------------------------------------------------
 struct StrictBuffers {
-  StrictWork w;
+  StrictWork w = {};
+  StrictKnobs knobs;    // the environment as it stood when the buffers were created
+  StrictLayout layout;  // of `block`
   void *block = nullptr;
-  // a target spread over ranks (strict_enqueue_sharded): [world][16] slots of the all-gathers, then row_base[16],
+  // a target spread over ranks (ensure_shard): [world][16] slots of the all-gathers, then row_base[16],
   // err_base[16] ([9] = pairs of all ranks), hop[16], start_bits[16] (uint32)
   double *shard = nullptr;
   int shard_world = 0;
-  bool shard_ring = false;  // `shard` was last laid out (and zeroed) for the ring form
-  void *counters = nullptr;  // slot / ticket counters (strict_reset)
-  size_t counters_bytes = 0, arrived_bytes = 0;
+  bool shard_ring = false;      // `shard` was last laid out (and zeroed) for the ring form
+  std::vector<void *> retired;  // the shard blocks of earlier worlds: enqueued kernels may still use them (strict_destroy)
+  uint8_t *at(int region) const { return (uint8_t *)block + layout.region[region].offset; }
 };
+
+constexpr StrictFacts kFacts;
+static_assert(kFacts.rows == kStrictRows && kFacts.tile == kTile && kFacts.lanes == kLanes && kFacts.chain_tiles == kChainTiles &&
+                  kFacts.aux_shards == kAuxShards && kFacts.cand == kCand && kFacts.repair_block == kRepairBlock &&
+                  kFacts.repair_min_tiles == kRepairMinTiles && kFacts.job_roles == kJobRoles && kFacts.tile_rec == sizeof(TileRec) &&
+                  kFacts.leaf_aux == sizeof(LeafAux) && kFacts.job_desc == sizeof(JobDesc),
+              "strict_plan.h plans with the kernels' constants");
+
+// What the environment says, read when a session's buffers are created (the tests change it between the sessions of one
+// process); PCGX_STRICT_REPAIR and PCGX_STRICT_SPEC once per process.
+static StrictKnobs strict_knobs() {
+  const auto num = [](const char *name, int absent) {
+    const char *e = getenv(name);
+    return e ? atoi(e) : absent;
+  };
+  static const bool repair_on = num("PCGX_STRICT_REPAIR", 1) != 0, spec_on = num("PCGX_STRICT_SPEC", 1) != 0;
+  StrictKnobs k;
+  k.spec_depth = num("PCGX_STRICT_SPEC_DEPTH", 4);
+  k.selfcheck = (getenv("PCGX_STRICT_SELFCHECK") ? 1 : 0) | (getenv("PCGX_STRICT_TRACE") ? 2 : 0) |
+                (getenv("PCGX_STRICT_NOSPEC") ? 4 : 0) | (getenv("PCGX_STRICT_CLOCKS") ? 8 : 0) | (getenv("PCGX_TEST_SPEC_MISS") ? 16 : 0);
+  k.exchange = num("PCGX_STRICT_EXCHANGE", 1) != 0 ? 1 : 0;
+  k.slots_per_shard = num("PCGX_STRICT_SLOTS_PER_SHARD", -1);
+  k.repair_on = repair_on;
+  k.spec_on = spec_on;
+  return k;
+}
+
+static hipError_t zero_runs(const StrictBuffers *b, const StrictLayout::Run *runs, int n, hipStream_t st) {
+  hipError_t e = hipSuccess;
+  for (int i = 0; i < n && e == hipSuccess; i++) {
+    const StrictLayout::Span s = b->layout.span(runs[i]);
+    e = hipMemsetAsync((uint8_t *)b->block + s.offset, 0, s.bytes, st);
+  }
+  return e;
+}
 
 pcgx_status strict_create(int64_t nt, const float *tx, const float *ty, const float *tz, const uint32_t *pos_of,
                           StrictBuffers **out, hipStream_t st) {
   StrictBuffers *b = new StrictBuffers();
-  StrictWork &W = b->w;
-  W.nt = nt;
-  W.raw_terms = nullptr;
-  W.row_base = W.err_base = nullptr;
-  W.start_bits = nullptr;
-  W.hop_out = nullptr;
-  W.first_exact = 1;
-  W.ring = nullptr;
-  W.ring_words = 0;
-  W.ring_tab = nullptr;
-  W.ring_mine = nullptr;
-  W.ring_guess_ticks = kRingGuessTicks;
-  W.rank = 0;
-  W.world = 1;
-  W.ring_epoch = 0u;
-  W.ring_base = nullptr;
-  W.ring_flag = nullptr;
-  W.ntiles = nt > 0 ? (nt + kTile - 1) / kTile : 1;
-  W.nrows = kStrictRows;
-  W.spec_depth = getenv("PCGX_STRICT_SPEC_DEPTH") ? atoi(getenv("PCGX_STRICT_SPEC_DEPTH")) : 4;
-  W.selfcheck = (getenv("PCGX_STRICT_SELFCHECK") ? 1 : 0) | (getenv("PCGX_STRICT_TRACE") ? 2 : 0) |
-                (getenv("PCGX_STRICT_NOSPEC") ? 4 : 0) | (getenv("PCGX_STRICT_CLOCKS") ? 8 : 0) | (getenv("PCGX_TEST_SPEC_MISS") ? 16 : 0);
-  // (4: the chain kernel ignores the candidate tables of tiles without a window; 8: tick columns of the debug counters)
-  auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
-  const size_t sz_tile = up((size_t)kStrictRows * W.ntiles * sizeof(double));  // (twice: sums and errors)
-  const size_t sz_pairs = up((size_t)W.ntiles * sizeof(uint32_t));
-  W.ntiles_pad = (W.ntiles + 127) & ~(int64_t)127;
-  const size_t sz_pub = up((size_t)W.ntiles_pad * 16 * sizeof(double));
-  const int64_t n_groups = (W.ntiles + 31) / 32;
-  const size_t sz_arr = up((size_t)(n_groups + (n_groups + 31) / 32) * 128);
-  // (PCGX_STRICT_EXCHANGE=0: the tile sums are formed by a pass of their own in front of the summaries, as in round 3)
-  W.exchange = (getenv("PCGX_STRICT_EXCHANGE") && atoi(getenv("PCGX_STRICT_EXCHANGE")) == 0) ? 0 : 1;
-  const size_t sz_rec = up((size_t)kStrictRows * W.ntiles * sizeof(TileRec));
-  // slots for the tiles that cross a level or have no window (6 KB of leaf records + 8 KB of terms each):
-  // a quarter of all tiles, far more than ever seen (C4: ~2 %; a sum hovering around zero over the whole
-  // row: ~15 %); a tile that finds none left is recomputed from the pairs by the chain kernel
-  W.naux = (int32_t)(kAuxShards * ((kStrictRows * W.ntiles / 4 + kAuxShards - 1) / kAuxShards + 4));
-  if (const char *e = getenv("PCGX_STRICT_SLOTS_PER_SHARD")) {  // tests: run out of slots (tiles then take the chain kernel's
-    const int per = atoi(e);                                    // recompute-from-the-pairs path)
-    if (per >= 0 && per * kAuxShards < W.naux) W.naux = per * kAuxShards;
-  }
-  const size_t sz_aux = up((size_t)W.naux * kLanes * sizeof(LeafAux));
-  const size_t sz_auxt = up((size_t)W.naux * kTile * sizeof(float));
-  const size_t sz_jobs = up((size_t)W.naux * sizeof(JobDesc));
-  const size_t sz_cand = up((size_t)W.naux * kCand * sizeof(uint32_t));
-  const size_t sz_xyz = up((size_t)(nt ? nt : 1) * 12 + 64);
-  const size_t sz_stamps = up((size_t)W.ntiles * 16 * sizeof(unsigned long long));
-  const size_t sz_ctr = 256 + (size_t)kAuxShards * 128;
-  W.nchunks = (int32_t)((W.ntiles + kChainTiles - 1) / kChainTiles);
-  W.epoch = 0u;
-  const size_t sz_chunk = up((size_t)kStrictRows * W.nchunks * 16 * sizeof(unsigned long long));
-  const size_t total = 2 * sz_tile + sz_pub + sz_arr + sz_pairs + sz_rec + sz_aux + sz_auxt + sz_jobs + sz_cand + sz_xyz + sz_ctr + 512 + sz_stamps + sz_chunk;
-  hipError_t e = dev_cache_alloc(&b->block, total);
+  b->knobs = strict_knobs();
+  b->layout = plan_strict_layout(nt, b->knobs, kFacts);
+  const StrictLayout &L = b->layout;
+  hipError_t e = dev_cache_alloc(&b->block, L.total);
   if (e != hipSuccess) {
+    const size_t total = L.total;
     delete b;
     return fail(PCGX_E_OOM, "strict sums: allocation of %zu bytes failed: %s", total, hipGetErrorString(e));
   }
-  uint8_t *p = (uint8_t *)b->block;
-  W.tile_sum = (double *)p; p += sz_tile;
-  W.tile_err = (double *)p; p += sz_tile;
-  W.tile_pub = (double *)p; p += sz_pub;  // (256-byte aligned: a tile's line is one 128-byte line)
-  W.tile_arrived = (unsigned int *)p; p += sz_arr;
-  W.tile_pairs = (uint32_t *)p; p += sz_pairs;
-  W.recs = (TileRec *)p; p += sz_rec;
-  W.aux = (LeafAux *)p; p += sz_aux;
-  W.aux_terms = (float4 *)p; p += sz_auxt;
-  W.jobs = (JobDesc *)p; p += sz_jobs;
-  W.cand = (uint32_t *)p; p += sz_cand;
-  W.xyz_caller = (const float *)p; p += sz_xyz;
-  uint8_t *counters = p;
-  b->counters = counters;
-  b->counters_bytes = sz_ctr;
-  b->arrived_bytes = sz_arr;
-  W.done_rows = (unsigned int *)(p + 12);
-  W.aux_count = (unsigned int *)(p + 256); p += sz_ctr;
-  W.dbg = (unsigned long long *)p; p += 512;
-  W.stamps = (unsigned long long *)p; p += sz_stamps;
-  W.chunk_state = (unsigned long long *)p;
-  // slot / ticket counters and debug counters start at zero (the chain kernel re-zeroes what it consumed)
-  e = hipMemsetAsync(counters, 0, sz_ctr + 512, st);
-  if (e == hipSuccess) e = hipMemsetAsync(W.tile_arrived, 0, sz_arr, st);
-  if (e == hipSuccess) e = hipMemsetAsync(W.chunk_state, 0, sz_chunk, st);  // (epoch 0: no launch's)
+  StrictWork &W = b->w;  // (all zero: one GPU, no raw terms, epoch 0)
+  W.nt = nt;
+  W.first_exact = 1;
+  W.ring_guess_ticks = kRingGuessTicks;
+  W.world = 1;
+  W.ntiles = L.ntiles;
+  W.ntiles_pad = L.ntiles_pad;
+  W.nchunks = L.nchunks;
+  W.naux = L.naux;
+  W.nrows = kStrictRows;
+  W.spec_depth = b->knobs.spec_depth;
+  W.selfcheck = b->knobs.selfcheck;
+  W.exchange = b->knobs.exchange;
+  W.tile_sum = (double *)b->at(kRegTileSum);
+  W.tile_err = (double *)b->at(kRegTileErr);
+  W.tile_pub = (double *)b->at(kRegTilePub);
+  W.tile_arrived = (unsigned int *)b->at(kRegTileArrived);
+  W.tile_pairs = (uint32_t *)b->at(kRegTilePairs);
+  W.recs = (TileRec *)b->at(kRegRecs);
+  W.aux = (LeafAux *)b->at(kRegAux);
+  W.aux_terms = (float4 *)b->at(kRegAuxTerms);
+  W.jobs = (JobDesc *)b->at(kRegJobs);
+  W.cand = (uint32_t *)b->at(kRegCand);
+  W.xyz_caller = (const float *)b->at(kRegXyzCaller);
+  W.done_rows = (unsigned int *)(b->at(kRegCounters) + kDoneRowsAt);
+  W.aux_count = (unsigned int *)(b->at(kRegCounters) + kAuxCountAt);
+  W.dbg = (unsigned long long *)b->at(kRegDbg);
+  W.stamps = (unsigned long long *)b->at(kRegStamps);
+  W.chunk_state = (unsigned long long *)b->at(kRegChunkState);
+  e = zero_runs(b, L.zero_create, 3, st);
   if (e == hipSuccess && nt > 0) {
     hipLaunchKernelGGL(strict_xyz_caller_kernel, dim3((unsigned)((nt + 255) / 256)), dim3(256), 0, st, tx, ty, tz, pos_of, nt,
                        const_cast<float *>(W.xyz_caller));
@@ -2788,9 +2783,11 @@ pcgx_status strict_create(int64_t nt, const float *tx, const float *ty, const fl
   return PCGX_OK;
 }
 
+// (its caller has waited for the stream the buffers' kernels were enqueued on)
 void strict_destroy(StrictBuffers *b) {
   if (!b) return;
   dev_cache_free(b->shard);
+  for (void *p : b->retired) dev_cache_free(p);
   dev_cache_free(b->block);
   delete b;
 }
@@ -2802,73 +2799,91 @@ const StrictWork *strict_work(StrictBuffers *b, const IcpKernelParams &kp) {
   b->w.nrows = kp.weight_fn == PCGX_WEIGHT_ONE ? kStrictRows - 1 : kStrictRows;
   return &b->w;
 }
-// (PCGX_STRICT_REPAIR=0: no repair pass in a Fit's first Evaluate -- measurement)
-static bool repair_enabled() {
-  static const bool on = !(getenv("PCGX_STRICT_REPAIR") && atoi(getenv("PCGX_STRICT_REPAIR")) == 0);
-  return on;
-}
 // a launch of the chain kernel: its epoch (the chunks' hand-over words, StrictWork::chunk_state)
 static const StrictWork &next_epoch(StrictBuffers *b) {
   if (++b->w.epoch == 0u) b->w.epoch = 1u;  // (a wrap after 2^32 launches: stale words are 2^32 launches old by then)
   return b->w;
 }
 
-// (PCGX_STRICT_SPEC=0: no walk ahead of a wait -- measurement)
-static bool spec_enabled() {
-  static const bool on = !(getenv("PCGX_STRICT_SPEC") && atoi(getenv("PCGX_STRICT_SPEC")) == 0);
-  return on;
+// ---- a step: what plan_strict_launches says, enqueued ------------------------------------------------------------------
+struct StepArgs {
+  const float4 *match;
+  const uint32_t *pos_of;
+  IcpState *state;
+  double *sums10;
+  const IcpKernelParams &kp;
+  hipStream_t st;
+  const CertifiedTerms *certify = nullptr;
+};
+// this step's descriptor (strict_work) as the plan sees it; the caller adds what it knows of the step
+static StrictStep step_of(StrictBuffers *b, const IcpKernelParams &kp) {
+  const StrictWork &W = *strict_work(b, kp);
+  StrictStep s;
+  s.ntiles = W.ntiles;
+  s.nchunks = W.nchunks;
+  s.naux = W.naux;
+  s.nrows = W.nrows;
+  return s;
 }
-// the chain kernel of a step; spec: some walker of the launch waits for its start state (several chunks, a rank behind
-// another) -- the instantiation whose walkers walk ahead of that wait.  One chunk on one GPU: the kernel without that code.
-static void launch_chain(const StrictWork &W, const float4 *match, const uint32_t *pos_of, IcpState *state, double *sums10,
-                         const IcpKernelParams &kp, int fuse_update, bool waits, hipStream_t st) {
-  const dim3 grid((unsigned)(W.nrows * W.nchunks)), block(kChainBlock);
-  if (W.selfcheck & 1)
-    hipLaunchKernelGGL((strict_chain_kernel<true, false>), grid, block, 0, st, match, pos_of, state, W, sums10, kp, fuse_update);
-  else if (waits && spec_enabled() && (W.ring ? W.rank : 0) * W.nchunks + W.nchunks - 1 >= W.spec_depth)  // (some walker of THIS launch walks ahead:
-    // the instantiation with that code spills thirty scalar registers more, which the real walk pays for -- 0.7 us a step)
-    hipLaunchKernelGGL((strict_chain_kernel<false, true>), grid, block, 0, st, match, pos_of, state, W, sums10, kp, fuse_update);
-  else
-    hipLaunchKernelGGL((strict_chain_kernel<false, false>), grid, block, 0, st, match, pos_of, state, W, sums10, kp, fuse_update);
+static void launch_tilesum(const StrictWork &W, const StepArgs &a) {
+  hipLaunchKernelGGL(strict_tilesum_kernel, dim3((unsigned)W.ntiles), dim3(kTileSumBlock), 0, a.st, a.match, a.pos_of,
+                     (const IcpState *)a.state, W);
+}
+enum : unsigned { kStageSummary = 1, kStageJobs = 2, kStageChain = 4 };
+// the stages `stages` of a step as L says, each in its ProfScope; W as the form has made it by then
+static pcgx_status enqueue_stages(unsigned stages, const StrictLaunches &L, const StrictWork &W, const StepArgs &a) {
+  if (!L.live) return PCGX_OK;
+  const IcpState *state = a.state;
+  if ((stages & kStageSummary) && L.summary != kSumNone) {
+    ProfScope prof(PCGX_PROF_STRICT_SUM, a.st);
+    const dim3 grid((unsigned)W.ntiles), block(kSumBlock);
+    if (L.summary == kSumPlain)
+      hipLaunchKernelGGL(strict_sum_kernel<false>, grid, block, 0, a.st, a.match, a.pos_of, state, W);
+    else if (L.summary == kSumExchange)
+      hipLaunchKernelGGL(strict_sum_kernel<true>, grid, block, 0, a.st, a.match, a.pos_of, state, W);
+    else if (L.summary == kSumRing)
+      hipLaunchKernelGGL((strict_sum_kernel<true, true>), grid, block, 0, a.st, a.match, a.pos_of, state, W);
+    else if (L.summary == kSumCertified)
+      hipLaunchKernelGGL((strict_sum_kernel<true, false, true>), grid, block, 0, a.st, a.match, a.pos_of, state, W, *a.certify);
+    else
+      return fail(PCGX_E_INVALID, "strict sums: the certified terms need the exchange and the pairs in the caller's order");
+  }
+  if (stages & kStageJobs) {
+    ProfScope prof(PCGX_PROF_STRICT_JOB, a.st);
+    if (L.repair_grid)
+      hipLaunchKernelGGL(strict_repair_kernel, dim3(L.repair_grid), dim3(kRepairBlock), 0, a.st, a.match, a.pos_of, state, W);
+    if (L.jobs_grid) hipLaunchKernelGGL(strict_job_kernel, dim3(L.jobs_grid), dim3(kJobBlock), 0, a.st, state, W);
+  }
+  if ((stages & kStageChain) && L.chain != kChainNone) {
+    ProfScope prof(PCGX_PROF_STRICT_CHAIN, a.st);
+    const dim3 grid(L.chain_grid), block(kChainBlock);
+    if (L.chain == kChainCheck)
+      hipLaunchKernelGGL((strict_chain_kernel<true, false>), grid, block, 0, a.st, a.match, a.pos_of, a.state, W, a.sums10, a.kp, L.fuse_update);
+    else if (L.chain == kChainSpec)
+      hipLaunchKernelGGL((strict_chain_kernel<false, true>), grid, block, 0, a.st, a.match, a.pos_of, a.state, W, a.sums10, a.kp, L.fuse_update);
+    else
+      hipLaunchKernelGGL((strict_chain_kernel<false, false>), grid, block, 0, a.st, a.match, a.pos_of, a.state, W, a.sums10, a.kp, L.fuse_update);
+  }
+  return PCGX_OK;
 }
 
 pcgx_status strict_enqueue(StrictBuffers *b, const float4 *match, const uint32_t *pos_of, IcpState *state,
                            double *sums10, const IcpKernelParams &kp, bool fuse_update, bool have_tile_sums, bool first_iter,
                            hipStream_t st, const CertifiedTerms *certify) {
-  (void)strict_work(b, kp);
+  StrictStep s = step_of(b, kp);
+  s.have_tile_sums = have_tile_sums;
+  s.first_iter = first_iter;
+  s.certify = certify != nullptr;
+  s.caller_order = pos_of == nullptr;
+  s.fuse_update = fuse_update;
+  const StrictLaunches L = plan_strict_launches(kOneGpu, s, b->knobs, kFacts);
   const StrictWork &W = next_epoch(b);
-  if (!have_tile_sums && !W.exchange) {
+  const StepArgs a{match, pos_of, state, sums10, kp, st, certify};
+  if (L.tilesum) {
     ProfScope prof(PCGX_PROF_STRICT_TERMS, st);
-    hipLaunchKernelGGL(strict_tilesum_kernel, dim3((unsigned)W.ntiles), dim3(kTileSumBlock), 0, st, match, pos_of,
-                       (const IcpState *)state, W);
+    launch_tilesum(W, a);
   }
-  {
-    ProfScope prof(PCGX_PROF_STRICT_SUM, st);
-    if (certify && W.exchange && !pos_of)  // (the step's correspondence as well: no grid pass in front, icp.hip)
-      hipLaunchKernelGGL((strict_sum_kernel<true, false, true>), dim3((unsigned)W.ntiles), dim3(kSumBlock), 0, st, match,
-                         pos_of, (const IcpState *)state, W, *certify);
-    else if (certify)
-      return fail(PCGX_E_INVALID, "strict sums: the certified terms need the exchange and the pairs in the caller's order");
-    else if (W.exchange)
-      hipLaunchKernelGGL(strict_sum_kernel<true>, dim3((unsigned)W.ntiles), dim3(kSumBlock), 0, st, match, pos_of,
-                         (const IcpState *)state, W);
-    else
-      hipLaunchKernelGGL(strict_sum_kernel<false>, dim3((unsigned)W.ntiles), dim3(kSumBlock), 0, st, match, pos_of,
-                         (const IcpState *)state, W);
-  }
-  {
-    ProfScope prof(PCGX_PROF_STRICT_JOB, st);
-    // (the first Evaluate of a Fit: the plain tiles the rows' drift has carried across a binade's end become jobs)
-    if (first_iter && W.naux > 0 && W.ntiles >= kRepairMinTiles && repair_enabled())
-      hipLaunchKernelGGL(strict_repair_kernel, dim3((unsigned)(W.nrows * ((W.ntiles + kRepairBlock - 1) / kRepairBlock))), dim3(kRepairBlock), 0,
-                         st, match, pos_of, (const IcpState *)state, W);
-    if (W.naux > 0)
-      hipLaunchKernelGGL(strict_job_kernel, dim3((unsigned)kJobRoles * (unsigned)W.naux), dim3(kJobBlock), 0, st, (const IcpState *)state, W);
-  }
-  {
-    ProfScope prof(PCGX_PROF_STRICT_CHAIN, st);
-    launch_chain(W, match, pos_of, state, sums10, kp, fuse_update ? 1 : 0, W.nchunks > 1, st);
-  }
+  PCGX_TRY(enqueue_stages(kStageSummary | kStageJobs | kStageChain, L, W, a));
   PCGX_HIP_TRY(hipGetLastError());
   return PCGX_OK;
 }
@@ -2940,19 +2955,34 @@ __global__ void strict_finish_kernel(const uint32_t *__restrict__ end_bits, cons
   icp_update_step(state, sums, kp);
 }
 
-pcgx_status strict_enqueue_sharded(StrictBuffers *b, const float4 *match, const uint32_t *pos_of, IcpState *state, double *sums10,
-                                   const IcpKernelParams &kp, pcgx_comm *c, int rank, int world, bool local_failed, hipStream_t st) {
-  if (!b->shard || b->shard_world != world) {
-    dev_cache_free(b->shard);
+// The block the sharded forms exchange through (plan_shard).  A block for another world replaces the one there is, which
+// kernels already enqueued on the session's stream may still use: it is kept until strict_destroy, not handed back to
+// the cache ((world + 4) * 128 bytes, and a session changes its world a handful of times at most).
+static pcgx_status ensure_shard(StrictBuffers *b, int world, bool want_ring, hipStream_t st) {
+  const ShardPlan p = plan_shard(b->shard != nullptr, b->shard_world, b->shard_ring, world, want_ring);
+  if (p.allocate) {
+    if (b->shard) b->retired.push_back(b->shard);
     b->shard = nullptr;
-    if (dev_cache_alloc((void **)&b->shard, (size_t)(world + 4) * 16 * sizeof(double)) != hipSuccess)
+    if (dev_cache_alloc((void **)&b->shard, p.bytes) != hipSuccess)
       return fail(PCGX_E_OOM, "strict sums over ranks: no memory for the exchange");
     b->shard_world = world;
   }
-  b->shard_ring = false;
+  if (p.zero) PCGX_HIP_TRY(hipMemsetAsync(b->shard, 0, p.bytes, st));
+  b->shard_ring = p.ring;
+  return PCGX_OK;
+}
+
+pcgx_status strict_enqueue_sharded(StrictBuffers *b, const float4 *match, const uint32_t *pos_of, IcpState *state, double *sums10,
+                                   const IcpKernelParams &kp, pcgx_comm *c, int rank, int world, bool local_failed, hipStream_t st) {
+  PCGX_TRY(ensure_shard(b, world, false, st));
   double *slots = b->shard, *row_base = slots + (size_t)world * 16, *err_base = row_base + 16, *hop = row_base + 32;
   uint32_t *start_bits = reinterpret_cast<uint32_t *>(hop + 16);
-  (void)strict_work(b, kp);
+  StrictStep s = step_of(b, kp);
+  s.rank = rank;
+  s.world = world;
+  s.local_failed = local_failed;
+  const StrictLaunches L = plan_strict_launches(kCollective, s, b->knobs, kFacts);
+  const StepArgs a{match, pos_of, state, sums10, kp, st};
   StrictWork W = next_epoch(b);  // (the session's descriptor stays in its one-GPU form)
   W.row_base = row_base;
   W.err_base = err_base;
@@ -2972,40 +3002,28 @@ pcgx_status strict_enqueue_sharded(StrictBuffers *b, const float4 *match, const 
   const int nslots = world * 16;
   // 1. the float64 totals of this rank's terms -> everybody -> the totals of the ranks before this one
   PCGX_HIP_TRY(hipMemsetAsync(slots, 0, (size_t)nslots * sizeof(double), st));
-  if (!local_failed) {
+  if (L.live) {
     ProfScope prof(PCGX_PROF_STRICT_TERMS, st);
-    hipLaunchKernelGGL(strict_tilesum_kernel, dim3((unsigned)W.ntiles), dim3(kTileSumBlock), 0, st, match, pos_of,
-                       (const IcpState *)state, W);
+    if (L.tilesum) launch_tilesum(W, a);
     hipLaunchKernelGGL(strict_row_totals_kernel, dim3(kStrictRows), dim3(64), 0, st, (const double *)W.tile_sum,
                        (const uint32_t *)nullptr, W.ntiles, W.nrows, (const IcpState *)state, slots + (size_t)rank * 16);
   }
   PCGX_TRY(exchange(slots, nslots, rank * 16 + 10));
-  if (!local_failed) {
-    hipLaunchKernelGGL(strict_base_kernel, dim3(1), dim3(64), 0, st, (const double *)slots, rank, world, row_base);
-    ProfScope prof(PCGX_PROF_STRICT_SUM, st);
-    hipLaunchKernelGGL(strict_sum_kernel<false>, dim3((unsigned)W.ntiles), dim3(kSumBlock), 0, st, match, pos_of,
-                       (const IcpState *)state, W);
-  }
+  if (L.live) hipLaunchKernelGGL(strict_base_kernel, dim3(1), dim3(64), 0, st, (const double *)slots, rank, world, row_base);
+  PCGX_TRY(enqueue_stages(kStageSummary, L, W, a));
   // 2. the chains' rounding errors and the pair counts -> everybody
   PCGX_HIP_TRY(hipMemsetAsync(slots, 0, (size_t)nslots * sizeof(double), st));
-  if (!local_failed)
+  if (L.live)
     hipLaunchKernelGGL(strict_row_totals_kernel, dim3(kStrictRows + 1), dim3(64), 0, st, (const double *)W.tile_err,
                        (const uint32_t *)W.tile_pairs, W.ntiles, W.nrows, (const IcpState *)state, slots + (size_t)rank * 16);
   PCGX_TRY(exchange(slots, nslots, rank * 16 + 10));
   hipLaunchKernelGGL(strict_base_kernel, dim3(1), dim3(64), 0, st, (const double *)slots, rank, world, err_base);
-  if (!local_failed) {
-    ProfScope prof(PCGX_PROF_STRICT_JOB, st);
-    if (W.naux > 0)
-      hipLaunchKernelGGL(strict_job_kernel, dim3((unsigned)kJobRoles * (unsigned)W.naux), dim3(kJobBlock), 0, st, (const IcpState *)state, W);
-  }
+  PCGX_TRY(enqueue_stages(kStageJobs, L, W, a));
   // 3. the walk goes round the ranks: every hop hands on nine states (their bits as float64: exact under the sum)
   hipLaunchKernelGGL(strict_zero_kernel, dim3(1), dim3(64), 0, st, reinterpret_cast<double *>(start_bits), 8, 0.0);  // 16 x 0.0f
   for (int k = 0; k < world; k++) {
     hipLaunchKernelGGL(strict_zero_kernel, dim3(1), dim3(64), 0, st, hop, 16, 0.0);
-    if (k == rank && !local_failed) {
-      ProfScope prof(PCGX_PROF_STRICT_CHAIN, st);
-      launch_chain(W, match, pos_of, state, sums10, kp, 0, W.nchunks > 1, st);
-    }
+    if (k == rank) PCGX_TRY(enqueue_stages(kStageChain, L, W, a));
     PCGX_TRY(exchange(hop, 16, 10));
     hipLaunchKernelGGL(strict_hop_kernel, dim3(1), dim3(64), 0, st, (const double *)hop, start_bits);
   }
@@ -3061,27 +3079,21 @@ __global__ void strict_ring_fail_kernel(IcpState *__restrict__ state) {
 
 pcgx_status strict_enqueue_ring(StrictBuffers *b, const float4 *match, const uint32_t *pos_of, IcpState *state, double *sums10,
                                 const IcpKernelParams &kp, const RingView &ring, bool local_failed, bool first_iter, hipStream_t st) {
-  // (the ring form keeps 32 doubles + a flag word of it; a block the collective form used holds that form's doubles
-  // where the flag word lies -- one equal to this step's number would let tiles read ring_base before tile 0 wrote it)
-  if (!b->shard || b->shard_world != ring.world || !b->shard_ring) {
-    if (!b->shard || b->shard_world != ring.world) {
-      dev_cache_free(b->shard);
-      b->shard = nullptr;
-      if (dev_cache_alloc((void **)&b->shard, (size_t)(ring.world + 4) * 16 * sizeof(double)) != hipSuccess)
-        return fail(PCGX_E_OOM, "strict sums over ranks: no memory for the exchange");
-      b->shard_world = ring.world;
-    }
-    PCGX_HIP_TRY(hipMemsetAsync(b->shard, 0, (size_t)(ring.world + 4) * 16 * sizeof(double), st));
-    b->shard_ring = true;
-  }
-  if (local_failed) {
+  PCGX_TRY(ensure_shard(b, ring.world, true, st));
+  StrictStep s = step_of(b, kp);
+  s.rank = ring.rank;
+  s.world = ring.world;
+  s.first_iter = first_iter;
+  s.local_failed = local_failed;
+  const StrictLaunches L = plan_strict_launches(kRing, s, b->knobs, kFacts);
+  if (!L.live) {
     // this rank launches nothing more: the others learn of it from the abort word, in whatever wait they are in
     ring_abort_from_host(ring, 1u);
     hipLaunchKernelGGL(strict_ring_fail_kernel, dim3(1), dim3(64), 0, st, state);
     PCGX_HIP_TRY(hipGetLastError());
     return PCGX_OK;
   }
-  (void)strict_work(b, kp);
+  const StepArgs a{match, pos_of, state, sums10, kp, st};
   StrictWork W = next_epoch(b);  // (the session's descriptor stays in its one-GPU form)
   W.ring = ring.words;
   W.ring_words = ring.words_per_rank;
@@ -3094,48 +3106,31 @@ pcgx_status strict_enqueue_ring(StrictBuffers *b, const float4 *match, const uin
   W.ring_base = b->shard;
   W.ring_flag = reinterpret_cast<unsigned int *>(b->shard + 32);
   W.first_exact = ring.rank == 0 ? 1 : 0;
-  W.exchange = 1;  // (the ring form rides on the summary kernel's own exchange)
-  {
-    ProfScope prof(PCGX_PROF_STRICT_SUM, st);
-    hipLaunchKernelGGL((strict_sum_kernel<true, true>), dim3((unsigned)W.ntiles), dim3(kSumBlock), 0, st, match, pos_of,
-                       (const IcpState *)state, W);
-  }
-  if (ring.world > 1)
-    hipLaunchKernelGGL(strict_ring_err_kernel, dim3(kStrictRows + (ring.rank > 0 ? 1 : 0)), dim3(64), 0, st, (const IcpState *)state, W);
-  if (ring.rank > 0) {  // (the job tiles' guesses: + the ranks before this one)
+  W.exchange = L.exchange;
+  PCGX_TRY(enqueue_stages(kStageSummary, L, W, a));
+  if (L.ring_err_grid) hipLaunchKernelGGL(strict_ring_err_kernel, dim3(L.ring_err_grid), dim3(64), 0, st, (const IcpState *)state, W);
+  if (L.bases_behind_summary) {  // (the job tiles' guesses: + the ranks before this one)
     W.row_base = W.ring_base;
     W.err_base = W.ring_base + 16;
   }
-  {
-    ProfScope prof(PCGX_PROF_STRICT_JOB, st);
-    if (first_iter && W.naux > 0 && W.ntiles >= kRepairMinTiles && repair_enabled())
-      hipLaunchKernelGGL(strict_repair_kernel, dim3((unsigned)(W.nrows * ((W.ntiles + kRepairBlock - 1) / kRepairBlock))), dim3(kRepairBlock), 0,
-                         st, match, pos_of, (const IcpState *)state, W);
-    if (W.naux > 0)
-      hipLaunchKernelGGL(strict_job_kernel, dim3((unsigned)kJobRoles * (unsigned)W.naux), dim3(kJobBlock), 0, st, (const IcpState *)state, W);
-  }
-  {
-    ProfScope prof(PCGX_PROF_STRICT_CHAIN, st);
-    launch_chain(W, match, pos_of, state, sums10, kp, 1, true, st);
-  }
+  PCGX_TRY(enqueue_stages(kStageJobs | kStageChain, L, W, a));
   PCGX_HIP_TRY(hipGetLastError());
   return PCGX_OK;
 }
 
-// a session between two Fits: whatever a launch that ended early (a broken ring) left in the counters
+// a session between two Fits (StrictLayout::zero_reset)
 pcgx_status strict_reset(StrictBuffers *b, hipStream_t st) {
-  if (!b) return PCGX_OK;
-  PCGX_HIP_TRY(hipMemsetAsync(b->counters, 0, b->counters_bytes, st));
-  PCGX_HIP_TRY(hipMemsetAsync(b->w.tile_arrived, 0, b->arrived_bytes, st));
+  if (b) PCGX_HIP_TRY(zero_runs(b, b->layout.zero_reset, 2, st));
   return PCGX_OK;
 }
 
 // what strict_reset zeroes, for a caller that has a kernel of its own in front of the next Fit (icp.hip, reset_state)
 void strict_reset_ranges(StrictBuffers *b, void *ptr[2], size_t bytes[2]) {
-  ptr[0] = b ? b->counters : nullptr;
-  bytes[0] = b ? b->counters_bytes : 0;
-  ptr[1] = b ? (void *)b->w.tile_arrived : nullptr;
-  bytes[1] = b ? b->arrived_bytes : 0;
+  for (int i = 0; i < 2; i++) {
+    const StrictLayout::Span s = b ? b->layout.span(b->layout.zero_reset[i]) : StrictLayout::Span{0, 0};
+    ptr[i] = b ? (uint8_t *)b->block + s.offset : nullptr;
+    bytes[i] = s.bytes;
+  }
 }
 
 pcgx_status strict_read_debug(StrictBuffers *b, unsigned long long out[64], hipStream_t st) {
@@ -3182,40 +3177,29 @@ extern "C" pcgx_status pcgx_debug_strict_sum_dev(const float *terms, int64_t n, 
   if (n > 0x7fffffffll) return fail(PCGX_E_TOO_LARGE, "pcgx_debug_strict_sum_dev: more than 2^31-1 terms per row");
   PCGX_TRY(ensure_init());
   hipStream_t st = ctx().stream;
-  float *d_terms = nullptr, *d_zero = nullptr;
-  uint32_t *d_pos = nullptr;
-  IcpState *d_state = nullptr;
-  double *d_sums = nullptr;
+  // one block: the terms, then (zeroed) a row of zero coordinates, pos_of, the loop state and the sums
+  const auto up = [](size_t v) { return (v + 255) & ~(size_t)255; };
+  const size_t sz_terms = up((size_t)kStrictRows * n * sizeof(float)), sz_row = up((size_t)n * sizeof(float)), sz_state = up(sizeof(IcpState));
+  const size_t total = sz_terms + 2 * sz_row + sz_state + 16 * sizeof(double);
+  uint8_t *block = nullptr;
   StrictBuffers *b = nullptr;
-  pcgx_status rc = PCGX_OK;
-  auto cleanup = [&]() {
+  const auto done = [&](pcgx_status rc) {
     (void)hipStreamSynchronize(st);
     if (b) strict_destroy(b);
-    (void)hipFree(d_terms);
-    (void)hipFree(d_zero);
-    (void)hipFree(d_pos);
-    (void)hipFree(d_state);
-    (void)hipFree(d_sums);
-  };
-  hipError_t e = hipMalloc((void **)&d_terms, (size_t)kStrictRows * n * sizeof(float));
-  if (e == hipSuccess) e = hipMalloc((void **)&d_zero, (size_t)n * sizeof(float));
-  if (e == hipSuccess) e = hipMalloc((void **)&d_pos, (size_t)n * sizeof(uint32_t));
-  if (e == hipSuccess) e = hipMalloc((void **)&d_state, sizeof(IcpState));
-  if (e == hipSuccess) e = hipMalloc((void **)&d_sums, 16 * sizeof(double));
-  if (e == hipSuccess) e = hipMemcpyAsync(d_terms, terms, (size_t)kStrictRows * n * sizeof(float), hipMemcpyHostToDevice, st);
-  if (e == hipSuccess) e = hipMemsetAsync(d_zero, 0, (size_t)n * sizeof(float), st);
-  if (e == hipSuccess) e = hipMemsetAsync(d_pos, 0, (size_t)n * sizeof(uint32_t), st);
-  if (e == hipSuccess) e = hipMemsetAsync(d_state, 0, sizeof(IcpState), st);
-  if (e == hipSuccess) e = hipMemsetAsync(d_sums, 0, 16 * sizeof(double), st);
-  if (e != hipSuccess) {
-    cleanup();
-    return fail(PCGX_E_HIP, "pcgx_debug_strict_sum_dev: %s", hipGetErrorString(e));
-  }
-  rc = strict_create(n, d_zero, d_zero, d_zero, d_pos, &b, st);
-  if (rc != PCGX_OK) {
-    cleanup();
+    (void)hipFree(block);
     return rc;
-  }
+  };
+  hipError_t e = hipMalloc((void **)&block, total);
+  if (e != hipSuccess) return done(fail(PCGX_E_HIP, "pcgx_debug_strict_sum_dev: %s", hipGetErrorString(e)));
+  float *d_terms = (float *)block, *d_zero = (float *)(block + sz_terms);
+  uint32_t *d_pos = (uint32_t *)(block + sz_terms + sz_row);
+  IcpState *d_state = (IcpState *)(block + sz_terms + 2 * sz_row);
+  double *d_sums = (double *)(block + sz_terms + 2 * sz_row + sz_state);
+  e = hipMemcpyAsync(d_terms, terms, (size_t)kStrictRows * n * sizeof(float), hipMemcpyHostToDevice, st);
+  if (e == hipSuccess) e = hipMemsetAsync(d_zero, 0, total - sz_terms, st);
+  if (e != hipSuccess) return done(fail(PCGX_E_HIP, "pcgx_debug_strict_sum_dev: %s", hipGetErrorString(e)));
+  pcgx_status rc = strict_create(n, d_zero, d_zero, d_zero, d_pos, &b, st);
+  if (rc != PCGX_OK) return done(rc);
   b->w.raw_terms = d_terms;
   IcpKernelParams kp;
   memset(&kp, 0, sizeof kp);
@@ -3237,8 +3221,7 @@ extern "C" pcgx_status pcgx_debug_strict_sum_dev(const float *terms, int64_t n, 
       for (int k = 0; k < 64; k++) stats[k] = (int64_t)dbg[k];
     }
   }
-  cleanup();
-  return rc;
+  return done(rc);
 }
 
 // Host model of the same pipeline (no GPU involved): the CPU tests run it against a plain

@@ -6,7 +6,8 @@ For every file of pcgol_amd.build.SOURCES the device side is compiled to assembl
 name -> text of the functions (a kernel with its descriptor and resource comments) and of the entries of the
 code-object metadata, because the order in which template instantiations are emitted follows the host's launch sites
 and may move.  What moves with that order is normalised away: the function index in local labels (.LBB<i>_<n>,
-.Lfunc_end<i>, the comments' BB<i>_<n>) and the __hip_cuid_<hash> symbol, which differs between two compiles of one source.
+.Lfunc_end<i>, the comments' BB<i>_<n>), the padding behind whichever function is emitted last, and the
+__hip_cuid_<hash> symbol, which differs between two compiles of one source.
 
     python tools/compare_device_code.py [--rev HEAD] [--jobs 8] [file.hip ...]
 
@@ -49,6 +50,12 @@ def split(asm):
             out[key] = [prev.pop()] if prev and prev[-1].split()[:1] in ([".text"], [".section"]) else []
         elif ".AMDGPU.gpr_maximums" in ln or ln.strip() == ".amdgpu_metadata":
             key = "rest"
+        elif ln.split()[:1] == [".p2alignl"]:
+            # (the padding behind the code object's last function -- .text, .p2alignl, .fill -- is whichever function's
+            # comes last in the emission order, not that function's)
+            prev = out[key]
+            key = "rest"
+            out[key] += [prev.pop()] if prev and prev[-1].split()[:1] == [".text"] else []
         out[key].append(ln)
     # the metadata's kernel entries: a YAML list under amdhsa.kernels, each entry with its .name
     rest, meta, entry = [], {}, None
