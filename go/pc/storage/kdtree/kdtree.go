@@ -18,9 +18,9 @@ import (
 // regiongrowing.go:26,47) should take the batch seams instead -- NearestBatch / RangeBatch here, or the icp and
 // segmentation types of this tree, which do.  pcgx.SinglePointCalls() counts such calls (tests guard hot loops with it).
 // Extensions with no reference counterpart come with the type: KNearest(p, k, maxRange) []storage.Neighbor (the k
-// nearest points, ties by ID; include/pcgx.h, pcgx_kdtree_knearest), KNearestBatch, Normals, FPFH, and the keypoint
-// detectors LocalMaxima(radius, score) and ISSKeypoints(salientRadius, nonMaxRadius, gamma21, gamma32, minNeighbors)
-// (include/pcgx.h, "keypoints").
+// nearest points, ties by ID; include/pcgx.h, pcgx_kdtree_knearest), KNearestBatch, Normals, FPFH, FPFHAt (FPFH's rows
+// at chosen ids only), and the keypoint detectors LocalMaxima(radius, score) and ISSKeypoints(salientRadius,
+// nonMaxRadius, gamma21, gamma32, minNeighbors) (include/pcgx.h, "keypoints").
 type KDTree = pcgx.KDTree
 
 // KDTreeOption is kdtree.KDTreeOption (kdtree.go:31).

@@ -356,6 +356,47 @@ func (k *KDTree) FPFH(radius float32, normals []mat.Vec3) ([][33]float32, error)
 	return fpfh, nil
 }
 
+// FPFHAt returns FPFH's rows at the listed point ids only, and the points themselves (extension: no reference parity;
+// include/pcgx.h, pcgx_kdtree_fpfh_at): row s is FPFH(radius, normals)'s row ids[s] bit for bit, without describing the
+// rest of the cloud.  ids: in any order, repeats allowed, e.g. what ISSKeypoints returns; an id outside [0, Len()) is
+// an error.  nSpfh: how many points' SPFH records had to be computed, the listed points and their neighbours.
+func (k *KDTree) FPFHAt(radius float32, normals []mat.Vec3, ids []int) (fpfh [][33]float32, xyz []mat.Vec3, nSpfh int, err error) {
+	runtime.LockOSThread() // the error text is thread-local on the C side: call and pcgx_last_error on one OS thread
+	defer runtime.UnlockOSThread()
+	defer runtime.KeepAlive(k) // the finalizer must not free the handle while a call is in flight
+	var ln C.int64_t
+	if err := status(C.pcgx_kdtree_len(k.t.h, &ln)); err != nil {
+		return nil, nil, 0, err
+	}
+	if len(normals) != int(ln) {
+		return nil, nil, 0, errors.New("pcgx: one normal per point of the tree is required")
+	}
+	fpfh = make([][33]float32, len(ids))
+	xyz = make([]mat.Vec3, len(ids))
+	if len(ids) == 0 {
+		return fpfh, xyz, 0, nil
+	}
+	ids64 := make([]C.int64_t, len(ids))
+	for i, id := range ids {
+		ids64[i] = C.int64_t(id)
+	}
+	var np *C.float // (an empty tree: every id is out of range, and the library says so)
+	if len(normals) > 0 {
+		np = (*C.float)(unsafe.Pointer(&normals[0]))
+	}
+	var cnt C.int64_t
+	rc := C.pcgx_kdtree_fpfh_at(k.t.h, np, C.float(radius), &ids64[0], C.int64_t(len(ids)),
+		(*C.float)(unsafe.Pointer(&fpfh[0])), (*C.float)(unsafe.Pointer(&xyz[0])), nil, nil, &cnt)
+	runtime.KeepAlive(normals)
+	runtime.KeepAlive(ids64)
+	runtime.KeepAlive(fpfh)
+	runtime.KeepAlive(xyz)
+	if err := status(rc); err != nil {
+		return nil, nil, 0, err
+	}
+	return fpfh, xyz, int(cnt), nil
+}
+
 // LocalMaxima returns, in ascending order, the ids of the points whose score is the largest of their radius
 // neighbourhood (extension: no reference parity; include/pcgx.h, pcgx_kdtree_local_maxima).  score: one per point in id
 // order; only a score > 0 qualifies (NaN never, +Inf does), ties go to the smaller id, a deleted id is never a maximum.

@@ -804,6 +804,46 @@ PCGX_API pcgx_status pcgx_kdtree_fpfh(const pcgx_kdtree *t, const float *normals
 PCGX_API pcgx_status pcgx_kdtree_fpfh_dev(const pcgx_kdtree *t, const float *d_normals, float radius, float *d_fpfh,
                                           int32_t *d_spfh_counts, int32_t *d_pair_counts, void *stream);
 
+/* ------------------------------------------- FPFH at chosen points (extension: no reference parity)
+ * NOT in the reference.  pcgx_kdtree_fpfh's rows at a list of point ids -- keypoints -- without describing the rest
+ * of the cloud: a descriptor is needed only at a listed point, an SPFH record only at a listed point or at one of its
+ * neighbours.  The outputs are compact, one slot per list entry, with a fixed capacity on the device, so that the
+ * chain keypoints -> descriptors -> match -> pose runs on one stream with nothing read back.
+ * Slots: on the device form n = clamp(*d_n_ids, 0, cap), read on the device (d_n_ids == NULL: n = cap); on the host
+ *   form n = n_ids.  Slot s is live iff s < n and 0 <= ids[s] < Len().  Ids may repeat and need not be sorted; deleted
+ *   ids are allowed, exactly as pcgx_kdtree_fpfh computes their rows.  The host form, which can read the list, rejects
+ *   an id out of range (as pcgx_pose_from_correspondences does); on the device form such an id makes its slot dead:
+ *   that covers the -1 pcgx_kdtree_local_maxima_dev pads with, so its d_ids and d_n_ids can be passed on as they are.
+ * Live slot s: fpfh[33 s ..], spfh_counts[33 s ..] and pair_counts[s] are what pcgx_kdtree_fpfh's contract defines
+ *   for point ids[s] on that handle (the counts exact, F within 2^-22 relative of the real-number value and its zeros
+ *   exact; in fact the bits pcgx_kdtree_fpfh writes, the sums being taken in its order); xyz[3 s ..] (may be NULL)
+ *   holds the point's three float32 bit for bit.
+ * Dead slot: 33 zeros, a zero xyz, zero counts: the row pcgx_fpfh_match never takes as a candidate and never answers
+ *   as a query, so a matcher given na = cap sees the padding as nothing.  Every slot of [0, cap) is written on every
+ *   call.
+ * n_spfh (may be NULL; one int32 on the device): the number of distinct points whose SPFH record the call computed:
+ *   the ids of the live slots and every member of their N(.).  Exact; it says, without a clock, how much of the cloud
+ *   was left alone.
+ * The same input gives the same bits on every call (no float atomics).  n_ids == 0 or cap == 0 is PCGX_OK.
+ * PCGX_E_INVALID: a radius that is not finite and > 0, a NULL tree, a negative count, NULL ids or NULL fpfh with a
+ * positive count, NULL normals with a positive count and Len() > 0, more than 2^31 - 1 ids or points; on the host
+ * form an id outside [0, Len()).  Always computed on the device.  Temporaries: Len() bytes of flags, cleared inside
+ * the call, and the 144 Len() bytes of records, of which only the n_spfh needed ones are written.  The first call on
+ * a handle without deletions builds the handle's id -> node map and waits for it, once. */
+PCGX_API pcgx_status pcgx_kdtree_fpfh_at(const pcgx_kdtree *t, const float *normals /* [3 Len()], id order */,
+                                         float radius, const int64_t *ids /* [n_ids] */, int64_t n_ids,
+                                         float *fpfh /* [33 n_ids] */, float *xyz /* [3 n_ids], may be NULL */,
+                                         int32_t *spfh_counts /* [33 n_ids], may be NULL */,
+                                         int32_t *pair_counts /* [n_ids], may be NULL */,
+                                         int64_t *n_spfh /* may be NULL */);
+/* Same, every array device resident, enqueued on `stream` (NULL: the library's); returns without waiting. */
+PCGX_API pcgx_status pcgx_kdtree_fpfh_at_dev(const pcgx_kdtree *t, const float *d_normals, float radius,
+                                             const int32_t *d_ids /* [cap] */, int64_t cap,
+                                             const int32_t *d_n_ids /* one int32; NULL: cap ids */,
+                                             float *d_fpfh /* [33 cap] */, float *d_xyz /* [3 cap], may be NULL */,
+                                             int32_t *d_spfh_counts, int32_t *d_pair_counts,
+                                             int32_t *d_n_spfh /* one int32, may be NULL */, void *stream);
+
 /* ------------------------------------------- FPFH matching (extension: no reference parity)
  * NOT in the reference.  For every row of one descriptor array, the nearest and the second nearest row of another,
  * brute force over all pairs, and the correspondence list made from them: what feature-based coarse alignment

@@ -253,6 +253,8 @@ SIGNATURES = {
     "pcgx_kdtree_normals_dev": (_i32, [_vp, _vp, _i64, _f32, _vp, _i32, _vp, _vp, _vp, _vp]),
     "pcgx_kdtree_fpfh": (_i32, [_vp, _vp, _f32, _vp, _vp, _vp]),
     "pcgx_kdtree_fpfh_dev": (_i32, [_vp, _vp, _f32, _vp, _vp, _vp, _vp]),
+    "pcgx_kdtree_fpfh_at": (_i32, [_vp, _vp, _f32, _vp, _i64, _vp, _vp, _vp, _vp, C.POINTER(_i64)]),
+    "pcgx_kdtree_fpfh_at_dev": (_i32, [_vp, _vp, _f32, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "pcgx_fpfh_match": (_i32, [_vp, _i64, _vp, _i64, _vp, _vp, _vp]),
     "pcgx_fpfh_match_dev": (_i32, [_vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp]),
     "pcgx_fpfh_correspondences": (_i32, [_vp, _i64, _vp, _i64, _f32, _i32, _vp, _vp, _vp]),

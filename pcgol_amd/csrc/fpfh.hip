@@ -16,9 +16,23 @@
 // A fat row (kRangeFatRow) is the whole wave's work in both kernels, as in normals_kernel: every lane takes every 64th
 // record of the owner's row; the counts go into the owner's LDS column by LDS atomics (integers: any order gives the
 // same bits), the float64 partials are summed by shuffles.
+//
+// Descriptors at chosen ids only (pcgx_kdtree_fpfh_at, include/pcgx.h "FPFH at chosen points"): three stages over the
+// same enumeration; the queries of the first and the third are the selected points, fetched by id, one slot per lane:
+//   fpfh_mark_kernel  a 1 into need[j] for the slot's point and for every member of its N(.) (plain byte stores of one
+//                     value: no atomics, any order), the slot's xyz, and a dead slot's zeros.
+//   spfh_need_kernel  spfh_kernel over the tree's own points in cell order, except that a lane whose need byte is 0
+//                     enumerates nothing and writes no record (local_maxima_kernel's way with a score that cannot
+//                     qualify).  The flags are then counted by bucket_grid.h's tile count and one scan workgroup.
+//   fpfh_at_kernel    fpfh_kernel with the records read by id and the row written at the slot.  A lane's sums run over
+//                     its query's neighbourhood in the order fpfh_kernel's lane takes for that point (the rows of the
+//                     grid as grid_cover names them, a walk from the root), so the row is fpfh_kernel's, bit for bit.
+// They are kernels of their own, not instantiations of a body shared with the two above: pcgx_kdtree_fpfh keeps the
+// instructions it had.
 #include <math.h>
 #include <stdlib.h>
 
+#include "bucket_grid.h"
 #include "fpfh_terms.h"
 #include "knn_grid.h"
 #include "knn_xwalk.h"
@@ -218,6 +232,234 @@ __global__ __launch_bounds__(kFpfhBlock) void fpfh_kernel(GridView g, TreeView t
   }
 }
 
+// ---- descriptors at chosen ids
+
+// the slots: ids[cap], of which the first clamp(*n_ids, 0, cap) count (n_ids == nullptr: all), and where a point's
+// xyz is found by id
+struct FpfhSlots {
+  const int32_t *ids;
+  const int32_t *n_ids;
+  int32_t cap;
+  int64_t n;            // Len()
+  const uint32_t *inv;  // grid, walk: id -> BFS slot of its node in the implicit tree (range_inverse_map)
+  const float *xyz;     // patched tree: the cloud's points by id (t->d_xsrc)
+};
+
+// slot s: live?  Then its point id i and the point.
+template <int kSrc>
+__device__ __forceinline__ bool read_slot(const FpfhSlots &S, const TreeView &tv, const int64_t s, int64_t &i, float &qx,
+                                          float &qy, float &qz) {
+  if (s >= (int64_t)S.cap) return false;
+  if (S.n_ids && s >= (int64_t)*S.n_ids) return false;  // (a negative count: no slot is below it)
+  const int32_t id = S.ids[s];
+  if (id < 0 || (int64_t)id >= S.n) return false;
+  i = (int64_t)id;
+  if constexpr (kSrc == kRangeXWalk) {
+    qx = S.xyz[3 * i];
+    qy = S.xyz[3 * i + 1];
+    qz = S.xyz[3 * i + 2];
+  } else {
+    const float4 nd = node_at(tv.nodes, S.inv[i]);
+    qx = nd.x;
+    qy = nd.y;
+    qz = nd.z;
+  }
+  return true;
+}
+
+struct FpfhAtOut {
+  float *fpfh;      // [33 cap]
+  float *xyz;       // [3 cap] or nullptr
+  int32_t *counts;  // [33 cap] or nullptr
+  int32_t *pairs;   // [cap] or nullptr
+};
+
+template <int kSrc>
+__global__ __launch_bounds__(kFpfhBlock) void fpfh_mark_kernel(GridView g, TreeView tv, XTreeView xv, FpfhSlots S,
+                                                               float bound, uint8_t *__restrict__ need, FpfhAtOut O,
+                                                               int64_t guard) {
+  extern __shared__ uint32_t s_stack[];
+  const int64_t s = (int64_t)blockIdx.x * kFpfhBlock + threadIdx.x;
+  int64_t i = 0;
+  float qx = 0.0f, qy = 0.0f, qz = 0.0f;
+  const bool live = read_slot<kSrc>(S, tv, s, i, qx, qy, qz);
+  if (s < (int64_t)S.cap) {
+    if (O.xyz) {
+      O.xyz[3 * s] = qx;
+      O.xyz[3 * s + 1] = qy;
+      O.xyz[3 * s + 2] = qz;
+    }
+    if (!live) {  // a dead slot: zeros (fpfh_at_kernel writes the live ones)
+      for (int k = 0; k < kFpfhLen; k++) {
+        O.fpfh[(size_t)kFpfhLen * (size_t)s + k] = 0.0f;
+        if (O.counts) O.counts[(size_t)kFpfhLen * (size_t)s + k] = 0;
+      }
+      if (O.pairs) O.pairs[s] = 0;
+    }
+  }
+  // (the grid path keeps every lane of the wave to the end: the fat rows are scanned by all 64)
+  if (kSrc != kRangeGrid && !live) return;
+  if (live) need[i] = (uint8_t)1;  // (a deleted id, a NaN coordinate: the point does not meet itself)
+  auto take = [&](const float4 &p) {
+    if (ref_dist_sq(p.x, p.y, p.z, qx, qy, qz) < bound) need[__float_as_uint(p.w)] = (uint8_t)1;
+  };
+  if constexpr (kSrc == kRangeGrid) {
+    const int lane = (int)(threadIdx.x & 63u);
+    grid_radius_scan(g, qx, qy, qz, bound, live, take, [&](int, uint32_t rf, uint32_t re, float ox, float oy, float oz) {
+      for (uint32_t r = rf + (uint32_t)lane; r < re; r += 64u) {
+        const float4 p = g.pts[r];
+        if (ref_dist_sq(p.x, p.y, p.z, ox, oy, oz) < bound) need[__float_as_uint(p.w)] = (uint8_t)1;
+      }
+    });
+  } else if constexpr (kSrc == kRangeWalk) {
+    range_walk_nodes<false>(tv, s_stack + threadIdx.x, kFpfhBlock, qx, qy, qz, bound, [=]() { return bound; },
+                            [&](const float4 &nd, float) {  // (range_walk_nodes reports only DistSq < bound)
+                              need[__float_as_uint(nd.w)] = (uint8_t)1;
+                            });
+  } else {
+    auto hit = [&](const float4 &nd, float) {
+      take(nd);
+      return true;
+    };
+    xwalk(xv, s_stack + threadIdx.x, kFpfhBlock, qx, qy, qz, guard, [&]() { return bound; }, hit, hit);
+  }
+}
+
+// spfh_kernel, for the points whose need byte is set; the others' records stay unwritten and nobody reads them
+template <int kSrc>
+__global__ __launch_bounds__(kFpfhBlock) void spfh_need_kernel(GridView g, TreeView tv, XTreeView xv, QuerySource Q,
+                                                               float bound, const uint8_t *__restrict__ need,
+                                                               const float *normals, uint4 *rec, int64_t guard) {
+  extern __shared__ uint32_t s_stack[];
+  __shared__ uint32_t s_cnt[kFpfhRows * kFpfhBlock];
+  const uint32_t n_tiles = (uint32_t)((Q.nq + kFpfhBlock - 1) / kFpfhBlock);
+  const int64_t pos = (int64_t)xcd_tile(blockIdx.x, n_tiles) * kFpfhBlock + threadIdx.x;
+  const int lane = (int)threadIdx.x;
+#pragma unroll
+  for (int k = 0; k < kFpfhRows; k++) s_cnt[k * kFpfhBlock + lane] = 0u;
+  int64_t i = 0;
+  float qx = 0.0f, qy = 0.0f, qz = 0.0f, nx = 0.0f, ny = 0.0f, nz = 0.0f;
+  bool want = false;
+  if (pos < Q.nq) {
+    read_query(Q, pos, i, qx, qy, qz);
+    want = need[i] != 0;
+  }
+  // (the grid path keeps every lane of the wave to the end: the fat rows are scanned by all 64)
+  if (kSrc != kRangeGrid && !want) return;
+  if (want) {
+    nx = normals[3 * i];
+    ny = normals[3 * i + 1];
+    nz = normals[3 * i + 2];
+  }
+  auto take = [&](const float4 &p) {
+    if (ref_dist_sq(p.x, p.y, p.z, qx, qy, qz) < bound) spfh_pair(s_cnt, lane, normals, p, qx, qy, qz, nx, ny, nz);
+  };
+  if constexpr (kSrc == kRangeGrid) {
+    __syncthreads();  // (one wave: the zeroes are in place before another lane's atomics land in this column)
+    grid_radius_scan(g, qx, qy, qz, bound, want, take, [&](int owner, uint32_t rf, uint32_t re, float ox, float oy, float oz) {
+      const float onx = __shfl(nx, owner), ony = __shfl(ny, owner), onz = __shfl(nz, owner);
+      for (uint32_t r = rf + (uint32_t)lane; r < re; r += 64u) {
+        const float4 p = g.pts[r];
+        if (ref_dist_sq(p.x, p.y, p.z, ox, oy, oz) < bound) spfh_pair(s_cnt, owner, normals, p, ox, oy, oz, onx, ony, onz);
+      }
+    });
+    __syncthreads();  // the other lanes' atomics before the owner reads its column
+    if (!want) return;
+  } else if constexpr (kSrc == kRangeWalk) {
+    range_walk_nodes<false>(tv, s_stack + threadIdx.x, kFpfhBlock, qx, qy, qz, bound, [=]() { return bound; },
+                            [&](const float4 &nd, float) {  // (range_walk_nodes reports only DistSq < bound)
+                              spfh_pair(s_cnt, lane, normals, nd, qx, qy, qz, nx, ny, nz);
+                            });
+  } else {
+    auto hit = [&](const float4 &nd, float) {
+      take(nd);
+      return true;
+    };
+    xwalk(xv, s_stack + threadIdx.x, kFpfhBlock, qx, qy, qz, guard, [&]() { return bound; }, hit, hit);
+  }
+  uint32_t c[kFpfhRec];
+#pragma unroll
+  for (int k = 0; k < kFpfhRec; k++) c[k] = k < kFpfhRows ? s_cnt[k * kFpfhBlock + lane] : 0u;
+#pragma unroll
+  for (int k = 0; k < kFpfhRec / 4; k++) rec[(kFpfhRec / 4) * i + k] = make_uint4(c[4 * k], c[4 * k + 1], c[4 * k + 2], c[4 * k + 3]);
+}
+
+__global__ __launch_bounds__(256) void fpfh_need_count_kernel(const uint8_t *__restrict__ need, int64_t n,
+                                                              uint32_t *__restrict__ tile_count) {
+  tile_flag_count(n, [&](int64_t j) { return need[j] != 0; }, tile_count);
+}
+__global__ __launch_bounds__(1024) void fpfh_need_scan_kernel(uint32_t *__restrict__ tile_count, int ntiles,
+                                                              uint32_t *__restrict__ total) {
+  tile_scan(tile_count, ntiles, total);
+}
+
+// fpfh_kernel, the queries the live slots' points; the row, the point's counts and its pairs go to the slot
+template <int kSrc>
+__global__ __launch_bounds__(kFpfhBlock) void fpfh_at_kernel(GridView g, TreeView tv, XTreeView xv, FpfhSlots S,
+                                                             float bound, const uint4 *rec, FpfhAtOut O, int64_t guard) {
+  extern __shared__ uint32_t s_stack[];
+  const int64_t s = (int64_t)blockIdx.x * kFpfhBlock + threadIdx.x;
+  int64_t i = 0;
+  float qx = 0.0f, qy = 0.0f, qz = 0.0f;
+  const bool live = read_slot<kSrc>(S, tv, s, i, qx, qy, qz);
+  if (kSrc != kRangeGrid && !live) return;
+  FpfhAcc acc;
+  acc.clear();
+  auto take = [&](const float4 &p) {
+    const float d = ref_dist_sq(p.x, p.y, p.z, qx, qy, qz);
+    if (d < bound) acc.add(rec, p, d);
+  };
+  if constexpr (kSrc == kRangeGrid) {
+    const int lane = (int)(threadIdx.x & 63u);
+    grid_radius_scan(g, qx, qy, qz, bound, live, take, [&](int owner, uint32_t rf, uint32_t re, float ox, float oy, float oz) {
+      FpfhAcc part;
+      part.clear();
+      for (uint32_t r = rf + (uint32_t)lane; r < re; r += 64u) {
+        const float4 p = g.pts[r];
+        const float d = ref_dist_sq(p.x, p.y, p.z, ox, oy, oz);
+        if (d < bound) part.add(rec, p, d);
+      }
+      part.wave_sum();
+      if (lane == owner) acc.merge(part);
+    });
+    if (!live) return;
+  } else if constexpr (kSrc == kRangeWalk) {
+    range_walk_nodes<false>(tv, s_stack + threadIdx.x, kFpfhBlock, qx, qy, qz, bound, [=]() { return bound; },
+                            [&](const float4 &nd, float d) {  // (range_walk_nodes reports only DistSq < bound)
+                              acc.add(rec, nd, d);
+                            });
+  } else {
+    auto hit = [&](const float4 &nd, float) {
+      take(nd);
+      return true;
+    };
+    xwalk(xv, s_stack + threadIdx.x, kFpfhBlock, qx, qy, qz, guard, [&]() { return bound; }, hit, hit);
+  }
+  // F = S_q + 100 W / T per feature
+  const uint4 *own = rec + (size_t)(kFpfhRec / 4) * (size_t)i;
+  uint4 q[kFpfhRec / 4];
+#pragma unroll
+  for (int k = 0; k < kFpfhRec / 4; k++) q[k] = own[k];
+  const uint32_t m = q[kFpfhLen / 4].y;
+  const double sq = m ? 100.0 / (double)m : 0.0;
+#pragma unroll
+  for (int f = 0; f < 3; f++) {
+    double T = 0.0;
+#pragma unroll
+    for (int b = 0; b < kFpfhBins; b++) T += acc.a[f * kFpfhBins + b];
+    const double sc = T > 0.0 ? 100.0 / T : 0.0;
+#pragma unroll
+    for (int b = 0; b < kFpfhBins; b++) {
+      const int k = f * kFpfhBins + b;
+      const uint4 &u = q[k / 4];
+      const uint32_t ck = k % 4 == 0 ? u.x : (k % 4 == 1 ? u.y : (k % 4 == 2 ? u.z : u.w));
+      O.fpfh[(size_t)kFpfhLen * (size_t)s + k] = (float)((double)ck * sq + acc.a[k] * sc);
+      if (O.counts) O.counts[(size_t)kFpfhLen * (size_t)s + k] = (int32_t)ck;
+    }
+  }
+  if (O.pairs) O.pairs[s] = (int32_t)m;
+}
+
 }  // namespace pcgx
 
 using namespace pcgx;
@@ -263,7 +505,135 @@ pcgx_status fpfh_enqueue(const pcgx_kdtree *t, const float *d_normals, float rad
   return PCGX_OK;
 }
 
+constexpr int64_t kFpfhAtMax = 0x7fffffff;  // ids and counts are int32 on the device
+
+pcgx_status fpfh_at_check(const char *fn, const pcgx_kdtree *t, const float *normals, float radius, const void *ids,
+                          int64_t count, const float *fpfh) {
+  if (!t) return fail(PCGX_E_INVALID, "%s: bad argument", fn);
+  if (!(radius > 0.0f) || !(radius < __builtin_inff())) return fail(PCGX_E_INVALID, "%s: radius must be finite and > 0", fn);
+  if (count < 0) return fail(PCGX_E_INVALID, "%s: negative number of ids", fn);
+  if (count > kFpfhAtMax || t->n > kFpfhAtMax) return fail(PCGX_E_INVALID, "%s: more than 2^31 - 1 ids or points", fn);
+  if (count > 0 && !ids) return fail(PCGX_E_INVALID, "%s: NULL ids", fn);
+  if (count > 0 && !fpfh) return fail(PCGX_E_INVALID, "%s: NULL fpfh", fn);
+  if (count > 0 && t->n > 0 && !normals) return fail(PCGX_E_INVALID, "%s: NULL normals", fn);
+  return PCGX_OK;
+}
+
+template <int kSrc>
+void fpfh_at_launch(const pcgx_kdtree *t, const TreeView &tv, const XTreeView &xv, const QuerySource &Q,
+                    const FpfhSlots &S, float bound, const float *d_normals, uint8_t *d_need, uint4 *d_rec,
+                    const FpfhAtOut &O, size_t stack_bytes, hipStream_t st) {
+  const dim3 slots((unsigned)(((int64_t)S.cap + kFpfhBlock - 1) / kFpfhBlock));
+  const dim3 points(xcd_grid((unsigned)((Q.nq + kFpfhBlock - 1) / kFpfhBlock))), block(kFpfhBlock);
+  const int64_t guard = xwalk_guard(t->n);
+  const GridView g = kSrc == kRangeGrid ? t->grid : GridView{};
+  hipLaunchKernelGGL(fpfh_mark_kernel<kSrc>, slots, block, stack_bytes, st, g, tv, xv, S, bound, d_need, O, guard);
+  hipLaunchKernelGGL(spfh_need_kernel<kSrc>, points, block, stack_bytes, st, g, tv, xv, Q, bound, (const uint8_t *)d_need,
+                     d_normals, d_rec, guard);
+  hipLaunchKernelGGL(fpfh_at_kernel<kSrc>, slots, block, stack_bytes, st, g, tv, xv, S, bound, (const uint4 *)d_rec, O,
+                     guard);
+}
+
+// Len() > 0, cap > 0, everything device resident; the flags, the SPFH records and the tile counts from ctx().arena
+pcgx_status fpfh_at_enqueue(const pcgx_kdtree *t, const float *d_normals, float radius, const int32_t *d_ids, int64_t cap,
+                            const int32_t *d_n_ids, const FpfhAtOut &O, int32_t *d_n_spfh, hipStream_t st) {
+  PCGX_TRY(ctx().arena.begin(st));
+  const int64_t n = t->n;
+  const RangeSrc src = range_source(t);  // as pcgx_kdtree_range_count takes it
+  XTreeView xv{};
+  if (src == kRangeXWalk) PCGX_TRY(xtree_view(t, &xv, st));
+  FpfhSlots S{d_ids, d_n_ids, (int32_t)cap, n, nullptr, nullptr};  // (xtree_view made d_xsrc)
+  if (src == kRangeXWalk) S.xyz = t->d_xsrc;
+  else PCGX_TRY(range_inverse_map(t, &S.inv, st));
+  const TreeView tv = t->view();
+  QuerySource Q;
+  PCGX_TRY(query_source(t, src, nullptr, n, &Q, st));
+  uint8_t *d_need = nullptr;
+  uint4 *d_rec = nullptr;
+  PCGX_TRY(ctx().arena.alloc_n((size_t)n, &d_need));
+  PCGX_TRY(ctx().arena.alloc_n((size_t)n * (kFpfhRec / 4), &d_rec));
+  // (the arena hands out what an earlier call used: the flags start from zero on every call)
+  PCGX_HIP_TRY(hipMemsetAsync(d_need, 0, (size_t)n, st));
+  const float bound = radius * radius;
+  if (src == kRangeXWalk)
+    fpfh_at_launch<kRangeXWalk>(t, tv, xv, Q, S, bound, d_normals, d_need, d_rec, O, xwalk_stack_bytes(xv, kFpfhBlock), st);
+  else if (src == kRangeGrid) fpfh_at_launch<kRangeGrid>(t, tv, xv, Q, S, bound, d_normals, d_need, d_rec, O, 0, st);
+  else fpfh_at_launch<kRangeWalk>(t, tv, xv, Q, S, bound, d_normals, d_need, d_rec, O, walk_stack_bytes(tv, kFpfhBlock), st);
+  if (d_n_spfh) {
+    const int ntiles = (int)((n + kRunTile - 1) / kRunTile);
+    uint32_t *tile_count = nullptr;
+    PCGX_TRY(ctx().arena.alloc_n((size_t)ntiles, &tile_count));
+    hipLaunchKernelGGL(fpfh_need_count_kernel, dim3(ntiles), dim3(256), 0, st, (const uint8_t *)d_need, n, tile_count);
+    hipLaunchKernelGGL(fpfh_need_scan_kernel, dim3(1), dim3(1024), 0, st, tile_count, ntiles, (uint32_t *)d_n_spfh);
+  }
+  PCGX_HIP_TRY(hipGetLastError());
+  return PCGX_OK;
+}
+
 }  // namespace
+
+extern "C" pcgx_status pcgx_kdtree_fpfh_at_dev(const pcgx_kdtree *t, const float *d_normals, float radius,
+                                               const int32_t *d_ids, int64_t cap, const int32_t *d_n_ids, float *d_fpfh,
+                                               float *d_xyz, int32_t *d_spfh_counts, int32_t *d_pair_counts,
+                                               int32_t *d_n_spfh, void *stream) {
+  PCGX_API_LOCK();
+  PCGX_TRY(fpfh_at_check("pcgx_kdtree_fpfh_at_dev", t, d_normals, radius, d_ids, cap, d_fpfh));
+  PCGX_TRY(ensure_init());
+  hipStream_t st = pick_stream(stream);
+  if (t->n == 0 || cap == 0) {  // no point to describe: every slot is dead
+    const size_t c = (size_t)cap;
+    if (d_n_spfh) PCGX_HIP_TRY(hipMemsetAsync(d_n_spfh, 0, sizeof(int32_t), st));
+    if (c == 0) return PCGX_OK;
+    PCGX_HIP_TRY(hipMemsetAsync(d_fpfh, 0, c * kFpfhLen * 4, st));
+    if (d_xyz) PCGX_HIP_TRY(hipMemsetAsync(d_xyz, 0, c * 12, st));
+    if (d_spfh_counts) PCGX_HIP_TRY(hipMemsetAsync(d_spfh_counts, 0, c * kFpfhLen * 4, st));
+    if (d_pair_counts) PCGX_HIP_TRY(hipMemsetAsync(d_pair_counts, 0, c * 4, st));
+    return PCGX_OK;
+  }
+  return fpfh_at_enqueue(t, d_normals, radius, d_ids, cap, d_n_ids, FpfhAtOut{d_fpfh, d_xyz, d_spfh_counts, d_pair_counts},
+                         d_n_spfh, st);
+}
+
+extern "C" pcgx_status pcgx_kdtree_fpfh_at(const pcgx_kdtree *t, const float *normals, float radius, const int64_t *ids,
+                                           int64_t n_ids, float *fpfh, float *xyz, int32_t *spfh_counts,
+                                           int32_t *pair_counts, int64_t *n_spfh) {
+  PCGX_API_CALL();
+  PCGX_TRY(fpfh_at_check("pcgx_kdtree_fpfh_at", t, normals, radius, ids, n_ids, fpfh));
+  if (n_spfh) *n_spfh = 0;
+  if (n_ids == 0) return PCGX_OK;
+  const int64_t n = t->n;
+  RawVector<int32_t> h((size_t)n_ids + 1);  // the ids, and the record count coming back
+  for (int64_t s = 0; s < n_ids; s++) {
+    if (ids[s] < 0 || ids[s] >= n) return fail(PCGX_E_INVALID, "pcgx_kdtree_fpfh_at: id out of range");
+    h[(size_t)s] = (int32_t)ids[s];
+  }
+  PCGX_TRY(ensure_init());
+  // always on the device: the bins and the sums are the kernels', not a host restatement
+  hipStream_t st = ctx().stream;
+  Arena &ha = ctx().host_arena;
+  PCGX_TRY(ha.begin(st));
+  float *d_n = nullptr, *d_f = nullptr, *d_x = nullptr;
+  int32_t *d_i = nullptr, *d_c = nullptr, *d_m = nullptr;  // d_i: ids [n_ids], the record count
+  PCGX_TRY(ha.alloc_n((size_t)n * 3, &d_n));
+  PCGX_TRY(staged_upload(d_n, normals, (size_t)n * 12, st));
+  PCGX_TRY(ha.alloc_n((size_t)n_ids + 1, &d_i));
+  PCGX_TRY(staged_upload(d_i, h.data(), (size_t)n_ids * 4, st));
+  PCGX_TRY(ha.alloc_n((size_t)n_ids * kFpfhLen, &d_f));
+  if (xyz) PCGX_TRY(ha.alloc_n((size_t)n_ids * 3, &d_x));
+  if (spfh_counts) PCGX_TRY(ha.alloc_n((size_t)n_ids * kFpfhLen, &d_c));
+  if (pair_counts) PCGX_TRY(ha.alloc_n((size_t)n_ids, &d_m));
+  PCGX_TRY(pcgx_kdtree_fpfh_at_dev(t, d_n, radius, d_i, n_ids, nullptr, d_f, d_x, d_c, d_m, d_i + n_ids, st));
+  PCGX_TRY(staged_download(fpfh, d_f, (size_t)n_ids * kFpfhLen * 4, st));
+  if (xyz) PCGX_TRY(staged_download(xyz, d_x, (size_t)n_ids * 12, st));
+  if (spfh_counts) PCGX_TRY(staged_download(spfh_counts, d_c, (size_t)n_ids * kFpfhLen * 4, st));
+  if (pair_counts) PCGX_TRY(staged_download(pair_counts, d_m, (size_t)n_ids * 4, st));
+  if (n_spfh) {
+    int32_t c = 0;
+    PCGX_TRY(staged_download(&c, d_i + n_ids, 4, st));
+    *n_spfh = c;
+  }
+  return PCGX_OK;
+}
 
 extern "C" pcgx_status pcgx_kdtree_fpfh_dev(const pcgx_kdtree *t, const float *d_normals, float radius, float *d_fpfh,
                                             int32_t *d_spfh_counts, int32_t *d_pair_counts, void *stream) {

@@ -187,6 +187,30 @@ class KDTree {  // pc/storage/kdtree/kdtree.go:14-23
                            n ? r.counts[0].data() : nullptr, r.pairs.data()));
     return r;
   }
+  // FPFH's rows at the listed point ids only (extension: no reference parity; include/pcgx.h, pcgx_kdtree_fpfh_at):
+  // row s is FPFH(radius, normals)'s row ids[s] bit for bit, xyz[s] that point.  Ids in any order, repeats allowed; an
+  // id outside [0, Len()) throws.  nSpfh: the points whose SPFH record had to be computed -- the listed points and
+  // their neighbours, not the cloud.
+  struct FPFHAtResult {
+    std::vector<std::array<float, 33>> fpfh;
+    std::vector<Vec3> xyz;
+    std::vector<std::array<int32_t, 33>> counts;
+    std::vector<int32_t> pairs;
+    int64_t nSpfh = 0;
+  };
+  FPFHAtResult FPFHAt(float radius, const std::vector<Vec3> &normals, const std::vector<int64_t> &ids) const {
+    const int64_t n = Len(), k = (int64_t)ids.size();
+    if ((int64_t)normals.size() != n) throw Error(PCGX_E_INVALID, "one normal per point of the tree is required");
+    FPFHAtResult r;
+    r.fpfh.resize((size_t)k);
+    r.xyz.resize((size_t)k);
+    r.counts.resize((size_t)k);
+    r.pairs.resize((size_t)k);
+    check(pcgx_kdtree_fpfh_at(h_.get(), n ? normals[0].data() : nullptr, radius, ids.data(), k,
+                              k ? r.fpfh[0].data() : nullptr, k ? r.xyz[0].data() : nullptr,
+                              k ? r.counts[0].data() : nullptr, r.pairs.data(), &r.nSpfh));
+    return r;
+  }
   // The points whose score is the largest of their radius neighbourhood, ascending ids (extension: no reference
   // parity; include/pcgx.h, pcgx_kdtree_local_maxima).  `score`: one per point in id order; only a score > 0
   // qualifies, ties go to the smaller id.

@@ -1,7 +1,7 @@
 """pc/storage/kdtree mirror: KDTree on the GPU behind the storage.Search shape
 (pc/storage/search.go:13-17): Vec3At / Len / Nearest, plus batched NearestBatch, and extensions with no
-reference counterpart: surface normals (Normals), FPFH descriptors (FPFH), keypoints (LocalMaxima, ISSKeypoints), k
-nearest neighbours (KNearest) and their covariances (Covariances)."""
+reference counterpart: surface normals (Normals), FPFH descriptors (FPFH, FPFHAt), keypoints (LocalMaxima,
+ISSKeypoints), k nearest neighbours (KNearest) and their covariances (Covariances)."""
 import ctypes as C
 
 import numpy as np
@@ -199,6 +199,39 @@ class KDTree:
             self._h, L.ptr(int(d_normals)), float(radius), L.ptr(int(d_fpfh)),
             L.ptr(int(d_counts)) if d_counts else None, L.ptr(int(d_pairs)) if d_pairs else None,
             L.ptr(stream) if stream else None))
+
+    def FPFHAt(self, radius, Normals, Ids):
+        """FPFH's rows at the listed point ids only -> (fpfh (k,33) float32, xyz (k,3) float32, counts (k,3,11) int32,
+        pairs (k,) int32, n_spfh int).  Ids: int64, any order, repeats allowed; an id outside [0, Len()) raises.  Row s
+        is FPFH(radius, Normals)'s row Ids[s], bit for bit, and xyz[s] is that point; n_spfh: how many points' SPFH
+        records had to be computed -- the listed points and their neighbours, not the cloud (include/pcgx.h,
+        pcgx_kdtree_fpfh_at)."""
+        n = self.Len()
+        nrm = L.f32c(Normals).reshape(-1, 3)
+        if len(nrm) != n:
+            raise ValueError("one normal per point of the tree is required")
+        ids = np.ascontiguousarray(Ids, dtype=np.int64).reshape(-1)
+        k = len(ids)
+        fpfh = np.empty((k, 33), np.float32)
+        xyz = np.empty((k, 3), np.float32)
+        counts = np.empty((k, 3, 11), np.int32)
+        pairs = np.empty(k, np.int32)
+        n_spfh = C.c_int64()
+        L.check(L.lib().pcgx_kdtree_fpfh_at(self._h, L.ptr(nrm), float(radius), L.ptr(ids), k, L.ptr(fpfh), L.ptr(xyz),
+                                            L.ptr(counts), L.ptr(pairs), C.byref(n_spfh)))
+        return fpfh, xyz, counts, pairs, n_spfh.value
+
+    def FPFHAtDev(self, radius, d_normals, d_ids, cap, d_fpfh, d_xyz, d_n_ids=0, d_counts=0, d_pairs=0, d_n_spfh=0,
+                  stream=0):
+        """Device-resident FPFHAt with a fixed capacity: raw device addresses (e.g. torch .data_ptr()); d_ids int32
+        [cap] and d_n_ids one int32 (0: all cap slots), e.g. what ISSKeypointsDev writes; d_fpfh float32 [33 cap],
+        d_xyz float32 [3 cap], d_counts int32 [33 cap], d_pairs int32 [cap], d_n_spfh one int32.  Slots from
+        clamp(*d_n_ids, 0, cap) on, and slots whose id is outside [0, Len()) (the -1 padding), get zero rows: the
+        matcher's "no descriptor".  Enqueued on `stream`, returns without waiting; nothing is read back."""
+        opt = lambda a: L.ptr(int(a)) if a else None  # noqa: E731
+        L.check(L.lib().pcgx_kdtree_fpfh_at_dev(
+            self._h, L.ptr(int(d_normals)), float(radius), opt(d_ids), int(cap), opt(d_n_ids), opt(d_fpfh), opt(d_xyz),
+            opt(d_counts), opt(d_pairs), opt(d_n_spfh), L.ptr(stream) if stream else None))
 
     # -- extension (no reference parity): keypoints, what a large cloud is described and matched at
     def LocalMaxima(self, radius, Score):
