@@ -585,6 +585,88 @@ func PoseFromCorrespondences(src, dst [][3]float32, pairs [][2]int64, samples []
 	return r, nil
 }
 
+// ScoreResult is what ScorePoses returns: per pose the number of source points that land within maxDist of the tree's
+// cloud and the float64 sum of their DistSq; Best is the live pose with the largest count (the smallest index among
+// equals, -1 if no pose is live: a pose of sixteen zeros is dead) and Pose its sixteen numbers.
+type ScoreResult struct {
+	Counts []int64
+	Sums   []float64
+	Best   int64
+	Pose   [16]float32
+}
+
+// ScorePoses scores poses (column-major, each takes src onto the tree's cloud) on the whole clouds in one call
+// (extension: no reference parity; include/pcgx.h, "score poses"): the verification a pose picked from correspondences
+// alone needs on scenes with repeated structure.
+func (k *KDTree) ScorePoses(src []mat.Vec3, poses [][16]float32, maxDist float32) (ScoreResult, error) {
+	runtime.LockOSThread() // the error text is thread-local on the C side: call and pcgx_last_error on one OS thread
+	defer runtime.UnlockOSThread()
+	defer runtime.KeepAlive(k) // the finalizer must not free the handle while a call is in flight
+	var r ScoreResult
+	r.Best = -1
+	n, np := len(src), len(poses)
+	r.Counts = make([]int64, np)
+	r.Sums = make([]float64, np)
+	var ps, pm *C.float
+	var pc *C.int64_t
+	var pd *C.double
+	if n > 0 {
+		ps = (*C.float)(unsafe.Pointer(&src[0]))
+	}
+	if np > 0 {
+		pm = (*C.float)(unsafe.Pointer(&poses[0]))
+		pc = (*C.int64_t)(unsafe.Pointer(&r.Counts[0]))
+		pd = (*C.double)(unsafe.Pointer(&r.Sums[0]))
+	}
+	var best C.int64_t
+	rc := C.pcgx_kdtree_score_poses(k.t.h, ps, C.int64_t(n), pm, C.int64_t(np), C.float(maxDist), pc, pd, &best,
+		(*C.float)(unsafe.Pointer(&r.Pose[0])))
+	runtime.KeepAlive(src)
+	runtime.KeepAlive(poses)
+	if err := status(rc); err != nil {
+		return ScoreResult{}, err
+	}
+	r.Best = int64(best)
+	return r, nil
+}
+
+// PoseSelect picks the k best hypotheses of a pose estimation for ScorePoses (include/pcgx.h, pcgx_pose_select): status 0
+// and count >= 3, by count descending, then by index; ids[j] and poses[j], -1 and a dead pose behind the last one.
+func PoseSelect(hypStatus []int32, counts []int64, poses [][16]float32, k int) (ids []int64, out [][16]float32, selected int, err error) {
+	runtime.LockOSThread()
+	defer runtime.UnlockOSThread()
+	n := len(hypStatus)
+	if len(counts) != n || len(poses) != n {
+		return nil, nil, 0, errors.New("pcgx: status, counts and poses must have one entry per hypothesis")
+	}
+	if k < 0 {
+		k = 0
+	}
+	ids = make([]int64, k)
+	out = make([][16]float32, k)
+	var pst *C.int32_t
+	var pct, pid *C.int64_t
+	var pps, pout *C.float
+	if n > 0 {
+		pst = (*C.int32_t)(unsafe.Pointer(&hypStatus[0]))
+		pct = (*C.int64_t)(unsafe.Pointer(&counts[0]))
+		pps = (*C.float)(unsafe.Pointer(&poses[0]))
+	}
+	if k > 0 {
+		pid = (*C.int64_t)(unsafe.Pointer(&ids[0]))
+		pout = (*C.float)(unsafe.Pointer(&out[0]))
+	}
+	var nSel C.int64_t
+	rc := C.pcgx_pose_select(pst, pct, pps, C.int64_t(n), C.int64_t(k), pid, pout, &nSel)
+	runtime.KeepAlive(hypStatus)
+	runtime.KeepAlive(counts)
+	runtime.KeepAlive(poses)
+	if err := status(rc); err != nil {
+		return nil, nil, 0, err
+	}
+	return ids, out, int(nSel), nil
+}
+
 // Covariance modes of KDTree.Covariances (include/pcgx.h, pcgx_kdtree_covariances).
 const (
 	CovRaw   = int(C.PCGX_COV_RAW)   // the covariance as it is

@@ -1007,6 +1007,64 @@ PCGX_API pcgx_status pcgx_pose_from_correspondences_dev(const float *d_src_xyz, 
  * across. */
 PCGX_API int32_t pcgx_pose_tile(void);
 
+/* ------------------------------------------- score poses (extension: no reference parity)
+ * NOT in the reference.  pcgx_pose_from_correspondences picks its pose by the inliers among the CORRESPONDENCES; on a
+ * scene with repeated structure a wrong pose can collect more of them than the right one.  This call counts, for each of
+ * K poses, how many points of the WHOLE source cloud land within max_dist of the tree's cloud ("fitness"), and sums
+ * their squared distances ("inlier RMSE" = sqrt(sum / count)), in one call, with nothing written per pair.  This comment
+ * is the contract, tests/score_oracle.py restates it.
+ * Dead pose: a pose whose 16 numbers all compare equal to 0 (what a rejected hypothesis has, what pcgx_pose_select pads
+ *   with).  Its count is 0, its sum is 0, it is never the best.  Every other pose is live (one with a NaN too).
+ * Pair rule: for a live pose k and point i, x' = pcgx_mat4_transform(pose_k, p_i): float32, nothing fused, the division
+ *   by w included.  The pair is found iff x' is finite in all three coordinates and
+ *   pcgx_kdtree_nearest_batch(t, x', 1, max_dist, 0, ...) returns an id >= 0 -- on every handle that call accepts
+ *   (after DeletePoint, PCGX_GRID=0 / 2, every point deleted), its rule at DistSq == max_dist^2 included; its DistSq is
+ *   the one that call returns (which of several tied points it names does not matter).
+ * counts[k]: the number of found pairs; exact, the same on every call.
+ * sum_dist_sq[k]: the float64 sum of the found pairs' float32 DistSq.  The order is the library's: two conforming
+ *   values differ by summation rounding only.  This implementation adds in a fixed order (lanes by a fixed tree, the
+ *   waves of a workgroup, then the workgroups' partials in tile order; no floating-point atomics): the same handle,
+ *   points, poses and chunk give the same bits on every call.
+ * best: the live pose with the largest count, the smallest k among equals; -1 when no pose is live.  pose16: its 16
+ *   numbers as given, or all zero.
+ * Errors (PCGX_E_INVALID): a NULL array with a positive count, NULL scalar outputs, negative counts, n or K above
+ *   2^31 - 1, max_dist not finite or not > 0.  K == 0 and n == 0 are PCGX_OK (counts 0; best the first live pose).
+ * Temporaries (the library's arena): 36 n bytes for the source in Morton order over its own box, and per round of
+ *   `chunk` poses 24 chunk n bytes for the pairs the grid cannot certify (ties, DistSq == max_dist^2, sparse regions) --
+ *   sized for the worst case, a tree of coincident points, where that is every pair -- plus 48 bytes per workgroup.
+ *   chunk = max(1, min(K, 65535, 2^22 / n)): at most max(96 MiB, 24 n bytes).  PCGX_SCORE_CHUNK=<poses> in the
+ *   environment, read per call, forces the chunk (held to what an int32 slot index allows); counts do not depend on it.
+ *   Handles with deletions or without a grid take one pose at a time through the handle's own search: 20 n bytes. */
+PCGX_API pcgx_status pcgx_kdtree_score_poses(const pcgx_kdtree *t, const float *src_xyz /* [3 n] */, int64_t n,
+                                             const float *poses /* [16 K], column-major */, int64_t K, float max_dist,
+                                             int64_t *counts /* [K] */, double *sum_dist_sq /* [K], may be NULL */,
+                                             int64_t *best, float pose16[16]);
+/* Same, every array device resident, enqueued on `stream` (NULL: the library's); returns without waiting, reads nothing
+ * back.  Counts are int32.  The scalar outputs go to d_result, PCGX_SCORE_RESULT_WORDS 4-byte words: int32 best,
+ * best_count, the number of live poses, n; the best's sum as one float64 in words 4..5 (0 without a best); words 6..7
+ * zero; the float32 pose in words 8..23.  Every word is written on every call, K == 0 and n == 0 included. */
+#define PCGX_SCORE_RESULT_WORDS 24
+PCGX_API pcgx_status pcgx_kdtree_score_poses_dev(const pcgx_kdtree *t, const float *d_src_xyz, int64_t n,
+                                                 const float *d_poses, int64_t K, float max_dist,
+                                                 int32_t *d_counts /* [K], may be NULL */,
+                                                 double *d_sums /* [K], may be NULL */, void *d_result, void *stream);
+/* Source points per workgroup of the scoring kernels: the boundary the tests put n across. */
+PCGX_API int32_t pcgx_score_tile(void);
+
+/* The hypotheses of a pcgx_pose_from_correspondences call worth scoring: among those with status 0 and count >= 3, by
+ * count descending, then by h ascending.  Slot j < K gets the j-th: ids[j] = h and its 16 pose numbers; the slots behind
+ * the last such hypothesis get id -1 and an all-zero (dead) pose.  *n_selected = min(K, the number of such hypotheses).
+ * Every slot of [0, K) is written on every call.  PCGX_E_INVALID: negative counts, n_hyp or K above 2^31 - 1, a NULL
+ * input with n_hyp > 0, a NULL output with K > 0, NULL n_selected.  The host form is plain host code. */
+PCGX_API pcgx_status pcgx_pose_select(const int32_t *status /* [n_hyp] */, const int64_t *counts /* [n_hyp] */,
+                                      const float *poses /* [16 n_hyp] */, int64_t n_hyp, int64_t K,
+                                      int64_t *ids /* [K] */, float *out_poses /* [16 K] */, int64_t *n_selected);
+/* Same on the device: int32 status and counts, exactly what pcgx_pose_from_correspondences_dev writes; int32 ids;
+ * n_selected is a device word.  Enqueued on `stream`, nothing read back. */
+PCGX_API pcgx_status pcgx_pose_select_dev(const int32_t *d_status, const int32_t *d_counts, const float *d_poses,
+                                          int64_t n_hyp, int64_t K, int32_t *d_ids, float *d_out_poses,
+                                          int32_t *d_n_selected, void *stream);
+
 /* ------------------------------------------- k nearest neighbours (extension: no reference parity)
  * NOT in the reference: pcgol's KD-tree answers Nearest (k = 1) and Range (a fixed radius).  For each query i: the k
  * points p of the tree with the smallest (DistSq(p, q[i]), id) in lexicographic order, among those with

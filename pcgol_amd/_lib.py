@@ -270,6 +270,11 @@ SIGNATURES = {
     "pcgx_pose_from_correspondences_dev": (_i32, [_vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _vp, _i64, _f32, _f32, _i32,
                                                   _vp, _vp, _vp, _vp, _vp, _vp]),
     "pcgx_pose_tile": (_i32, []),
+    "pcgx_kdtree_score_poses": (_i32, [_vp, _vp, _i64, _vp, _i64, _f32, _vp, _vp, C.POINTER(_i64), _vp]),
+    "pcgx_kdtree_score_poses_dev": (_i32, [_vp, _vp, _i64, _vp, _i64, _f32, _vp, _vp, _vp, _vp]),
+    "pcgx_score_tile": (_i32, []),
+    "pcgx_pose_select": (_i32, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, C.POINTER(_i64)]),
+    "pcgx_pose_select_dev": (_i32, [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp]),
     "pcgx_kdtree_knearest": (_i32, [_vp, _vp, _i64, _i32, _f32, _vp, _vp, _vp]),
     "pcgx_kdtree_knearest_dev": (_i32, [_vp, _vp, _i64, _i32, _f32, _vp, _vp, _vp, _vp]),
     "pcgx_kdtree_covariances": (_i32, [_vp, _vp, _i64, _i32, _f32, _i32, _f32, _vp, _vp, _vp, _vp]),

@@ -90,3 +90,101 @@ def ReadResult(words):
     w = np.ascontiguousarray(words, np.int32).reshape(RESULT_WORDS)
     return dict(found=bool(w[0]), best=int(w[1]), best_count=int(w[2]), refined=bool(w[3]), n_inliers=int(w[4]),
                 m=int(w[5]), pose=w[8:24].view(np.float32).copy())
+
+
+# ---- verification on the whole clouds (include/pcgx.h, "score poses")
+
+def ScoreTile():
+    """Source points per workgroup of the scoring kernels (the boundary the tests put n across)."""
+    return int(L.lib().pcgx_score_tile())
+
+
+def _poses(a):
+    a = L.f32c(a).reshape(-1, 16)
+    return a
+
+
+def ScorePoses(tree, P, poses, MaxDist):
+    """-> (counts, sums, best, pose).  tree: the KDTree over the target cloud; P (n, 3) float32; poses (K, 16) float32,
+    column-major.  counts (K,) int64: the points of P that land within MaxDist of the tree's cloud under each pose; sums
+    (K,) float64: the sum of their DistSq; best: the live pose with the largest count (the smallest k among equals, -1
+    if none is live -- a pose of sixteen zeros is dead); pose: its sixteen numbers, or zeros."""
+    p = _xyz(P, "P") if len(P) else np.zeros((0, 3), np.float32)
+    m = _poses(poses)
+    K = len(m)
+    counts = np.zeros(K, np.int64)
+    sums = np.zeros(K, np.float64)
+    best = C.c_int64(-1)
+    pose = np.zeros(16, np.float32)
+    L.check(L.lib().pcgx_kdtree_score_poses(tree._h, L.ptr(p) if len(p) else None, len(p), L.ptr(m) if K else None, K,
+                                            float(np.float32(MaxDist)), L.ptr(counts) if K else None,
+                                            L.ptr(sums) if K else None, C.byref(best), L.ptr(pose)))
+    return counts, sums, best.value, pose
+
+
+def ScorePosesDev(tree, d_src_xyz, n, d_poses, K, MaxDist, d_result, d_counts=0, d_sums=0, stream=0):
+    """Device-resident ScorePoses: raw device addresses.  d_src_xyz float32 [3 n], d_poses float32 [16 K], d_result
+    RESULT_WORDS 4-byte words (ReadScore); optional d_counts int32 [K], d_sums float64 [K].  Enqueued on `stream`,
+    returns without waiting, reads nothing back."""
+
+    def opt(a):
+        return L.ptr(int(a)) if a else None
+
+    L.check(L.lib().pcgx_kdtree_score_poses_dev(tree._h, opt(d_src_xyz), int(n), opt(d_poses), int(K),
+                                                float(np.float32(MaxDist)), opt(d_counts), opt(d_sums), opt(d_result),
+                                                L.ptr(stream) if stream else None))
+
+
+def ReadScore(words):
+    """the record ScorePosesDev writes, from its host copy (24 int32 words) -> dict"""
+    w = np.ascontiguousarray(words, np.int32).reshape(RESULT_WORDS)
+    return dict(best=int(w[0]), best_count=int(w[1]), live=int(w[2]), n=int(w[3]), sum=float(w[4:6].view(np.float64)[0]),
+                pose=w[8:24].view(np.float32).copy())
+
+
+def SelectPoses(status, counts, poses, K):
+    """-> (ids, poses, n_selected): the K best hypotheses of an EstimatePose(per_hypothesis=True) call -- status 0 and
+    count >= 3, by count descending, then by index ascending; ids (K,) int64 and poses (K, 16) float32, -1 and zeros
+    in the slots behind the last one."""
+    st = np.ascontiguousarray(status, np.int32)
+    ct = np.ascontiguousarray(counts, np.int64)
+    m = _poses(poses)
+    if not (len(st) == len(ct) == len(m)):
+        raise ValueError("status, counts and poses must have one row per hypothesis")
+    K = int(K)
+    ids = np.empty(max(K, 0), np.int64)
+    out = np.empty((max(K, 0), 16), np.float32)
+    n_sel = C.c_int64(0)
+    nh = len(st)
+    L.check(L.lib().pcgx_pose_select(L.ptr(st) if nh else None, L.ptr(ct) if nh else None, L.ptr(m) if nh else None, nh,
+                                     K, L.ptr(ids) if K > 0 else None, L.ptr(out) if K > 0 else None, C.byref(n_sel)))
+    return ids, out, n_sel.value
+
+
+def SelectPosesDev(d_status, d_counts, d_poses, n, K, d_ids, d_out_poses, d_n_selected, stream=0):
+    """Device-resident SelectPoses over what EstimatePoseDev writes: d_status int32 [n], d_counts int32 [n], d_poses
+    float32 [16 n] -> d_ids int32 [K], d_out_poses float32 [16 K], d_n_selected int32 [1].  Enqueued on `stream`."""
+
+    def opt(a):
+        return L.ptr(int(a)) if a else None
+
+    L.check(L.lib().pcgx_pose_select_dev(opt(d_status), opt(d_counts), opt(d_poses), int(n), int(K), opt(d_ids),
+                                         opt(d_out_poses), opt(d_n_selected), L.ptr(stream) if stream else None))
+
+
+def EstimatePoseVerified(tree_Q, P, Q, pairs, n, MaxDist, K=16, VerifyDist=None, EdgeSimilarity=0.9, Refine=True, seed=None,
+                         samples=None):
+    """-> (found, pose, info).  EstimatePose over the pairs, then its K best hypotheses scored on the whole clouds: the
+    pose under which most points of P land within VerifyDist (default MaxDist) of Q, the cloud tree_Q was built over.
+    info: `estimate` (EstimatePose's own found, pose and info: its best is the one most CORRESPONDENCES agree on),
+    `ids` (the selected hypotheses), `counts` and `sums` (their whole-cloud scores), `best_slot`, `best` (the verified
+    hypothesis's index, -1 if none) and `agree` (the two name the same hypothesis).  found is False when no hypothesis
+    agrees with three pairs."""
+    found, pose, inl, est = EstimatePose(P, Q, pairs, n, MaxDist, EdgeSimilarity=EdgeSimilarity, Refine=Refine, seed=seed,
+                                         samples=samples, per_hypothesis=True)
+    ids, sel, n_sel = SelectPoses(est["status"], est["counts"], est["poses"], K)
+    counts, sums, slot, vpose = ScorePoses(tree_Q, P, sel, MaxDist if VerifyDist is None else VerifyDist)
+    best = int(ids[slot]) if slot >= 0 else -1
+    info = dict(estimate=dict(found=found, pose=pose, inliers=inl, **est), ids=ids, n_selected=n_sel, counts=counts,
+                sums=sums, best_slot=slot, best=best, agree=best == est["best"])
+    return slot >= 0, vpose, info

@@ -362,6 +362,46 @@ inline PoseResult pose_from_correspondences(const std::vector<Vec3> &src, const 
   return r;
 }
 
+// K poses scored on the whole clouds (extension: no reference parity; include/pcgx.h, "score poses"): for each pose the
+// number of points of src that land within maxDist of the tree's cloud and the float64 sum of their DistSq; best: the
+// live pose with the largest count (the smallest k among equals, -1 if none is live: a pose of sixteen zeros is dead).
+struct ScoreResult {
+  std::vector<int64_t> counts;
+  std::vector<double> sums;
+  int64_t best = -1;
+  Mat4 pose{};
+};
+inline ScoreResult score_poses(const KDTree &tree, const std::vector<Vec3> &src, const std::vector<Mat4> &poses,
+                               float maxDist) {
+  ScoreResult r;
+  const int64_t n = (int64_t)src.size(), K = (int64_t)poses.size();
+  r.counts.assign((size_t)K, 0);
+  r.sums.assign((size_t)K, 0.0);
+  check(pcgx_kdtree_score_poses(tree.handle(), n ? src[0].data() : nullptr, n, K ? poses[0].data() : nullptr, K, maxDist,
+                                K ? r.counts.data() : nullptr, K ? r.sums.data() : nullptr, &r.best, r.pose.data()));
+  return r;
+}
+
+// The K best hypotheses of a pose_from_correspondences call (status 0, count >= 3; by count descending, then by index):
+// ids[j] and poses[j], -1 and a dead pose in the slots behind the last one.
+struct PoseSelection {
+  std::vector<int64_t> ids;
+  std::vector<Mat4> poses;
+  int64_t selected = 0;
+};
+inline PoseSelection pose_select(const std::vector<int32_t> &status, const std::vector<int64_t> &counts,
+                                 const std::vector<Mat4> &poses, int64_t K) {
+  PoseSelection r;
+  const int64_t n = (int64_t)status.size();
+  if (counts.size() != status.size() || poses.size() != status.size())
+    throw Error(PCGX_E_INVALID, "pose_select: status, counts and poses must have one entry per hypothesis");
+  r.ids.assign((size_t)(K > 0 ? K : 0), -1);
+  r.poses.assign((size_t)(K > 0 ? K : 0), Mat4{});
+  check(pcgx_pose_select(n ? status.data() : nullptr, n ? counts.data() : nullptr, n ? poses[0].data() : nullptr, n, K,
+                         K > 0 ? r.ids.data() : nullptr, K > 0 ? r.poses[0].data() : nullptr, &r.selected));
+  return r;
+}
+
 class VoxelGrid {  // pc/filter/voxelgrid/voxelgrid.go:23-33 + option.go:14-18
  public:
   Vec3 LeafSize;

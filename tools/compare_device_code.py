@@ -78,6 +78,9 @@ def split(asm):
 
 
 def compare(src, here, there):
+    if not os.path.exists(os.path.join(there, "pcgol_amd", "csrc", src)):  # a file the other commit does not have
+        a = split(device_asm(here, src))
+        return src, sum(k.startswith("fn ") for k in a), sum(k.startswith("meta ") for k in a), None
     a, b = split(device_asm(here, src)), split(device_asm(there, src))
     differing = sorted(k for k in set(a) | set(b) if a.get(k) != b.get(k))
     return src, sum(k.startswith("fn ") for k in a), sum(k.startswith("meta ") for k in a), differing
@@ -98,11 +101,15 @@ def main():
             results = list(pool.map(lambda s: compare(s, ROOT, there), sources))
     n_fn = n_kernels = n_diff = 0
     for src, fns, kernels, differing in results:
+        if differing is None:  # (nothing to compare with: every existing function is in the other files)
+            print("%-24s %3d functions (%3d kernels): new, not in %s" % (src, fns, kernels, args.rev))
+            continue
         print("%-24s %3d functions (%3d kernels): %s" % (src, fns, kernels, "identical" if not differing else "DIFFER"))
         for k in differing:
             print("    " + k)
         n_fn, n_kernels, n_diff = n_fn + fns, n_kernels + kernels, n_diff + len(differing)
-    print("%d files, %d functions, %d kernels compared with %s: %d differ" % (len(results), n_fn, n_kernels, args.rev, n_diff))
+    print("%d files, %d functions, %d kernels compared with %s: %d differ"
+          % (sum(r[3] is not None for r in results), n_fn, n_kernels, args.rev, n_diff))
     return 1 if n_diff else 0
 
 
