@@ -326,6 +326,56 @@ func (k *KDTree) NormalsAt(q []mat.Vec3, radius float32, viewpoint mat.Vec3, min
 	return normals, curvature, counts, nil
 }
 
+// MLS smooths the tree's own points by moving least squares (extension: no reference parity; include/pcgx.h,
+// pcgx_kdtree_mls): every point is projected onto the plane (order 1) or the quadratic height field (order 2) fitted
+// to its radius neighbourhood with Gauss weights of width sigma (<= 0: the radius).  The result is in the tree's id
+// order.  kinds: 0 the point came back unchanged (normal zero), 1 projected onto the plane, 2 onto the polynomial.
+func (k *KDTree) MLS(radius, sigma float32, order, minNeighbors int, viewpoint mat.Vec3) (points, normals []mat.Vec3, kinds, counts []int32, err error) {
+	return k.MLSAt(nil, radius, sigma, order, minNeighbors, viewpoint)
+}
+
+// MLSAt is MLS for arbitrary query points; q == nil takes the tree's own points.
+func (k *KDTree) MLSAt(q []mat.Vec3, radius, sigma float32, order, minNeighbors int, viewpoint mat.Vec3) ([]mat.Vec3, []mat.Vec3, []int32, []int32, error) {
+	runtime.LockOSThread() // the error text is thread-local on the C side: call and pcgx_last_error on one OS thread
+	defer runtime.UnlockOSThread()
+	defer runtime.KeepAlive(k) // the finalizer must not free the handle while a call is in flight
+	var qp *C.float
+	n := len(q)
+	if q == nil {
+		var ln C.int64_t
+		if err := status(C.pcgx_kdtree_len(k.t.h, &ln)); err != nil {
+			return nil, nil, nil, nil, err
+		}
+		n = int(ln)
+	} else if n > 0 {
+		qp = (*C.float)(unsafe.Pointer(&q[0]))
+	}
+	points := make([]mat.Vec3, n)
+	normals := make([]mat.Vec3, n)
+	kinds := make([]int32, n)
+	counts := make([]int32, n)
+	if n == 0 {
+		return points, normals, kinds, counts, nil
+	}
+	if !(sigma > 0) {
+		sigma = radius
+	}
+	vp := viewpoint
+	rc := C.pcgx_kdtree_mls(k.t.h, qp, C.int64_t(n), C.float(radius), C.float(sigma), C.int32_t(order),
+		C.int32_t(minNeighbors), (*C.float)(unsafe.Pointer(&vp[0])), (*C.float)(unsafe.Pointer(&points[0])),
+		(*C.float)(unsafe.Pointer(&normals[0])), (*C.int32_t)(unsafe.Pointer(&kinds[0])),
+		(*C.int32_t)(unsafe.Pointer(&counts[0])))
+	runtime.KeepAlive(q)
+	runtime.KeepAlive(points)
+	runtime.KeepAlive(normals)
+	runtime.KeepAlive(kinds)
+	runtime.KeepAlive(counts)
+	if err := status(rc); err != nil {
+		return nil, nil, nil, nil, err
+	}
+	return points, normals, kinds, counts, nil
+}
+
 // FPFH returns the Fast Point Feature Histogram of every point of the tree over its radius neighbourhood (extension: no
 // reference parity; include/pcgx.h, pcgx_kdtree_fpfh): 33 numbers per point in id order, eleven bins for each of the
 // three pair features, each feature summing to 200 where the point has valid pairs.  normals: one per point in id

@@ -763,6 +763,46 @@ PCGX_API pcgx_status pcgx_kdtree_normals_dev(const pcgx_kdtree *t, const float *
                                              const float viewpoint[3], int32_t min_neighbors, float *d_normals,
                                              float *d_curvature, int32_t *d_counts, void *stream);
 
+/* ------------------------------------------- moving least squares (extension: no reference parity)
+ * NOT in the reference.  Moving-least-squares smoothing (Alexa et al. 2003; PCL's MovingLeastSquares with the SIMPLE
+ * projection): every query is projected onto a low-order polynomial fitted to its radius neighbourhood and comes back
+ * with the polynomial's normal -- what puts noisy points back onto the surface every other stage assumes they lie on.
+ * This comment is the contract; tests/mls_oracle.py restates it in float64 NumPy.
+ * Queries and neighbourhood: pcgx_kdtree_normals' conventions.  q == NULL: the tree's own points, nq must equal Len(),
+ *   output in id order, deleted ids included.  N(q) is exactly the set pcgx_kdtree_range_count counts on that handle
+ *   (float32 DistSq < radius^2); count = |N(q)| (exact).  Outputs must not alias q.
+ * Unchanged (kind 0): count < max(min_neighbors, 3), or all neighbours coincide (the exact box test of normals), or the
+ *   float64 trace of C is <= 0.  points holds the query's own bits (a NaN query stays NaN), normals 0.
+ * Plane (kind 1): C, mean and the eigenvectors of C's eigenvalues l0 <= l1 <= l2 exactly as normals compute them, with
+ *   d = p - q in float64.  n: the unit eigenvector of l0; u, v: the other two, unit and orthogonal.  The origin is the
+ *   query's projection onto the plane through the centroid, d0 = (mean . n) n.  Output q + d0, normal n.  order == 1
+ *   stops here.
+ * Polynomial (kind 2): order == 2 and count >= 6.  Per neighbour, all float64: e = d - d0, h = e . n,
+ *   a = (e . u) / radius, b = (e . v) / radius, w = exp(-|e|^2 / sigma^2).  Basis, in this order:
+ *   B = (1, a, b, a^2, a b, b^2); normal equations M = sum w B B^T, g = sum w B h.  The solve is Cholesky in the basis'
+ *   order; it fails when sum w is not > 0, or when a pivot s_k = M_kk - sum_j L_kj^2 is not greater than 1e-10 M_kk
+ *   (the smallest s_k / M_kk is the pivot ratio).  A failed solve gives kind 1.  With c = M^-1 g: |c0| > radius (the
+ *   fitted height at the query lies outside its own neighbourhood) gives kind 1; otherwise the output is
+ *   q + d0 + c0 n and the normal n - (c1 / radius) u - (c2 / radius) v, normalised.
+ * Every kind: normals of kind 1 and 2 are turned towards the viewpoint (NULL: the origin) as pcgx_kdtree_normals
+ *   turns them.  Positions and normals are computed in float64 and rounded to float32 once.  The result does not
+ *   depend on which u, v the eigen-solve returns (the basis spans all polynomials of degree <= 2, the weight depends
+ *   on |e| only); only the pivot ratio does, so a solve at the threshold may fall either way.  The same input gives
+ *   the same bits on every call: no float atomics.
+ * PCGX_E_INVALID: radius or sigma not finite and > 0, order outside {1, 2}, a NULL tree, nq < 0, q == NULL with
+ *   nq != Len(), NULL points with nq > 0.  nq == 0 is PCGX_OK.  normals, kinds and counts may be NULL.  Always
+ *   computed on the device.  Cost: pcgx_kdtree_normals' enumeration twice for order 2, once for order 1. */
+enum { PCGX_MLS_UNCHANGED = 0, PCGX_MLS_PLANE = 1, PCGX_MLS_POLY = 2 };
+PCGX_API pcgx_status pcgx_kdtree_mls(const pcgx_kdtree *t, const float *q, int64_t nq, float radius, float sigma,
+                                     int32_t order, int32_t min_neighbors, const float viewpoint[3],
+                                     float *points /* [3nq] */, float *normals /* [3nq], may be NULL */,
+                                     int32_t *kinds /* [nq], may be NULL */, int32_t *counts /* [nq], may be NULL */);
+/* Same, every array device resident, enqueued on `stream` (NULL: the library's); returns without waiting. */
+PCGX_API pcgx_status pcgx_kdtree_mls_dev(const pcgx_kdtree *t, const float *d_q, int64_t nq, float radius, float sigma,
+                                         int32_t order, int32_t min_neighbors, const float viewpoint[3],
+                                         float *d_points, float *d_normals, int32_t *d_kinds, int32_t *d_counts,
+                                         void *stream);
+
 /* ------------------------------------------- FPFH descriptors (extension: no reference parity)
  * NOT in the reference.  The Fast Point Feature Histogram (Rusu, Blodow, Beetz 2009) of every point of the tree: 33
  * numbers per point, the input of feature-based coarse alignment, which finds the starting pose every ICP here needs.

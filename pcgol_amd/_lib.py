@@ -251,6 +251,8 @@ SIGNATURES = {
     "pcgx_sac_plane_is_in": (_i32, [_vp, C.POINTER(SacPlane), _vp, _f32, C.POINTER(_i32)]),
     "pcgx_kdtree_normals": (_i32, [_vp, _vp, _i64, _f32, _vp, _i32, _vp, _vp, _vp]),
     "pcgx_kdtree_normals_dev": (_i32, [_vp, _vp, _i64, _f32, _vp, _i32, _vp, _vp, _vp, _vp]),
+    "pcgx_kdtree_mls": (_i32, [_vp, _vp, _i64, _f32, _f32, _i32, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "pcgx_kdtree_mls_dev": (_i32, [_vp, _vp, _i64, _f32, _f32, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "pcgx_kdtree_fpfh": (_i32, [_vp, _vp, _f32, _vp, _vp, _vp]),
     "pcgx_kdtree_fpfh_dev": (_i32, [_vp, _vp, _f32, _vp, _vp, _vp, _vp]),
     "pcgx_kdtree_fpfh_at": (_i32, [_vp, _vp, _f32, _vp, _i64, _vp, _vp, _vp, _vp, C.POINTER(_i64)]),

@@ -168,6 +168,30 @@ class KDTree {  // pc/storage/kdtree/kdtree.go:14-23
                               n ? r.normals[0].data() : nullptr, r.curvature.data(), r.counts.data()));
     return r;
   }
+  // Moving-least-squares smoothing over radius neighbourhoods (extension: no reference parity; include/pcgx.h,
+  // pcgx_kdtree_mls): every query projected onto the plane (order 1) or the quadratic height field (order 2) fitted to
+  // its neighbourhood with Gauss weights of width sigma (<= 0: the radius).  An empty `queries` takes the tree's own
+  // points, in id order.  kinds: PCGX_MLS_UNCHANGED (the query came back as it was, normal {0, 0, 0}), _PLANE, _POLY.
+  struct MLSResult {
+    std::vector<Vec3> points;
+    std::vector<Vec3> normals;
+    std::vector<int32_t> kinds;
+    std::vector<int32_t> counts;
+  };
+  MLSResult MLS(float radius, float sigma = 0.0f, int32_t order = 2, int32_t minNeighbors = 3,
+                const Vec3 &viewpoint = Vec3{0.0f, 0.0f, 0.0f}, const std::vector<Vec3> &queries = {}) const {
+    const bool own = queries.empty();
+    const int64_t n = own ? Len() : (int64_t)queries.size();
+    MLSResult r;
+    r.points.resize((size_t)n);
+    r.normals.resize((size_t)n);
+    r.kinds.resize((size_t)n);
+    r.counts.resize((size_t)n);
+    check(pcgx_kdtree_mls(h_.get(), own ? nullptr : queries[0].data(), n, radius, sigma > 0.0f ? sigma : radius, order,
+                          minNeighbors, viewpoint.data(), n ? r.points[0].data() : nullptr,
+                          n ? r.normals[0].data() : nullptr, r.kinds.data(), r.counts.data()));
+    return r;
+  }
   // FPFH descriptors of the tree's own points over radius neighbourhoods (extension: no reference parity;
   // include/pcgx.h, pcgx_kdtree_fpfh).  `normals`: one per point in id order, e.g. Normals(radius).normals.  counts:
   // the valid pairs per feature and bin (3 x 11, feature major), pairs: how many there are.  All in id order.

@@ -1,7 +1,8 @@
 """pc/storage/kdtree mirror: KDTree on the GPU behind the storage.Search shape
 (pc/storage/search.go:13-17): Vec3At / Len / Nearest, plus batched NearestBatch, and extensions with no
-reference counterpart: surface normals (Normals), FPFH descriptors (FPFH, FPFHAt), keypoints (LocalMaxima,
-ISSKeypoints), k nearest neighbours (KNearest) and their covariances (Covariances)."""
+reference counterpart: surface normals (Normals), moving-least-squares smoothing (MLS), FPFH descriptors
+(FPFH, FPFHAt), keypoints (LocalMaxima, ISSKeypoints), k nearest neighbours (KNearest) and their covariances
+(Covariances)."""
 import ctypes as C
 
 import numpy as np
@@ -172,6 +173,43 @@ class KDTree:
             self._h, L.ptr(int(d_q)) if d_q else None, int(nq), float(radius), L.ptr(vp), int(MinNeighbors),
             L.ptr(int(d_normals)), L.ptr(int(d_curvature)) if d_curvature else None,
             L.ptr(int(d_counts)) if d_counts else None, L.ptr(stream) if stream else None))
+
+    # -- extension (no reference parity): moving-least-squares smoothing, which puts noisy points back onto the surface
+    def MLS(self, radius, Sigma=None, Order=2, MinNeighbors=3, Viewpoint=(0.0, 0.0, 0.0), Queries=None):
+        """Every query projected onto the polynomial (Order 2: a quadratic height field over the neighbourhood's
+        plane; Order 1: the plane) fitted to its radius neighbourhood (DistSq < radius^2, Range's set) with Gauss
+        weights of width Sigma (None: the radius) -> (points (n,3) float32, normals (n,3) float32, kinds (n,) int32,
+        counts (n,) int32).  Queries None: the tree's own points, in id order.  kinds: 0 the query came back
+        unchanged (fewer than max(MinNeighbors, 3) neighbours, or all of them at one place; normal 0), 1 projected
+        onto the plane, 2 onto the polynomial (include/pcgx.h, pcgx_kdtree_mls)."""
+        q = None if Queries is None else L.f32c(Queries).reshape(-1, 3)
+        n = self.Len() if q is None else len(q)
+        vp = L.f32c(Viewpoint).reshape(3)
+        points = np.empty((n, 3), np.float32)
+        normals = np.empty((n, 3), np.float32)
+        kinds = np.empty(n, np.int32)
+        counts = np.empty(n, np.int32)
+        L.check(L.lib().pcgx_kdtree_mls(self._h, L.ptr(q), n, float(radius), float(radius if Sigma is None else Sigma),
+                                        int(Order), int(MinNeighbors), L.ptr(vp), L.ptr(points), L.ptr(normals),
+                                        L.ptr(kinds), L.ptr(counts)))
+        return points, normals, kinds, counts
+
+    def MLSDev(self, radius, d_points, d_normals=0, d_kinds=0, d_counts=0, d_q=0, nq=None, Sigma=None, Order=2,
+               MinNeighbors=3, Viewpoint=(0.0, 0.0, 0.0), stream=0):
+        """Device-resident MLS: raw device addresses (e.g. torch .data_ptr()); d_q 0 takes the tree's own points
+        (nq = Len()).  Enqueued on `stream`, returns without waiting."""
+        if nq is None:
+            if d_q:
+                raise ValueError("nq is required with d_q")
+            nq = self.Len()
+        vp = L.f32c(Viewpoint).reshape(3)
+
+        def opt(a):
+            return L.ptr(int(a)) if a else None
+        L.check(L.lib().pcgx_kdtree_mls_dev(
+            self._h, opt(d_q), int(nq), float(radius), float(radius if Sigma is None else Sigma), int(Order),
+            int(MinNeighbors), L.ptr(vp), opt(d_points), opt(d_normals), opt(d_kinds), opt(d_counts),
+            L.ptr(stream) if stream else None))
 
     # -- extension (no reference parity): FPFH descriptors, the input of feature-based coarse alignment
     def FPFH(self, radius, Normals):
