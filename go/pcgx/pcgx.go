@@ -1812,3 +1812,149 @@ func (m *SACPlaneModel) IsIn(c *SACPlane, p mat.Vec3, d float32) bool {
 	C.pcgx_sac_plane_is_in(m.h, c.cptr(), (*C.float)(unsafe.Pointer(&p[0])), C.float(d), &in)
 	return in != 0
 }
+
+// ------------------------------------------------- NDT registration (extension: no reference parity)
+
+// NDTMap is the base cloud as one Gaussian per occupied voxel of a BucketGrid (include/pcgx.h, "Normal Distributions
+// Transform").  No counterpart in the reference.  The map copies what it needs: the grid and the cloud may go afterwards.
+type NDTMap struct {
+	h *C.pcgx_ndt_map
+}
+
+// NDTCells lists the occupied voxels in ascending address; Cov and ICov are xx, xy, xz, yy, yz, zz, zero when invalid.
+type NDTCells struct {
+	Addr  []int64
+	Count []int32
+	Valid []int32
+	Mean  []mat.Vec3
+	Cov   [][6]float32
+	ICov  [][6]float32
+}
+
+// NewNDTMap builds the map over ra, the cloud g was built from.  A voxel with fewer than max(minPoints, 3) points, or
+// whose points coincide, is invalid; a valid voxel's eigenvalues are raised to minEigenRatio times the largest.
+func NewNDTMap(g *BucketGrid, ra pc.Vec3RandomAccessor, minPoints int, minEigenRatio float32) (*NDTMap, error) {
+	runtime.LockOSThread() // the error text is thread-local on the C side: call and pcgx_last_error on one OS thread
+	defer runtime.UnlockOSThread()
+	defer runtime.KeepAlive(g)
+	xyz := packVec3(ra)
+	var data unsafe.Pointer
+	if len(xyz) > 0 {
+		data = unsafe.Pointer(&xyz[0])
+	}
+	m := &NDTMap{}
+	rc := C.pcgx_ndt_map_create(g.h, data, C.int64_t(ra.Len()), 12, 0, 0, C.int32_t(minPoints), C.float(minEigenRatio), &m.h)
+	runtime.KeepAlive(xyz)
+	if err := status(rc); err != nil {
+		return nil, err
+	}
+	runtime.SetFinalizer(m, func(m *NDTMap) { m.Close() })
+	return m, nil
+}
+
+// Close releases the map.
+func (m *NDTMap) Close() {
+	runtime.LockOSThread()
+	defer runtime.UnlockOSThread()
+	defer runtime.KeepAlive(m)
+	if m.h != nil {
+		C.pcgx_ndt_map_free(m.h)
+		m.h = nil
+	}
+}
+
+// Counts returns the numbers of occupied and of valid voxels.
+func (m *NDTMap) Counts() (occupied, valid int, err error) {
+	runtime.LockOSThread()
+	defer runtime.UnlockOSThread()
+	defer runtime.KeepAlive(m)
+	var a, b C.int64_t
+	err = status(C.pcgx_ndt_map_counts(m.h, &a, &b))
+	return int(a), int(b), err
+}
+
+// Cells reads the map out.
+func (m *NDTMap) Cells() (*NDTCells, error) {
+	n, _, err := m.Counts()
+	if err != nil {
+		return nil, err
+	}
+	runtime.LockOSThread()
+	defer runtime.UnlockOSThread()
+	defer runtime.KeepAlive(m)
+	c := &NDTCells{Addr: make([]int64, n), Count: make([]int32, n), Valid: make([]int32, n), Mean: make([]mat.Vec3, n),
+		Cov: make([][6]float32, n), ICov: make([][6]float32, n)}
+	if n == 0 {
+		return c, nil
+	}
+	rc := C.pcgx_ndt_map_cells(m.h, (*C.int64_t)(unsafe.Pointer(&c.Addr[0])), (*C.int32_t)(unsafe.Pointer(&c.Count[0])),
+		(*C.int32_t)(unsafe.Pointer(&c.Valid[0])), (*C.float)(unsafe.Pointer(&c.Mean[0][0])),
+		(*C.float)(unsafe.Pointer(&c.Cov[0][0])), (*C.float)(unsafe.Pointer(&c.ICov[0][0])))
+	return c, status(rc)
+}
+
+// Evaluate returns the 30 float64 sums {sum e, sum g [6], upper triangle of sum H [21], sum omega, pair count} of the
+// target at pose trans (nil: the identity); neighbors is 1, 7 or 27.
+func (m *NDTMap) Evaluate(target pc.Vec3RandomAccessor, trans *mat.Mat4, neighbors int, outlierRatio float32) ([30]float64, error) {
+	runtime.LockOSThread()
+	defer runtime.UnlockOSThread()
+	defer runtime.KeepAlive(m)
+	var sums [30]float64
+	t := packVec3(target)
+	var tp, pose *C.float
+	if len(t) > 0 {
+		tp = (*C.float)(unsafe.Pointer(&t[0]))
+	}
+	if trans != nil {
+		pose = (*C.float)(unsafe.Pointer(&trans[0]))
+	}
+	rc := C.pcgx_ndt_evaluate(m.h, tp, C.int64_t(target.Len()), pose, C.int32_t(neighbors), C.float(outlierRatio),
+		(*C.double)(unsafe.Pointer(&sums[0])))
+	return sums, status(rc)
+}
+
+// NDT is the Fit on an NDTMap: evaluate, the plane Fit's evaluate tail, the Gauss-Newton update, repeated on the device
+// with one read-back.  Zero values select the defaults of the plane Fit (MinPairs 6, Threshold 0.01, MaxIteration 20);
+// Neighbors 0 selects 7 and OutlierRatio 0 selects 0.55.
+type NDT struct {
+	Neighbors    int
+	OutlierRatio float32
+	MinPairs     int
+	Threshold    mat.Vec6
+	MaxIteration int
+	Damping      float32
+}
+
+// Fit moves target onto the map, starting from init (nil: the identity).  When no point sees a valid voxel with a
+// weight above zero the gradient is 0 and init comes back as converged: Evaluate's sums[28] (sum omega) tells.
+func (n *NDT) Fit(m *NDTMap, target pc.Vec3RandomAccessor, init *mat.Mat4) (mat.Mat4, icp.Stat, error) {
+	runtime.LockOSThread() // the error text is thread-local on the C side: call and pcgx_last_error on one OS thread
+	defer runtime.UnlockOSThread()
+	defer runtime.KeepAlive(m)
+	var trans mat.Mat4
+	stat := icp.Stat{}
+	var p C.pcgx_icp_params
+	p.min_pairs, p.max_iteration = C.int32_t(n.MinPairs), C.int32_t(n.MaxIteration)
+	for i := 0; i < 6; i++ {
+		p.threshold[i] = C.float(n.Threshold[i])
+	}
+	nb, outlier := n.Neighbors, n.OutlierRatio
+	if nb == 0 {
+		nb = 7
+	}
+	if outlier == 0 {
+		outlier = 0.55
+	}
+	t := packVec3(target)
+	var tp, ip *C.float
+	if len(t) > 0 {
+		tp = (*C.float)(unsafe.Pointer(&t[0]))
+	}
+	if init != nil {
+		ip = (*C.float)(unsafe.Pointer(&init[0]))
+	}
+	var st C.pcgx_icp_stat
+	rc := C.pcgx_ndt_fit(m.h, tp, C.int64_t(target.Len()), 0, &p, C.float(n.Damping), C.int32_t(nb), C.float(outlier), ip,
+		(*C.float)(unsafe.Pointer(&trans[0])), &st, (*C.float)(unsafe.Pointer(&stat.Hessian[0])))
+	return trans, stat, gicpStat(&st, &stat, rc)
+}

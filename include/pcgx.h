@@ -1249,6 +1249,90 @@ PCGX_API pcgx_status pcgx_sor_filter_dev(const void *d_data, int64_t n, int32_t 
                                          int32_t mean_k, float std_mul, int32_t negative, void *d_out,
                                          int64_t *out_n, double *d_mean_dist, double stats[3], void *stream);
 
+/* ------------------------------------------- Normal Distributions Transform (extension: no reference parity)
+ * NOT in the reference: pcgol has nothing like it.  NDT registration (Biber and Strasser 2003; Magnusson 2009; PCL's
+ * NormalDistributionsTransform) as a fourth Fit beside point-to-point, point-to-plane and Generalized ICP.  It needs
+ * no nearest-neighbour search: the BASE cloud (fixed) becomes a map of one Gaussian per voxel of a bucket voxel grid,
+ * and the TARGET (the cloud that moves) is scored against the Gaussians of the voxels its points fall into.  Its basin
+ * of convergence is about the voxel size, not the point spacing.  Tests check against a NumPy float64 restatement
+ * (tests/ndt_oracle.py).
+ *
+ * The map.  data / n / stride / xyz_off are the cloud the grid was built from (as pcgx_sac_plane_model_create takes
+ * them; on_device = 1: device records); creation copies what it needs into library-owned device memory, the grid and
+ * the caller's buffers may go afterwards.  Per occupied voxel with integer coordinates v, whose points are the ids
+ * whose pcgx_bucket_grid_addr names it (count of them), everything float64 from the float32 inputs widened:
+ *   centre      o_k = origin_k + v_k * resolution      (the address arithmetic rounds, so voxel v is centred there)
+ *   offsets     d = p - o;  mean_d = sum d / count
+ *   covariance  C = (sum d d^T - count * mean_d mean_d^T) / (count - 1)
+ *   mean        o + mean_d, rounded to float32 once
+ * A voxel is INVALID when count < max(min_points, 3) (min_points below 3 counts as 3), when all its points coincide (the
+ * exact min / max box test of pcgx_kdtree_normals), or when the float64 trace of C is <= 0.  Invalid voxels are listed
+ * with valid = 0 and zero cov6 / icov6, and take no part in an evaluation.  A valid voxel is regularised: with
+ * eigenvalues l0 <= l1 <= l2 and eigenvectors V of C (the Jacobi solve of normals and covariances),
+ *   l'_k = max(l_k, min_eigen_ratio * l2),  cov6 = V diag(l') V^T,  icov6 = V diag(1 / l') V^T,
+ * each rounded to float32 once: cond <= 1 / min_eigen_ratio, collinear and coplanar voxels stay usable.  The sums of a
+ * voxel are taken in a fixed order (one wave over its ids in bucket order, no float atomics): the same call gives the
+ * same bits.  PCGX_E_INVALID: a NULL grid or out, n different from the grid's, min_eigen_ratio outside (0, 1].  An
+ * empty grid gives a map with no voxels, which is no error.
+ * pcgx_ndt_map_cells lists the occupied voxels in ascending voxel address (n_occupied entries each; every array may be
+ * NULL); cov6 / icov6 in the order xx, xy, xz, yy, yz, zz of pcgx_kdtree_covariances. */
+typedef struct pcgx_ndt_map pcgx_ndt_map;
+PCGX_API pcgx_status pcgx_ndt_map_create(const pcgx_bucket_grid *g, const void *data, int64_t n, int32_t stride,
+                                         int32_t xyz_off, int32_t on_device, int32_t min_points, float min_eigen_ratio,
+                                         pcgx_ndt_map **out);
+PCGX_API pcgx_status pcgx_ndt_map_free(pcgx_ndt_map *m);
+PCGX_API pcgx_status pcgx_ndt_map_counts(const pcgx_ndt_map *m, int64_t *n_occupied, int64_t *n_valid);
+PCGX_API pcgx_status pcgx_ndt_map_cells(const pcgx_ndt_map *m, int64_t *addr, int32_t *count, int32_t *valid,
+                                        float *mean3, float *cov6, float *icov6);
+
+/* One evaluation at pose T (trans16, column-major; NULL: the identity).
+ * Pairs: p_i = Mat4.Transform(T, target_i) in float32 (the bits pcgx_mat4_transform gives; always applied, for the
+ * identity too).  The grid's address arithmetic names p_i's voxel v; a point it refuses (outside the grid, NaN, Inf)
+ * contributes nothing.  The candidate voxels are v itself (neighbors = 1), v and its six face neighbours (7), or the
+ * 3 x 3 x 3 block round v (27); a candidate is used if it lies inside the grid on every axis -- a neighbour beyond
+ * size[k] is NOT the voxel whose address happens to follow -- and is a valid voxel of the map.  Every (point, valid
+ * voxel) is a pair.
+ * Constants (Magnusson 2009, as PCL's ndt.hpp; res the grid's float32 resolution), formed in extended precision on the
+ * host and rounded to float64 once:
+ *   c1 = 10 (1 - outlier_ratio);  c2 = outlier_ratio / res^3;  d3 = -log c2;  d1 = -log(c1 + c2) - d3;
+ *   k2 = -2 log((-log(c1 e^-1/2 + c2) - d3) / d1)
+ * Per pair, all float64; mu and M the voxel's float32 mean and icov6 widened; the pose increment is
+ * p' = p + t + w x p with parameters {t0, t1, t2, w0, w1, w2} as everywhere here:
+ *   q = p - mu;  m = q^T M q;  omega = exp(-k2 m / 2);  J_k = e_k,  J_{3+k} = e_k x p
+ *   e = (2 / k2) (1 - omega);  g_k = omega J_k^T M q;  H_kl = omega J_k^T M J_l  (k <= l)
+ * The 30 sums have the plane session's layout {sum e, sum g [6], upper triangle of sum H row-major [21], sum omega,
+ * pair count}: unlike Generalized ICP the weight slot holds sum omega, NOT the count, so pcgx_icp_plane_finish_evaluate
+ * yields the omega-weighted mean gradient 2 sum g / sum omega, which does not fade with the weights when the clouds
+ * are far apart.  This is iteratively reweighted Gauss-Newton on Magnusson's score; the negative-curvature term
+ * -k2 g g^T of the full Newton Hessian is left out on purpose, so sum H stays positive semi-definite and the Cholesky
+ * rule of the plane Fit applies.  There is no cut-off on distant pairs: omega underflows by itself.  The sums are
+ * reduced in a fixed order (lanes, waves, workgroup rows, one final reduce): two calls give the same bits.  nt == 0
+ * gives thirty zeros.  PCGX_E_INVALID: outlier_ratio outside (0, 1), k2 not finite or not > 0, neighbors outside
+ * {1, 7, 27}, a NULL map, nt < 0, a NULL target with nt > 0, NULL sums. */
+PCGX_API pcgx_status pcgx_ndt_evaluate(const pcgx_ndt_map *m, const float *target, int64_t nt,
+                                       const float trans16[16] /* NULL: identity */, int32_t neighbors,
+                                       float outlier_ratio, double sums30[30]);
+/* Same, d_target and d_sums30 device resident, enqueued on `stream` (NULL: the library's); returns without waiting. */
+PCGX_API pcgx_status pcgx_ndt_evaluate_dev(const pcgx_ndt_map *m, const float *d_target, int64_t nt,
+                                           const float trans16[16], int32_t neighbors, float outlier_ratio,
+                                           double *d_sums30, void *stream);
+
+/* The Fit.  From init16 (NULL: the identity) the loop repeats: evaluate; the plane session's tail (the min_pairs test
+ * on the pair count, 0 -> 6, then pcgx_icp_plane_finish_evaluate's arithmetic); pcgx_icp_gauss_newton_update's
+ * arithmetic (flat test, damping, Translate * (Rodrigues * trans), iteration cap).  Of params only min_pairs, threshold
+ * and max_iteration are read.  The whole loop runs on the device behind a `done` flag with one read-back at the end,
+ * and equals a host loop of pcgx_ndt_evaluate -> pcgx_icp_plane_finish_evaluate -> pcgx_icp_gauss_newton_update bit for
+ * bit.  PCGX_E_NOT_ENOUGH_PAIRS and PCGX_E_SINGULAR as for plane Fits (trans16 is then the pose the failing iteration
+ * started from); stat is filled as there, with dist_rms = 0; hessian36 may be NULL; target: host floats, or device
+ * floats with on_device = 1.
+ * PCGX_E_INVALID: what pcgx_ndt_evaluate refuses, NULL params or trans16, a negative min_pairs or max_iteration.
+ * When no point sees a valid voxel with omega > 0 (and min_pairs lets the evaluation pass), the gradient is 0, the flat
+ * test holds and the input pose comes back as converged: the caller reads sum omega from an evaluation to tell. */
+PCGX_API pcgx_status pcgx_ndt_fit(const pcgx_ndt_map *m, const float *target, int64_t nt, int32_t on_device,
+                                  const pcgx_icp_params *params, float damping, int32_t neighbors, float outlier_ratio,
+                                  const float init16[16] /* NULL: identity */, float trans16[16], pcgx_icp_stat *stat,
+                                  float hessian36[36] /* may be NULL */);
+
 #ifdef __cplusplus
 }
 #endif

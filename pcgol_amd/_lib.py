@@ -289,6 +289,14 @@ SIGNATURES = {
                                      C.POINTER(IcpStat), _vp]),
     "pcgx_sor_filter": (_i32, [_vp, _i64, _i32, _i32, _i32, _f32, _i32, _vp, C.POINTER(_i64), _vp, _vp]),
     "pcgx_sor_filter_dev": (_i32, [_vp, _i64, _i32, _i32, _i32, _f32, _i32, _vp, C.POINTER(_i64), _vp, _vp, _vp]),
+    "pcgx_ndt_map_create": (_i32, [_vp, _vp, _i64, _i32, _i32, _i32, _i32, _f32, C.POINTER(_vp)]),
+    "pcgx_ndt_map_free": (_i32, [_vp]),
+    "pcgx_ndt_map_counts": (_i32, [_vp, C.POINTER(_i64), C.POINTER(_i64)]),
+    "pcgx_ndt_map_cells": (_i32, [_vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "pcgx_ndt_evaluate": (_i32, [_vp, _vp, _i64, _vp, _i32, _f32, _vp]),
+    "pcgx_ndt_evaluate_dev": (_i32, [_vp, _vp, _i64, _vp, _i32, _f32, _vp, _vp]),
+    "pcgx_ndt_fit": (_i32, [_vp, _vp, _i64, _i32, C.POINTER(IcpParams), _f32, _i32, _f32, _vp, _vp, C.POINTER(IcpStat),
+                            _vp]),
 }
 
 _lib = None

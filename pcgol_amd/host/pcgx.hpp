@@ -738,6 +738,74 @@ class GeneralizedICP {
   }
 };
 
+// Extension (no counterpart in the reference; include/pcgx.h "Normal Distributions Transform"): the base cloud as one
+// Gaussian per voxel of a BucketVoxelGrid.  The map copies what it needs: the grid and the cloud may go afterwards.
+class NDTMap {
+ public:
+  struct CellList {  // the occupied voxels, ascending address; cov / icov: xx, xy, xz, yy, yz, zz, zero when invalid
+    std::vector<int64_t> addr;
+    std::vector<int32_t> count, valid;
+    std::vector<Vec3> mean;
+    std::vector<std::array<float, 6>> cov, icov;
+  };
+  NDTMap(const BucketVoxelGrid &vg, const CloudView &c, int32_t minPoints = 6, float minEigenRatio = 0.01f) {
+    check(pcgx_ndt_map_create(vg.handle(), c.data, c.points, c.stride, c.xyz_offset, 0, minPoints, minEigenRatio, &h_));
+  }
+  ~NDTMap() { pcgx_ndt_map_free(h_); }
+  NDTMap(const NDTMap &) = delete;
+  NDTMap &operator=(const NDTMap &) = delete;
+  int64_t Occupied() const { int64_t n; check(pcgx_ndt_map_counts(h_, &n, nullptr)); return n; }
+  int64_t Valid() const { int64_t n; check(pcgx_ndt_map_counts(h_, nullptr, &n)); return n; }
+  CellList Cells() const {
+    CellList c;
+    const size_t m = (size_t)Occupied();
+    c.addr.resize(m); c.count.resize(m); c.valid.resize(m); c.mean.resize(m); c.cov.resize(m); c.icov.resize(m);
+    if (m > 0)
+      check(pcgx_ndt_map_cells(h_, c.addr.data(), c.count.data(), c.valid.data(), c.mean[0].data(), c.cov[0].data(),
+                               c.icov[0].data()));
+    return c;
+  }
+  // The 30 float64 sums {sum e, sum g [6], sum H upper triangle [21], sum omega, pairs} at pose trans (nullptr: identity)
+  std::array<double, 30> Evaluate(const std::vector<Vec3> &target, const Mat4 *trans = nullptr, int32_t neighbors = 7,
+                                  float outlierRatio = 0.55f) const {
+    std::array<double, 30> s{};
+    check(pcgx_ndt_evaluate(h_, target.empty() ? nullptr : target[0].data(), (int64_t)target.size(),
+                            trans ? trans->data() : nullptr, neighbors, outlierRatio, s.data()));
+    return s;
+  }
+  const pcgx_ndt_map *handle() const { return h_; }
+
+ private:
+  pcgx_ndt_map *h_ = nullptr;
+};
+
+// The NDT Fit: evaluate, the plane Fit's tail, the Gauss-Newton update, on the device with one read-back.
+class NDT {
+ public:
+  int32_t Neighbors = 7;  // 1, 7 or 27 candidate voxels per point
+  float OutlierRatio = 0.55f;
+  int MinPairs = 0;
+  std::array<float, 6> Threshold{};
+  int MaxIteration = 0;
+  float Damping = 0.0f;
+  bool HasGradient() const { return true; }
+  bool HasHessian() const { return true; }
+  std::pair<Mat4, PlaneStat> Fit(const NDTMap &map, const std::vector<Vec3> &target, const Mat4 *init = nullptr) const {
+    pcgx_icp_params p{};
+    p.min_pairs = MinPairs;
+    std::memcpy(p.threshold, Threshold.data(), sizeof p.threshold);
+    p.max_iteration = MaxIteration;
+    Mat4 t;
+    PlaneStat ps{};
+    pcgx_icp_stat st{};
+    check(pcgx_ndt_fit(map.handle(), target.empty() ? nullptr : target[0].data(), (int64_t)target.size(), 0, &p, Damping,
+                       Neighbors, OutlierRatio, init ? init->data() : nullptr, t.data(), &st, ps.Hessian.data()));
+    ps.Evaluated = st.evaluated;
+    ps.NumIteration = st.num_iteration;
+    return {t, ps};
+  }
+};
+
 // ---- the reference's package surface, name for name ------------------------------------------------------------
 // What go/pc/storage/kdtree, go/pc/filter/voxelgrid and go/pc/registration/icp are to a Go caller (see go/README.md):
 // the exported names of the three reference packages over the classes above, so that code written against
