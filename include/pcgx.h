@@ -303,7 +303,9 @@ PCGX_API pcgx_status pcgx_minmax(const void *data, int64_t n, int32_t stride, in
 
 /* Filter: out_data must hold n*stride bytes (worst case); *out_n = number of
  * output records (Width of the returned cloud, Height = 1).  chunk = {0,0,0}
- * (any product == 0) selects the non-chunked path (voxelgrid.go:45-47). */
+ * (any product == 0) selects the non-chunked path (voxelgrid.go:45-47).
+ * A non-finite coordinate (NaN, +-inf) or a point whose cell lies outside the
+ * dense grid ends the call with PCGX_E_OUT_OF_RANGE, as the Go code panics. */
 PCGX_API pcgx_status pcgx_voxel_filter(const void *data, int64_t n, int32_t stride,
                                        int32_t xyz_off, const float leaf[3],
                                        const int32_t chunk[3], void *out_data, int64_t *out_n);
