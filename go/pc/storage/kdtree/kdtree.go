@@ -20,7 +20,8 @@ import (
 // Extensions with no reference counterpart come with the type: KNearest(p, k, maxRange) []storage.Neighbor (the k
 // nearest points, ties by ID; include/pcgx.h, pcgx_kdtree_knearest), KNearestBatch, Normals, FPFH, FPFHAt (FPFH's rows
 // at chosen ids only), and the keypoint detectors LocalMaxima(radius, score) and ISSKeypoints(salientRadius,
-// nonMaxRadius, gamma21, gamma32, minNeighbors) (include/pcgx.h, "keypoints").
+// nonMaxRadius, gamma21, gamma32, minNeighbors) (include/pcgx.h, "keypoints"), and cluster extraction,
+// Clusters(radius, pcgx.ClusterParams{...}) (include/pcgx.h, "clusters").
 type KDTree = pcgx.KDTree
 
 // KDTreeOption is kdtree.KDTreeOption (kdtree.go:31).

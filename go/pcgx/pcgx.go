@@ -510,6 +510,76 @@ func (k *KDTree) ISSKeypoints(salientRadius, nonMaxRadius, gamma21, gamma32 floa
 	return ids[:int(m)], eigenvalues, saliency, nil
 }
 
+// ClusterParams are the optional parts of (*KDTree).Clusters.  Normals (nil: none): an edge also needs
+// |n_i . n_j| >= MinCos (n_i . n_j when Oriented), and a point whose normal is not finite or zero belongs to no
+// cluster.  Curvature (nil: none): a point above MaxCurvature, or NaN, belongs to no cluster.  A cluster has
+// max(MinSize, 1) <= size, and size <= MaxSize unless MaxSize is 0.
+type ClusterParams struct {
+	Normals      []mat.Vec3
+	MinCos       float32
+	Oriented     bool
+	Curvature    []float32
+	MaxCurvature float32
+	MinSize      int64
+	MaxSize      int64
+}
+
+// Clusters returns the connected components of the radius graph over the tree's points (extension: no reference
+// parity; include/pcgx.h, pcgx_kdtree_clusters), largest first, equal sizes by smallest id: labels per point in id
+// order (the cluster's number, or -1), sizes per cluster, and ids: the members of cluster 0 ascending, then those of
+// cluster 1, and so on (cluster c starts at the sum of the sizes before it).
+func (k *KDTree) Clusters(radius float32, p ClusterParams) (labels, sizes, ids []int64, err error) {
+	runtime.LockOSThread() // the error text is thread-local on the C side: call and pcgx_last_error on one OS thread
+	defer runtime.UnlockOSThread()
+	defer runtime.KeepAlive(k) // the finalizer must not free the handle while a call is in flight
+	var ln C.int64_t
+	if err := status(C.pcgx_kdtree_len(k.t.h, &ln)); err != nil {
+		return nil, nil, nil, err
+	}
+	n := int(ln)
+	if p.Normals != nil && len(p.Normals) != n {
+		return nil, nil, nil, errors.New("pcgx: one normal per point of the tree is required")
+	}
+	if p.Curvature != nil && len(p.Curvature) != n {
+		return nil, nil, nil, errors.New("pcgx: one curvature per point of the tree is required")
+	}
+	labels = make([]int64, n)
+	sizes = make([]int64, n)
+	ids = make([]int64, n)
+	if n == 0 {
+		return labels, sizes, ids, nil
+	}
+	var nrm, cur *C.float
+	if p.Normals != nil {
+		nrm = (*C.float)(unsafe.Pointer(&p.Normals[0]))
+	}
+	if p.Curvature != nil {
+		cur = (*C.float)(unsafe.Pointer(&p.Curvature[0]))
+	}
+	oriented := C.int32_t(0)
+	if p.Oriented {
+		oriented = 1
+	}
+	var c C.int64_t
+	rc := C.pcgx_kdtree_clusters(k.t.h, C.float(radius), nrm, C.float(p.MinCos), oriented, cur, C.float(p.MaxCurvature),
+		C.int64_t(p.MinSize), C.int64_t(p.MaxSize), (*C.int64_t)(unsafe.Pointer(&labels[0])), &c,
+		(*C.int64_t)(unsafe.Pointer(&sizes[0])), (*C.int64_t)(unsafe.Pointer(&ids[0])))
+	runtime.KeepAlive(p.Normals)
+	runtime.KeepAlive(p.Curvature)
+	runtime.KeepAlive(labels)
+	runtime.KeepAlive(sizes)
+	runtime.KeepAlive(ids)
+	if err := status(rc); err != nil {
+		return nil, nil, nil, err
+	}
+	sizes = sizes[:int(c)]
+	total := int64(0)
+	for _, s := range sizes {
+		total += s
+	}
+	return labels, sizes, ids[:int(total)], nil
+}
+
 // FPFHMatch finds, for every row of a, the nearest usable row of b and the runner-up's distance (extension: no
 // reference parity; include/pcgx.h, "FPFH matching"): float32 squared distances over the 33 values, summed left to
 // right, ties to the smaller id.  ids[i] is -1 and both distances are +Inf where a's row is unusable (not finite, or

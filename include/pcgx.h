@@ -976,6 +976,62 @@ PCGX_API pcgx_status pcgx_kdtree_iss_keypoints_dev(const pcgx_kdtree *t, float s
                                                    float *d_eigenvalues, float *d_saliency, int32_t *d_ids /* [Len()] */,
                                                    int32_t *d_n_ids, void *stream);
 
+/* ------------------------------------------- clusters (extension: no reference parity)
+ * NOT in the reference.  The connected components of the radius graph over the tree's own points -- PCL's
+ * EuclideanClusterExtraction -- optionally cut where the normals turn or the curvature is high (smooth faces), kept
+ * inside a size range, ranked, and returned as labels, sizes and grouped member ids.  Every array is in id order over
+ * the tree's own points, deleted ids included (the q == NULL convention of pcgx_kdtree_normals, _fpfh and
+ * _local_maxima).  This comment is the contract, tests/cluster_oracle.py restates it.
+ * Neighbourhood: N(i) = the points p of the tree with DistSq(p, point i) < radius^2, DistSq the reference's float32
+ *   expression: exactly the set pcgx_kdtree_range_count counts on that handle (grid, forced walk, after DeletePoint).
+ *   Deleted points are nobody's neighbour.
+ * Usable point: i is usable when all three hold:
+ *   i is in N(i) (this excludes a deleted id and a point with a NaN or infinite coordinate);
+ *   if normals != NULL, its three normal components are finite and not all zero (the zero normal is what
+ *     pcgx_kdtree_normals answers for a degenerate neighbourhood);
+ *   if curvature != NULL, curvature[i] <= max_curvature (a NaN curvature fails: again the degenerate answer).
+ *   An unusable point gets label -1, belongs to no cluster and carries no edge.
+ * Edge: {i, j} with i != j is an edge when both points are usable, j is in N(i) (the expression is symmetric bit for
+ *   bit), and, if normals != NULL, the normals agree: with the float32 components widened to float64,
+ *   c = (nx_i nx_j + ny_i ny_j) + nz_i nz_j (the products are exact, the two additions rounded in this order, nothing
+ *   contracted); the edge holds iff c >= (double)min_cos when oriented != 0, else iff fabs(c) >= (double)min_cos.
+ *   Normals are taken as given, not normalised.  With normals == NULL, min_cos and oriented are ignored; with
+ *   curvature == NULL, max_curvature is ignored.
+ * Clusters: a cluster is a connected component of the usable points under these edges whose size s satisfies
+ *   max(min_size, 1) <= s, and also s <= max_size when max_size > 0 (max_size == 0: no upper limit).  A usable point
+ *   without an edge is a component of size 1.  The clusters are numbered 0 .. C-1 by decreasing size, equal sizes by the
+ *   smallest member id, ascending.
+ * Outputs: labels[i] = the cluster's number, or -1 for an unusable point or a point of a component outside the size
+ *   range.  *n_clusters = C.  sizes[0 .. C) holds the sizes and is 0 in every remaining slot.  ids holds the members of
+ *   cluster 0 in ascending id, then those of cluster 1, and so on, then -1 in every remaining slot (the padding of
+ *   pcgx_kdtree_local_maxima); cluster c starts at the sum of the sizes before it.
+ * PCGX_E_INVALID: a radius that is not finite and > 0; a NaN min_cos with normals given; a NaN max_curvature with
+ *   curvature given; min_size < 0 or max_size < 0; 0 < max_size < max(min_size, 1); a NULL tree; NULL labels or
+ *   n_clusters with Len() > 0.  Len() == 0 is PCGX_OK and writes only *n_clusters = 0.  A component is a property of a
+ *   set: the same input gives the same bits on every call.
+ * Always computed on the device.  Cost: the sum over the usable points of the records in the cells (or tree nodes) that
+ *   their radius covers, as for Range, twice on a handle with a grid (a hook pass and a union pass), plus two radix sorts
+ *   of Len() keys of ceil(log2(Len() + 1)) bits (one when ids is NULL).  What the edge test reads of a neighbour lies
+ *   beside the grid's cell-ordered points (1 byte a record, 16 more with normals), not behind its id.  There is no
+ *   wave-shared path for a grid row of thousands of coincident points (region growing has none either): such a row is one
+ *   lane's loop for each of its points.
+ *   Temporaries: 9 arrays of 4 Len() bytes, Len() bytes of flags, 16 Len() bytes with normals, and the radix sort's
+ *   workspace; the host form stages its inputs and 4 (3 Len() + 1) bytes of outputs beside them. */
+PCGX_API pcgx_status pcgx_kdtree_clusters(const pcgx_kdtree *t, float radius,
+                                          const float *normals /* [3 Len()], may be NULL */, float min_cos,
+                                          int32_t oriented, const float *curvature /* [Len()], may be NULL */,
+                                          float max_curvature, int64_t min_size, int64_t max_size,
+                                          int64_t *labels /* [Len()] */, int64_t *n_clusters,
+                                          int64_t *sizes /* [Len()], may be NULL */,
+                                          int64_t *ids /* [Len()], may be NULL */);
+/* Same, every array device resident (labels, sizes, ids and the count are int32 there), enqueued on `stream` (NULL: the
+ * library's); returns without waiting, reads nothing back. */
+PCGX_API pcgx_status pcgx_kdtree_clusters_dev(const pcgx_kdtree *t, float radius, const float *d_normals, float min_cos,
+                                              int32_t oriented, const float *d_curvature, float max_curvature,
+                                              int64_t min_size, int64_t max_size, int32_t *d_labels /* [Len()] */,
+                                              int32_t *d_n_clusters, int32_t *d_sizes /* [Len()], may be NULL */,
+                                              int32_t *d_ids /* [Len()], may be NULL */, void *stream);
+
 /* ------------------------------------------- pose from correspondences (extension: no reference parity)
  * NOT in the reference.  The rigid motion (a proper rotation and a translation, no scale) that most pairs of a
  * correspondence list agree on, by sample consensus: the starting pose every Fit here needs, from what

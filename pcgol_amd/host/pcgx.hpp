@@ -268,6 +268,42 @@ class KDTree {  // pc/storage/kdtree/kdtree.go:14-23
     r.ids.resize((size_t)m);
     return r;
   }
+  // Cluster extraction (extension: no reference parity; include/pcgx.h, pcgx_kdtree_clusters): the connected
+  // components of the radius graph over the tree's own points, kept when max(minSize, 1) <= size (<= maxSize unless 0),
+  // largest first, equal sizes by smallest id.  normals (empty: none): an edge also needs |n_i . n_j| >= minCos
+  // (n_i . n_j when oriented); curvature (empty: none): a point above maxCurvature, or NaN, belongs to no cluster.
+  // labels: per point its cluster's number or -1; sizes: per cluster; ids: cluster 0's members ascending, then cluster
+  // 1's, ...; Members(c) cuts cluster c out of ids.
+  struct ClustersResult {
+    std::vector<int64_t> labels, sizes, ids;
+    std::vector<int64_t> Members(size_t c) const {
+      size_t at = 0;
+      for (size_t k = 0; k < c; k++) at += (size_t)sizes[k];
+      return std::vector<int64_t>(ids.begin() + (std::ptrdiff_t)at, ids.begin() + (std::ptrdiff_t)(at + (size_t)sizes[c]));
+    }
+  };
+  ClustersResult Clusters(float radius, const std::vector<Vec3> &normals = {}, float minCos = 0.0f, bool oriented = false,
+                          const std::vector<float> &curvature = {}, float maxCurvature = 0.0f, int64_t minSize = 1,
+                          int64_t maxSize = 0) const {
+    const int64_t n = Len();
+    if (!normals.empty() && (int64_t)normals.size() != n)
+      throw Error(PCGX_E_INVALID, "one normal per point of the tree is required");
+    if (!curvature.empty() && (int64_t)curvature.size() != n)
+      throw Error(PCGX_E_INVALID, "one curvature per point of the tree is required");
+    ClustersResult r;
+    r.labels.resize((size_t)n);
+    r.sizes.resize((size_t)n);
+    r.ids.resize((size_t)n);
+    int64_t c = 0;
+    check(pcgx_kdtree_clusters(h_.get(), radius, normals.empty() ? nullptr : normals[0].data(), minCos, oriented ? 1 : 0,
+                               curvature.empty() ? nullptr : curvature.data(), maxCurvature, minSize, maxSize,
+                               r.labels.data(), &c, r.sizes.data(), r.ids.data()));
+    r.sizes.resize((size_t)c);
+    size_t total = 0;
+    for (int64_t s : r.sizes) total += (size_t)s;
+    r.ids.resize(total);
+    return r;
+  }
   // The k points with the smallest (DistSq, ID) among those with DistSq < maxRange^2, ascending (extension: no
   // reference parity; include/pcgx.h, pcgx_kdtree_knearest: ties go by ID).
   std::vector<Neighbor> KNearest(const Vec3 &p, int32_t k, float maxRange) const {

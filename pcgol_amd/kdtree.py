@@ -1,8 +1,8 @@
 """pc/storage/kdtree mirror: KDTree on the GPU behind the storage.Search shape
 (pc/storage/search.go:13-17): Vec3At / Len / Nearest, plus batched NearestBatch, and extensions with no
 reference counterpart: surface normals (Normals), moving-least-squares smoothing (MLS), FPFH descriptors
-(FPFH, FPFHAt), keypoints (LocalMaxima, ISSKeypoints), k nearest neighbours (KNearest) and their covariances
-(Covariances)."""
+(FPFH, FPFHAt), keypoints (LocalMaxima, ISSKeypoints), cluster extraction (Clusters), k nearest neighbours
+(KNearest) and their covariances (Covariances)."""
 import ctypes as C
 
 import numpy as np
@@ -318,6 +318,49 @@ class KDTree:
             self._h, float(SalientRadius), float(NonMaxRadius), float(Gamma21), float(Gamma32), int(MinNeighbors),
             L.ptr(int(d_eigenvalues)) if d_eigenvalues else None, L.ptr(int(d_saliency)) if d_saliency else None,
             L.ptr(int(d_ids)), L.ptr(int(d_n_ids)), L.ptr(stream) if stream else None))
+
+    # -- extension (no reference parity): clusters, the connected components of the radius graph
+    def Clusters(self, radius, Normals=None, MinCos=0.0, Oriented=False, Curvature=None, MaxCurvature=0.0, MinSize=1,
+                 MaxSize=0):
+        """The connected components of the radius graph (DistSq < radius^2, Range's set) over the tree's own points,
+        kept when MinSize <= size (<= MaxSize unless 0), largest first, equal sizes by smallest id -> (labels int64
+        (n,), sizes int64 (C,), ids int64 (sum(sizes),)).  Normals (n,3): an edge also needs (|n_i . n_j| or, Oriented,
+        n_i . n_j) >= MinCos, and a non-finite or zero normal makes its point unusable; Curvature (n,): a point above
+        MaxCurvature (or NaN) is unusable.  labels: the cluster's number, -1 for an unusable point or one of a
+        component outside the size range; ids: cluster 0's members ascending, then cluster 1's, ... (include/pcgx.h,
+        pcgx_kdtree_clusters)."""
+        n = self.Len()
+        nrm = cur = None
+        if Normals is not None:
+            nrm = L.f32c(Normals).reshape(-1, 3)
+            if len(nrm) != n:
+                raise ValueError("one normal per point of the tree is required")
+        if Curvature is not None:
+            cur = L.f32c(Curvature).reshape(-1)
+            if len(cur) != n:
+                raise ValueError("one curvature per point of the tree is required")
+        labels = np.empty(n, np.int64)
+        sizes = np.empty(n, np.int64)
+        ids = np.empty(n, np.int64)
+        cnt = C.c_int64()
+        L.check(L.lib().pcgx_kdtree_clusters(
+            self._h, float(radius), L.ptr(nrm) if nrm is not None else None, float(MinCos), int(bool(Oriented)),
+            L.ptr(cur) if cur is not None else None, float(MaxCurvature), int(MinSize), int(MaxSize),
+            L.ptr(labels) if n else None, C.byref(cnt), L.ptr(sizes) if n else None, L.ptr(ids) if n else None))
+        sizes = sizes[:cnt.value]
+        return labels, sizes, ids[:int(sizes.sum())]
+
+    def ClustersDev(self, radius, d_labels, d_n_clusters, d_sizes=0, d_ids=0, d_normals=0, MinCos=0.0, Oriented=False,
+                    d_curvature=0, MaxCurvature=0.0, MinSize=1, MaxSize=0, stream=0):
+        """Device-resident Clusters: raw device addresses (e.g. torch .data_ptr()); d_labels int32 [Len()],
+        d_n_clusters one int32, d_sizes int32 [Len()] (the sizes, then 0), d_ids int32 [Len()] (the members cluster by
+        cluster, then -1), d_normals float32 [3 Len()] and d_curvature float32 [Len()] (what NormalsDev writes for the
+        tree's own points).  Enqueued on `stream`, returns without waiting; nothing is read back."""
+        opt = lambda a: L.ptr(int(a)) if a else None  # noqa: E731
+        L.check(L.lib().pcgx_kdtree_clusters_dev(
+            self._h, float(radius), opt(d_normals), float(MinCos), int(bool(Oriented)), opt(d_curvature),
+            float(MaxCurvature), int(MinSize), int(MaxSize), opt(d_labels), opt(d_n_clusters), opt(d_sizes), opt(d_ids),
+            L.ptr(stream) if stream else None))
 
     # -- extension (no reference parity): k nearest neighbours
     def KNearest(self, p, k, maxRange):

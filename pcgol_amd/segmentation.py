@@ -161,3 +161,52 @@ class RegionGrowing:
         L.check(L.lib().pcgx_region_growing_segment(self.search._h, L.ptr(self.labels), L.ptr(comp), L.ptr(p),
                                                     float(np.float32(maxRange)), L.ptr(out), len(out), C.byref(cnt)))
         return out[: cnt.value].copy()
+
+
+class ClusterExtraction:
+    """Cluster extraction in PCL's vocabulary (EuclideanClusterExtraction; with normals, its smooth variant), over
+    KDTree.Clusters (extension: no reference parity; include/pcgx.h, "clusters").  search: a pcgol_amd KDTree.
+
+        ce = ClusterExtraction(tree, ClusterTolerance=0.05, MinClusterSize=100)
+        for ids in ce.Extract(): ...
+
+    The clusters come largest first, equal sizes by smallest id, each as ascending int64 ids."""
+
+    def __init__(self, search, ClusterTolerance=0.0, MinClusterSize=1, MaxClusterSize=0):
+        self.search = search
+        self.tolerance = float(ClusterTolerance)
+        self.min_size, self.max_size = int(MinClusterSize), int(MaxClusterSize)
+        self.normals = self.curvature = None
+        self.min_cos, self.oriented, self.max_curvature = 0.0, False, 0.0
+        self.labels = self.sizes = None
+
+    New = classmethod(lambda cls, search, *a, **k: cls(search, *a, **k))
+
+    def SetClusterTolerance(self, tolerance):
+        self.tolerance = float(tolerance)
+
+    def SetMinClusterSize(self, n):
+        self.min_size = int(n)
+
+    def SetMaxClusterSize(self, n):
+        """0: no upper limit"""
+        self.max_size = int(n)
+
+    def SetInputNormals(self, Normals, MinCos=0.0, Oriented=False):
+        """an edge also needs |n_i . n_j| >= MinCos (n_i . n_j when Oriented); None: Euclidean clustering again"""
+        self.normals, self.min_cos, self.oriented = Normals, float(MinCos), bool(Oriented)
+
+    def SetSmoothnessThreshold(self, angle):
+        """PCL's form of MinCos: the largest angle (radians) between the normals of two joined points"""
+        self.min_cos = float(np.cos(angle))
+
+    def SetInputCurvature(self, Curvature, MaxCurvature=0.0):
+        """a point whose curvature is above MaxCurvature (or NaN) belongs to no cluster; None: no such test"""
+        self.curvature, self.max_curvature = Curvature, float(MaxCurvature)
+
+    def Extract(self):
+        """-> [ids of cluster 0, ids of cluster 1, ...]; .labels and .sizes hold the call's other two results"""
+        self.labels, self.sizes, ids = self.search.Clusters(
+            self.tolerance, Normals=self.normals, MinCos=self.min_cos, Oriented=self.oriented, Curvature=self.curvature,
+            MaxCurvature=self.max_curvature, MinSize=self.min_size, MaxSize=self.max_size)
+        return np.split(ids, np.cumsum(self.sizes)[:-1]) if len(self.sizes) else []
