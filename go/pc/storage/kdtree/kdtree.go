@@ -21,7 +21,8 @@ import (
 // nearest points, ties by ID; include/pcgx.h, pcgx_kdtree_knearest), KNearestBatch, Normals, FPFH, FPFHAt (FPFH's rows
 // at chosen ids only), and the keypoint detectors LocalMaxima(radius, score) and ISSKeypoints(salientRadius,
 // nonMaxRadius, gamma21, gamma32, minNeighbors) (include/pcgx.h, "keypoints"), and cluster extraction,
-// Clusters(radius, pcgx.ClusterParams{...}) (include/pcgx.h, "clusters").
+// Clusters(radius, pcgx.ClusterParams{...}) (include/pcgx.h, "clusters"), with the geometry of its groups,
+// GroupStats(ids, sizes) (include/pcgx.h, "group geometry").
 type KDTree = pcgx.KDTree
 
 // KDTreeOption is kdtree.KDTreeOption (kdtree.go:31).

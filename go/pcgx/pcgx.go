@@ -580,6 +580,52 @@ func (k *KDTree) Clusters(radius float32, p ClusterParams) (labels, sizes, ids [
 	return labels, sizes, ids[:int(total)], nil
 }
 
+// GroupGeometry is the result of (*KDTree).GroupStats, one row per group: Count of live members; AABB lo x, y, z then
+// hi x, y, z; Centroid; Cov in the order xx, xy, xz, yy, yz, zz; Eig descending; Axes: the three unit eigenvectors as
+// rows (axis 2 is the fitted plane's normal); OBB: centre x, y, z, then the half-extents along the axes.  A group
+// without a live member is all zero.
+type GroupGeometry struct {
+	Count    []int64
+	AABB     [][6]float32
+	Centroid [][3]float64
+	Cov      [][6]float64
+	Eig      [][3]float64
+	Axes     [][9]float64
+	OBB      [][6]float64
+}
+
+// GroupStats returns the geometry of every group of a grouped id list over the tree's points (extension: no reference
+// parity; include/pcgx.h, pcgx_kdtree_group_stats): ids holds group 0's members, then group 1's, and so on, sizes the
+// groups' sizes -- what Clusters returns.  An id outside [0, Len()) or sizes that add up to more than len(ids) are
+// ErrInvalid.
+func (k *KDTree) GroupStats(ids, sizes []int64) (*GroupGeometry, error) {
+	runtime.LockOSThread() // the error text is thread-local on the C side: call and pcgx_last_error on one OS thread
+	defer runtime.UnlockOSThread()
+	defer runtime.KeepAlive(k) // the finalizer must not free the handle while a call is in flight
+	g := len(sizes)
+	r := &GroupGeometry{Count: make([]int64, g), AABB: make([][6]float32, g), Centroid: make([][3]float64, g),
+		Cov: make([][6]float64, g), Eig: make([][3]float64, g), Axes: make([][9]float64, g), OBB: make([][6]float64, g)}
+	if g == 0 {
+		return r, nil
+	}
+	var pi *C.int64_t
+	if len(ids) > 0 {
+		pi = (*C.int64_t)(unsafe.Pointer(&ids[0]))
+	}
+	rc := C.pcgx_kdtree_group_stats(k.t.h, pi, C.int64_t(len(ids)), (*C.int64_t)(unsafe.Pointer(&sizes[0])), C.int64_t(g),
+		(*C.int64_t)(unsafe.Pointer(&r.Count[0])), (*C.float)(unsafe.Pointer(&r.AABB[0])),
+		(*C.double)(unsafe.Pointer(&r.Centroid[0])), (*C.double)(unsafe.Pointer(&r.Cov[0])),
+		(*C.double)(unsafe.Pointer(&r.Eig[0])), (*C.double)(unsafe.Pointer(&r.Axes[0])),
+		(*C.double)(unsafe.Pointer(&r.OBB[0])))
+	runtime.KeepAlive(ids)
+	runtime.KeepAlive(sizes)
+	runtime.KeepAlive(r)
+	if err := status(rc); err != nil {
+		return nil, err
+	}
+	return r, nil
+}
+
 // FPFHMatch finds, for every row of a, the nearest usable row of b and the runner-up's distance (extension: no
 // reference parity; include/pcgx.h, "FPFH matching"): float32 squared distances over the 33 values, summed left to
 // right, ties to the smaller id.  ids[i] is -1 and both distances are +Inf where a's row is unusable (not finite, or

@@ -1032,6 +1032,80 @@ PCGX_API pcgx_status pcgx_kdtree_clusters_dev(const pcgx_kdtree *t, float radius
                                               int32_t *d_n_clusters, int32_t *d_sizes /* [Len()], may be NULL */,
                                               int32_t *d_ids /* [Len()], may be NULL */, void *stream);
 
+/* ------------------------------------------- group geometry (extension: no reference parity)
+ * NOT in the reference.  What a user takes from clusters next: per group of a grouped id list over the tree's own
+ * points -- the shape pcgx_kdtree_clusters writes, and what region growing's components, a plane's inliers or a keypoint
+ * list are -- the count, the axis-aligned box, centroid and covariance, the covariance's eigenvalues and axes (the fitted
+ * plane and the principal frame) and the oriented box in that frame.  This comment is the contract,
+ * tests/group_oracle.py restates it.
+ *   pcgx_kdtree_group_stats    (t, ids[n_ids] i64, n_ids, sizes[n_groups] i64, n_groups, outputs...)
+ *   pcgx_kdtree_group_stats_dev(t, d_ids[cap_ids] i32, cap_ids, d_sizes[cap_groups] i32, cap_groups,
+ *                               d_n_groups (one int32; NULL: cap_groups), outputs... [cap_groups rows], stream)
+ * Groups: on the device form G = clamp(*d_n_groups, 0, cap_groups), read on the device; on the host form G = n_groups.
+ *   Group g owns the slots [o_g, o_g + max(sizes[g], 0)) of ids, o_g = the sum of the earlier (clamped) sizes: the
+ *   layout pcgx_kdtree_clusters writes.  Slots at or beyond cap_ids do not exist: the list is clipped there.  The labels
+ *   array is not an input.  d_ids, d_sizes and d_n_clusters of pcgx_kdtree_clusters_dev can be passed on as they are,
+ *   with cap_ids = cap_groups = Len().
+ * Live member: a slot is live when 0 <= id < Len() and the point's three coordinates are finite.  Ids may repeat and
+ *   are then counted each time.  Deleted ids are allowed and use the stored coordinates (as pcgx_kdtree_fpfh_at allows).
+ *   A dead slot is skipped; this covers the -1 padding.  The host form rejects an id outside [0, Len()) and a size sum
+ *   above n_ids, as pcgx_kdtree_fpfh_at does, and then writes nothing.
+ * Outputs: each may be NULL.  Every row of [0, cap_groups) is written on every call; rows >= G, and rows of groups
+ *   without a live member, are all zero.
+ *   count[g]        the number of live members (int32 on the device, int64 on the host).
+ *   aabb[6 g ..]    float32: lo x, y, z then hi x, y, z over the live members.  Exact.
+ *   centroid[3 g ..], cov[6 g ..]  float64: the mean of the members, and sum d d^T / n - m m^T in the order (xx, xy, xz,
+ *                   yy, yz, zz) (csrc/cov3.h), both evaluated in float64 with the sums centred on a pivot inside the
+ *                   group's own box: the box centre (lo + hi) / 2 widened to double.  d = p - pivot in float64, the sums
+ *                   with one rounding per term (the products are fused into the additions), in an order fixed by the
+ *                   group's place in the list alone: per run of the group inside 64 consecutive slots, then the runs in
+ *                   slot order (a group of more than four such runs: lanes striding the runs, then a butterfly over the
+ *                   64 partial sums); centroid = pivot + s / n,
+ *                   cov = q / n - (s / n)(s / n)^T (csrc/group_terms.h).
+ *                   Bounds, n the live count, D the diagonal of the group's box: each element of cov within
+ *                   (2 n + 4) 2^-53 D^2 of the exact value (tests/cov_exact.py's bound B with S <= D^2; it holds for any
+ *                   pivot inside the box and any order), each component c of the centroid within
+ *                   (n + 2) 2^-53 D + 2^-53 |c| of the exact mean (n - 1 additions of terms bounded by D, the division,
+ *                   the addition of the pivot).  Both take p - pivot to be exact in float64, which it is whenever a
+ *                   group's nonzero coordinates along an axis differ by less than 2^28 in magnitude.
+ *   eig[3 g ..]     float64: the eigenvalues of cov, descending.
+ *   axes[9 g ..]    float64: the three unit eigenvectors as rows, in that order.  Axis 2 is the fitted plane's normal,
+ *                   the plane passes through the centroid, and eig[2] / (eig[0] + eig[1] + eig[2]) is the surface
+ *                   variation pcgx_kdtree_normals calls curvature.  Sign: axis 0 and axis 1 are each turned so that their
+ *                   component of largest magnitude is positive (on a tie the first such component decides);
+ *                   axis 2 = axis 0 x axis 1, so the frame is right-handed.  If the trace is 0 or not finite (all
+ *                   members at one place), eig = 0 and axes = identity.  Equal eigenvalues keep the order of their
+ *                   diagonal positions (x, y, z) in the solve: cyclic Jacobi at unit trace, as csrc/cov3.h.
+ *   obb[6 g ..]     float64: with e-_k and e+_k the least and greatest of (p - centroid) . axis_k over the live members,
+ *                   evaluated in float64: the centre centroid + sum_k ((e+_k + e-_k) / 2) axis_k as x, y, z, then the
+ *                   half-extents h_k = (e+_k - e-_k) / 2.  The principal-axes box, not the box of smallest volume.
+ * PCGX_E_INVALID: a NULL tree; negative counts or capacities; NULL ids or sizes with a positive count; more than
+ *   2^31 - 1 slots (or groups); on the host form an id outside [0, Len()) or a size sum above n_ids.  G = 0 or
+ *   cap_groups = 0 is PCGX_OK.
+ * Determinism: the same input gives the same bits on every call.  No floating-point atomic feeds a sum; min / max are
+ *   combined with integer atomics on order-preserving keys, in any order.
+ * Always computed on the device (csrc/group_stats.hip), nothing read back in the device form.  Cost: three gathers of
+ *   16 B per slot (box, moments, extents; two when obb is NULL), 16 B of reads per slot and pass for the slot -> group
+ *   map and the ids, one record of 80 B per run of a group inside 64 consecutive slots in an array of
+ *   ceil(cap_ids / 64) + cap_groups records, and per group 24 + 48 B of keys, 96 B of frame and a Jacobi solve in one
+ *   lane.  The id -> node map of the handle is made on first use (as pcgx_kdtree_fpfh_at makes it). */
+PCGX_API pcgx_status pcgx_kdtree_group_stats(const pcgx_kdtree *t, const int64_t *ids /* [n_ids] */, int64_t n_ids,
+                                             const int64_t *sizes /* [n_groups] */, int64_t n_groups,
+                                             int64_t *count /* [n_groups] */, float *aabb /* [6 n_groups] */,
+                                             double *centroid /* [3 n_groups] */, double *cov /* [6 n_groups] */,
+                                             double *eig /* [3 n_groups] */, double *axes /* [9 n_groups] */,
+                                             double *obb /* [6 n_groups] */);
+/* Same, every array device resident (ids, sizes and counts are int32 there), enqueued on `stream` (NULL: the library's);
+ * returns without waiting, reads nothing back. */
+PCGX_API pcgx_status pcgx_kdtree_group_stats_dev(const pcgx_kdtree *t, const int32_t *d_ids /* [cap_ids] */,
+                                                 int64_t cap_ids, const int32_t *d_sizes /* [cap_groups] */,
+                                                 int64_t cap_groups, const int32_t *d_n_groups /* may be NULL */,
+                                                 int32_t *d_count, float *d_aabb, double *d_centroid, double *d_cov,
+                                                 double *d_eig, double *d_axes, double *d_obb, void *stream);
+/* Slots per tile of the slot -> group map; the gathers cut a run of a group every 64 slots and take four tiles to a
+ * workgroup (the boundaries the tests put groups across). */
+PCGX_API int32_t pcgx_group_stats_tile(void);
+
 /* ------------------------------------------- pose from correspondences (extension: no reference parity)
  * NOT in the reference.  The rigid motion (a proper rotation and a translation, no scale) that most pairs of a
  * correspondence list agree on, by sample consensus: the starting pose every Fit here needs, from what

@@ -304,6 +304,33 @@ class KDTree {  // pc/storage/kdtree/kdtree.go:14-23
     r.ids.resize(total);
     return r;
   }
+  // Group geometry (extension: no reference parity; include/pcgx.h, pcgx_kdtree_group_stats): per group of a grouped id
+  // list over the tree's own points -- ids: group 0's members, then group 1's, ...; sizes: per group; what Clusters
+  // returns -- the count of live members, the axis-aligned box (lo xyz, hi xyz), centroid and covariance (xx, xy, xz,
+  // yy, yz, zz), the covariance's eigenvalues (descending) and unit axes (three rows of three; axis 2 is the fitted
+  // plane's normal) and the oriented box in that frame (centre xyz, then the half-extents).  Row g of every array is
+  // group g's; a group without a live member is all zero.
+  struct GroupStatsResult {
+    std::vector<int64_t> count;
+    std::vector<float> aabb;                           // 6 per group
+    std::vector<double> centroid, cov, eig, axes, obb; // 3, 6, 3, 9, 6 per group
+  };
+  GroupStatsResult GroupStats(const std::vector<int64_t> &ids, const std::vector<int64_t> &sizes) const {
+    const size_t g = sizes.size();
+    GroupStatsResult r;
+    r.count.resize(g);
+    r.aabb.resize(6 * g);
+    r.centroid.resize(3 * g);
+    r.cov.resize(6 * g);
+    r.eig.resize(3 * g);
+    r.axes.resize(9 * g);
+    r.obb.resize(6 * g);
+    check(pcgx_kdtree_group_stats(h_.get(), ids.data(), (int64_t)ids.size(), sizes.data(), (int64_t)g, r.count.data(),
+                                  r.aabb.data(), r.centroid.data(), r.cov.data(), r.eig.data(), r.axes.data(),
+                                  r.obb.data()));
+    return r;
+  }
+  GroupStatsResult GroupStats(const ClustersResult &c) const { return GroupStats(c.ids, c.sizes); }
   // The k points with the smallest (DistSq, ID) among those with DistSq < maxRange^2, ascending (extension: no
   // reference parity; include/pcgx.h, pcgx_kdtree_knearest: ties go by ID).
   std::vector<Neighbor> KNearest(const Vec3 &p, int32_t k, float maxRange) const {

@@ -1,8 +1,9 @@
 """pc/storage/kdtree mirror: KDTree on the GPU behind the storage.Search shape
 (pc/storage/search.go:13-17): Vec3At / Len / Nearest, plus batched NearestBatch, and extensions with no
 reference counterpart: surface normals (Normals), moving-least-squares smoothing (MLS), FPFH descriptors
-(FPFH, FPFHAt), keypoints (LocalMaxima, ISSKeypoints), cluster extraction (Clusters), k nearest neighbours
-(KNearest) and their covariances (Covariances)."""
+(FPFH, FPFHAt), keypoints (LocalMaxima, ISSKeypoints), cluster extraction (Clusters), per-group geometry
+(GroupStats), k nearest neighbours (KNearest) and their covariances (Covariances)."""
+import collections
 import ctypes as C
 
 import numpy as np
@@ -20,6 +21,15 @@ class Neighbor:  # pc/storage/search.go:8-11
 
     def __repr__(self):
         return "Neighbor{ID:%d, DistSq:%r}" % (self.ID, float(self.DistSq))
+
+
+GroupGeometry = collections.namedtuple("GroupGeometry", "count aabb centroid cov eig axes obb")  # KDTree.GroupStats
+
+
+def GroupStatsTile():
+    """Slots per tile of GroupStats' slot -> group map (the gathers cut a group's runs every 64 slots and take four
+    tiles to a workgroup): the boundaries the tests put groups across."""
+    return int(L.lib().pcgx_group_stats_tile())
 
 
 class KDTree:
@@ -361,6 +371,35 @@ class KDTree:
             self._h, float(radius), opt(d_normals), float(MinCos), int(bool(Oriented)), opt(d_curvature),
             float(MaxCurvature), int(MinSize), int(MaxSize), opt(d_labels), opt(d_n_clusters), opt(d_sizes), opt(d_ids),
             L.ptr(stream) if stream else None))
+
+    # -- extension (no reference parity): group geometry, the moments, boxes and planes of a grouped id list
+    def GroupStats(self, ids, sizes):
+        """Per group of a grouped id list over the tree's own points (ids: group 0's members, then group 1's, ...;
+        sizes: per group -- what Clusters returns) -> GroupGeometry(count int64 (G,), aabb float32 (G, 6) lo xyz hi
+        xyz, centroid float64 (G, 3), cov float64 (G, 6) xx xy xz yy yz zz, eig float64 (G, 3) descending, axes float64
+        (G, 3, 3) unit eigenvectors as rows (axis 2: the fitted plane's normal), obb float64 (G, 6) centre xyz and
+        half-extents along the axes).  A group without a live member is all zero (include/pcgx.h,
+        pcgx_kdtree_group_stats)."""
+        ids = np.ascontiguousarray(ids, np.int64).reshape(-1)
+        sizes = np.ascontiguousarray(sizes, np.int64).reshape(-1)
+        g = len(sizes)
+        out = GroupGeometry(np.zeros(g, np.int64), np.zeros((g, 6), np.float32), np.zeros((g, 3)), np.zeros((g, 6)),
+                            np.zeros((g, 3)), np.zeros((g, 3, 3)), np.zeros((g, 6)))
+        L.check(L.lib().pcgx_kdtree_group_stats(self._h, L.ptr(ids) if len(ids) else None, len(ids),
+                                                L.ptr(sizes) if g else None, g, *[L.ptr(a) if g else None for a in out]))
+        return out
+
+    def GroupStatsDev(self, d_ids, cap_ids, d_sizes, cap_groups, d_n_groups=0, d_count=0, d_aabb=0, d_centroid=0, d_cov=0,
+                      d_eig=0, d_axes=0, d_obb=0, stream=0):
+        """Device-resident GroupStats: raw device addresses (e.g. torch .data_ptr()); d_ids int32 [cap_ids], d_sizes
+        int32 [cap_groups], d_n_groups one int32 (0: cap_groups groups) -- ClustersDev's d_ids, d_sizes and d_n_clusters
+        as they are, with cap_ids = cap_groups = Len(); the outputs (0: not wanted) hold cap_groups rows: d_count int32,
+        d_aabb float32 [6], d_centroid [3], d_cov [6], d_eig [3], d_axes [9], d_obb [6] float64.  Enqueued on `stream`,
+        returns without waiting; nothing is read back."""
+        opt = lambda a: L.ptr(int(a)) if a else None  # noqa: E731
+        L.check(L.lib().pcgx_kdtree_group_stats_dev(
+            self._h, opt(d_ids), int(cap_ids), opt(d_sizes), int(cap_groups), opt(d_n_groups), opt(d_count), opt(d_aabb),
+            opt(d_centroid), opt(d_cov), opt(d_eig), opt(d_axes), opt(d_obb), L.ptr(stream) if stream else None))
 
     # -- extension (no reference parity): k nearest neighbours
     def KNearest(self, p, k, maxRange):

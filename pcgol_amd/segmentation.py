@@ -178,7 +178,7 @@ class ClusterExtraction:
         self.min_size, self.max_size = int(MinClusterSize), int(MaxClusterSize)
         self.normals = self.curvature = None
         self.min_cos, self.oriented, self.max_curvature = 0.0, False, 0.0
-        self.labels = self.sizes = None
+        self.labels = self.sizes = self.ids = None
 
     New = classmethod(lambda cls, search, *a, **k: cls(search, *a, **k))
 
@@ -209,4 +209,12 @@ class ClusterExtraction:
         self.labels, self.sizes, ids = self.search.Clusters(
             self.tolerance, Normals=self.normals, MinCos=self.min_cos, Oriented=self.oriented, Curvature=self.curvature,
             MaxCurvature=self.max_curvature, MinSize=self.min_size, MaxSize=self.max_size)
+        self.ids = ids
         return np.split(ids, np.cumsum(self.sizes)[:-1]) if len(self.sizes) else []
+
+    def Boxes(self):
+        """After Extract(): the geometry of the extracted clusters, one row each -> KDTree.GroupStats' tuple (count,
+        aabb, centroid, cov, eig, axes, obb): a centre, a box to track, a plane to test."""
+        if self.sizes is None:
+            raise RuntimeError("Boxes() needs Extract() first")
+        return self.search.GroupStats(self.ids, self.sizes)
