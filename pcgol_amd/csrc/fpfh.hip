@@ -2,7 +2,7 @@
 // neighbourhoods and caller-given normals (extension: no reference parity; include/pcgx.h, "FPFH descriptors").
 //
 // The input of feature-based coarse alignment, the step before every ICP here.  Two kernels over the enumeration that
-// Range, normals and region growing share (range_enum.h), one query per lane, the queries the tree's own points as
+// Range, normals and region growing share (radius_visit.h), one query per lane, the queries the tree's own points as
 // query_source lays them out, on each of the three kinds of handle (grid, forced walk, patched tree after DeletePoint):
 //   spfh_kernel  per neighbour: its normal by id, the pair's three bins (fpfh_terms.h), three 32-bit counters of the
 //                lane's column of an LDS table [34][64] (the bin index is dynamic: registers indexed by it would go to
@@ -13,30 +13,29 @@
 // The record keeps the COUNTS, not 100 c / m rounded to float32: the same 144 bytes, one division per neighbour
 // instead of none, and the sums are then those of the contract's real numbers to float64 rounding -- a bin nobody
 // counted is exactly 0, and the factor 100 cancels in W / T.
-// A fat row (kRangeFatRow) is the whole wave's work in both kernels, as in normals_kernel: every lane takes every 64th
-// record of the owner's row; the counts go into the owner's LDS column by LDS atomics (integers: any order gives the
-// same bits), the float64 partials are summed by shuffles.
+// Of a fat row's shares, in both kernels: the counts go into the owner's LDS column by LDS atomics (integers: any order
+// gives the same bits), the float64 partials are summed by shuffles.
 //
 // Descriptors at chosen ids only (pcgx_kdtree_fpfh_at, include/pcgx.h "FPFH at chosen points"): three stages over the
 // same enumeration; the queries of the first and the third are the selected points, fetched by id, one slot per lane:
-//   fpfh_mark_kernel  a 1 into need[j] for the slot's point and for every member of its N(.) (plain byte stores of one
-//                     value: no atomics, any order), the slot's xyz, and a dead slot's zeros.
-//   spfh_need_kernel  spfh_kernel over the tree's own points in cell order, except that a lane whose need byte is 0
-//                     enumerates nothing and writes no record (local_maxima_kernel's way with a score that cannot
-//                     qualify).  The flags are then counted by bucket_grid.h's tile count and one scan workgroup.
-//   fpfh_at_kernel    fpfh_kernel with the records read by id and the row written at the slot.  A lane's sums run over
-//                     its query's neighbourhood in the order fpfh_kernel's lane takes for that point (the rows of the
-//                     grid as grid_cover names them, a walk from the root), so the row is fpfh_kernel's, bit for bit.
-// They are kernels of their own, not instantiations of a body shared with the two above: pcgx_kdtree_fpfh keeps the
-// instructions it had.
+//   fpfh_mark_kernel         a 1 into need[j] for the slot's point and for every member of its N(.) (plain byte stores
+//                            of one value: no atomics, any order), the slot's xyz, and a dead slot's zeros.
+//   spfh_kernel<., true>     over the tree's own points in cell order; a lane whose need byte is 0 enumerates nothing
+//                            and writes no record (local_maxima_kernel's way with a score that cannot qualify).  The
+//                            flags are then counted by bucket_grid.h's tile count and one scan workgroup.
+//   fpfh_kernel<., true>     the query a live slot's point, the row written at the slot.  A lane's sums run over its
+//                            query's neighbourhood in the order the every-point form's lane takes for that point (the
+//                            rows of the grid as grid_cover names them, a walk from the root): the same row, bit for bit.
+// Each pair is one kernel template, the form a compile-time bool; what that did to the every-point instantiations'
+// resources and times is DESIGN.md 3.6.1.
 #include <math.h>
 #include <stdlib.h>
 
+#include <type_traits>
+
 #include "bucket_grid.h"
 #include "fpfh_terms.h"
-#include "knn_grid.h"
-#include "knn_xwalk.h"
-#include "range_walk.h"
+#include "radius_visit.h"
 
 namespace pcgx {
 
@@ -51,6 +50,7 @@ struct SpfhOut {
   uint4 *rec;            // [9 n]
   int32_t *counts;       // [33 n] or nullptr
   int32_t *pairs;        // [n] or nullptr
+  const uint8_t *need;   // [n], kNeed only: a record where the byte is set, the others stay unwritten and unread
 };
 
 // the pair (query s of column col, neighbour p) into the column's counters
@@ -68,7 +68,8 @@ __device__ __forceinline__ void spfh_pair(uint32_t *cnt, const int col, const fl
   atomicAdd(&cnt[kFpfhLen * kFpfhBlock + col], 1u);
 }
 
-template <int kSrc>
+// kNeed: only the points whose need byte is set (FPFH at chosen points); else every point
+template <int kSrc, bool kNeed>
 __global__ __launch_bounds__(kFpfhBlock) void spfh_kernel(GridView g, TreeView tv, XTreeView xv, QuerySource Q,
                                                           float bound, SpfhOut O, int64_t guard) {
   extern __shared__ uint32_t s_stack[];
@@ -78,43 +79,29 @@ __global__ __launch_bounds__(kFpfhBlock) void spfh_kernel(GridView g, TreeView t
   const int lane = (int)threadIdx.x;
 #pragma unroll
   for (int k = 0; k < kFpfhRows; k++) s_cnt[k * kFpfhBlock + lane] = 0u;
-  // (the grid path keeps every lane of the wave to the end: the fat rows are scanned by all 64)
-  const bool live = pos < Q.nq;
-  if (kSrc != kRangeGrid && !live) return;
+  bool live = pos < Q.nq;
   int64_t i = 0;
   float qx = 0.0f, qy = 0.0f, qz = 0.0f, nx = 0.0f, ny = 0.0f, nz = 0.0f;
   if (live) {
     read_query(Q, pos, i, qx, qy, qz);
+    if constexpr (kNeed) live = O.need[i] != 0;
+  }
+  if (live) {
     nx = O.normals[3 * i];
     ny = O.normals[3 * i + 1];
     nz = O.normals[3 * i + 2];
   }
-  auto take = [&](const float4 &p) {
-    if (ref_dist_sq(p.x, p.y, p.z, qx, qy, qz) < bound) spfh_pair(s_cnt, lane, O.normals, p, qx, qy, qz, nx, ny, nz);
-  };
-  if constexpr (kSrc == kRangeGrid) {
-    __syncthreads();  // (one wave: the zeroes are in place before another lane's atomics land in this column)
-    grid_radius_scan(g, qx, qy, qz, bound, live, take, [&](int owner, uint32_t rf, uint32_t re, float ox, float oy, float oz) {
-      const float onx = __shfl(nx, owner), ony = __shfl(ny, owner), onz = __shfl(nz, owner);
-      for (uint32_t r = rf + (uint32_t)lane; r < re; r += 64u) {
-        const float4 p = g.pts[r];
-        if (ref_dist_sq(p.x, p.y, p.z, ox, oy, oz) < bound) spfh_pair(s_cnt, owner, O.normals, p, ox, oy, oz, onx, ony, onz);
-      }
-    });
-    __syncthreads();  // the other lanes' atomics before the owner reads its column
-    if (!live) return;
-  } else if constexpr (kSrc == kRangeWalk) {
-    range_walk_nodes<false>(tv, s_stack + threadIdx.x, kFpfhBlock, qx, qy, qz, bound, [=]() { return bound; },
-                            [&](const float4 &nd, float) {  // (range_walk_nodes reports only DistSq < bound)
-                              spfh_pair(s_cnt, lane, O.normals, nd, qx, qy, qz, nx, ny, nz);
-                            });
-  } else {
-    auto hit = [&](const float4 &nd, float) {
-      take(nd);
-      return true;
-    };
-    xwalk(xv, s_stack + threadIdx.x, kFpfhBlock, qx, qy, qz, guard, [&]() { return bound; }, hit, hit);
-  }
+  // (one wave: the zeroes are in place before another lane's atomics land in this column)
+  if constexpr (kSrc == kRangeGrid) __syncthreads();
+  radius_visit<kSrc>(
+      RadiusViews{g, tv, xv, guard}, s_stack + threadIdx.x, kFpfhBlock, qx, qy, qz, bound, live,
+      [&](const float4 &p, float) { spfh_pair(s_cnt, lane, O.normals, p, qx, qy, qz, nx, ny, nz); },
+      [&](int owner, float ox, float oy, float oz, auto rows) {
+        const float onx = __shfl(nx, owner), ony = __shfl(ny, owner), onz = __shfl(nz, owner);
+        rows([&](const float4 &p, float) { spfh_pair(s_cnt, owner, O.normals, p, ox, oy, oz, onx, ony, onz); });
+      });
+  if constexpr (kSrc == kRangeGrid) __syncthreads();  // the other lanes' atomics before the owner reads its column
+  if (!live) return;
   uint32_t c[kFpfhRec];
 #pragma unroll
   for (int k = 0; k < kFpfhRec; k++) c[k] = k < kFpfhRows ? s_cnt[k * kFpfhBlock + lane] : 0u;
@@ -166,73 +153,7 @@ struct FpfhAcc {
   }
 };
 
-template <int kSrc>
-__global__ __launch_bounds__(kFpfhBlock) void fpfh_kernel(GridView g, TreeView tv, XTreeView xv, QuerySource Q,
-                                                          float bound, const uint4 *rec, float *fpfh, int64_t guard) {
-  extern __shared__ uint32_t s_stack[];
-  const uint32_t n_tiles = (uint32_t)((Q.nq + kFpfhBlock - 1) / kFpfhBlock);
-  const int64_t pos = (int64_t)xcd_tile(blockIdx.x, n_tiles) * kFpfhBlock + threadIdx.x;
-  const bool live = pos < Q.nq;
-  if (kSrc != kRangeGrid && !live) return;
-  int64_t i = 0;
-  float qx = 0.0f, qy = 0.0f, qz = 0.0f;
-  if (live) read_query(Q, pos, i, qx, qy, qz);
-  FpfhAcc acc;
-  acc.clear();
-  auto take = [&](const float4 &p) {
-    const float d = ref_dist_sq(p.x, p.y, p.z, qx, qy, qz);
-    if (d < bound) acc.add(rec, p, d);
-  };
-  if constexpr (kSrc == kRangeGrid) {
-    const int lane = (int)(threadIdx.x & 63u);
-    grid_radius_scan(g, qx, qy, qz, bound, live, take, [&](int owner, uint32_t rf, uint32_t re, float ox, float oy, float oz) {
-      FpfhAcc part;
-      part.clear();
-      for (uint32_t r = rf + (uint32_t)lane; r < re; r += 64u) {
-        const float4 p = g.pts[r];
-        const float d = ref_dist_sq(p.x, p.y, p.z, ox, oy, oz);
-        if (d < bound) part.add(rec, p, d);
-      }
-      part.wave_sum();
-      if (lane == owner) acc.merge(part);
-    });
-    if (!live) return;
-  } else if constexpr (kSrc == kRangeWalk) {
-    range_walk_nodes<false>(tv, s_stack + threadIdx.x, kFpfhBlock, qx, qy, qz, bound, [=]() { return bound; },
-                            [&](const float4 &nd, float d) {  // (range_walk_nodes reports only DistSq < bound)
-                              acc.add(rec, nd, d);
-                            });
-  } else {
-    auto hit = [&](const float4 &nd, float) {
-      take(nd);
-      return true;
-    };
-    xwalk(xv, s_stack + threadIdx.x, kFpfhBlock, qx, qy, qz, guard, [&]() { return bound; }, hit, hit);
-  }
-  // F = S_q + 100 W / T per feature
-  const uint4 *own = rec + (size_t)(kFpfhRec / 4) * (size_t)i;
-  uint4 q[kFpfhRec / 4];
-#pragma unroll
-  for (int k = 0; k < kFpfhRec / 4; k++) q[k] = own[k];
-  const uint32_t m = q[kFpfhLen / 4].y;
-  const double sq = m ? 100.0 / (double)m : 0.0;
-#pragma unroll
-  for (int f = 0; f < 3; f++) {
-    double T = 0.0;
-#pragma unroll
-    for (int b = 0; b < kFpfhBins; b++) T += acc.a[f * kFpfhBins + b];
-    const double sc = T > 0.0 ? 100.0 / T : 0.0;
-#pragma unroll
-    for (int b = 0; b < kFpfhBins; b++) {
-      const int k = f * kFpfhBins + b;
-      const uint4 &u = q[k / 4];
-      const uint32_t ck = k % 4 == 0 ? u.x : (k % 4 == 1 ? u.y : (k % 4 == 2 ? u.z : u.w));
-      fpfh[(size_t)kFpfhLen * (size_t)i + k] = (float)((double)ck * sq + acc.a[k] * sc);
-    }
-  }
-}
-
-// ---- descriptors at chosen ids
+// ---- descriptors at chosen ids: where the queries come from and where the rows go
 
 // the slots: ids[cap], of which the first clamp(*n_ids, 0, cap) count (n_ids == nullptr: all), and where a point's
 // xyz is found by id
@@ -274,167 +195,40 @@ struct FpfhAtOut {
   int32_t *pairs;   // [cap] or nullptr
 };
 
-template <int kSrc>
-__global__ __launch_bounds__(kFpfhBlock) void fpfh_mark_kernel(GridView g, TreeView tv, XTreeView xv, FpfhSlots S,
-                                                               float bound, uint8_t *__restrict__ need, FpfhAtOut O,
-                                                               int64_t guard) {
+// kAt: a query per slot, the live slot's point, and the row, the point's counts and its pairs written at the slot;
+// else the tree's own points as query_source lays them out, the row (O.fpfh alone) at the point's id
+template <int kSrc, bool kAt>
+__global__ __launch_bounds__(kFpfhBlock) void fpfh_kernel(GridView g, TreeView tv, XTreeView xv,
+                                                          std::conditional_t<kAt, FpfhSlots, QuerySource> Q, float bound,
+                                                          const uint4 *rec, FpfhAtOut O, int64_t guard) {
   extern __shared__ uint32_t s_stack[];
-  const int64_t s = (int64_t)blockIdx.x * kFpfhBlock + threadIdx.x;
-  int64_t i = 0;
+  int64_t i = 0, row = 0;
   float qx = 0.0f, qy = 0.0f, qz = 0.0f;
-  const bool live = read_slot<kSrc>(S, tv, s, i, qx, qy, qz);
-  if (s < (int64_t)S.cap) {
-    if (O.xyz) {
-      O.xyz[3 * s] = qx;
-      O.xyz[3 * s + 1] = qy;
-      O.xyz[3 * s + 2] = qz;
-    }
-    if (!live) {  // a dead slot: zeros (fpfh_at_kernel writes the live ones)
-      for (int k = 0; k < kFpfhLen; k++) {
-        O.fpfh[(size_t)kFpfhLen * (size_t)s + k] = 0.0f;
-        if (O.counts) O.counts[(size_t)kFpfhLen * (size_t)s + k] = 0;
-      }
-      if (O.pairs) O.pairs[s] = 0;
-    }
-  }
-  // (the grid path keeps every lane of the wave to the end: the fat rows are scanned by all 64)
-  if (kSrc != kRangeGrid && !live) return;
-  if (live) need[i] = (uint8_t)1;  // (a deleted id, a NaN coordinate: the point does not meet itself)
-  auto take = [&](const float4 &p) {
-    if (ref_dist_sq(p.x, p.y, p.z, qx, qy, qz) < bound) need[__float_as_uint(p.w)] = (uint8_t)1;
-  };
-  if constexpr (kSrc == kRangeGrid) {
-    const int lane = (int)(threadIdx.x & 63u);
-    grid_radius_scan(g, qx, qy, qz, bound, live, take, [&](int, uint32_t rf, uint32_t re, float ox, float oy, float oz) {
-      for (uint32_t r = rf + (uint32_t)lane; r < re; r += 64u) {
-        const float4 p = g.pts[r];
-        if (ref_dist_sq(p.x, p.y, p.z, ox, oy, oz) < bound) need[__float_as_uint(p.w)] = (uint8_t)1;
-      }
-    });
-  } else if constexpr (kSrc == kRangeWalk) {
-    range_walk_nodes<false>(tv, s_stack + threadIdx.x, kFpfhBlock, qx, qy, qz, bound, [=]() { return bound; },
-                            [&](const float4 &nd, float) {  // (range_walk_nodes reports only DistSq < bound)
-                              need[__float_as_uint(nd.w)] = (uint8_t)1;
-                            });
+  bool live;
+  if constexpr (kAt) {
+    row = (int64_t)blockIdx.x * kFpfhBlock + threadIdx.x;
+    live = read_slot<kSrc>(Q, tv, row, i, qx, qy, qz);
   } else {
-    auto hit = [&](const float4 &nd, float) {
-      take(nd);
-      return true;
-    };
-    xwalk(xv, s_stack + threadIdx.x, kFpfhBlock, qx, qy, qz, guard, [&]() { return bound; }, hit, hit);
+    const uint32_t n_tiles = (uint32_t)((Q.nq + kFpfhBlock - 1) / kFpfhBlock);
+    const int64_t pos = (int64_t)xcd_tile(blockIdx.x, n_tiles) * kFpfhBlock + threadIdx.x;
+    live = pos < Q.nq;
+    if (live) read_query(Q, pos, i, qx, qy, qz);
+    row = i;
   }
-}
-
-// spfh_kernel, for the points whose need byte is set; the others' records stay unwritten and nobody reads them
-template <int kSrc>
-__global__ __launch_bounds__(kFpfhBlock) void spfh_need_kernel(GridView g, TreeView tv, XTreeView xv, QuerySource Q,
-                                                               float bound, const uint8_t *__restrict__ need,
-                                                               const float *normals, uint4 *rec, int64_t guard) {
-  extern __shared__ uint32_t s_stack[];
-  __shared__ uint32_t s_cnt[kFpfhRows * kFpfhBlock];
-  const uint32_t n_tiles = (uint32_t)((Q.nq + kFpfhBlock - 1) / kFpfhBlock);
-  const int64_t pos = (int64_t)xcd_tile(blockIdx.x, n_tiles) * kFpfhBlock + threadIdx.x;
-  const int lane = (int)threadIdx.x;
-#pragma unroll
-  for (int k = 0; k < kFpfhRows; k++) s_cnt[k * kFpfhBlock + lane] = 0u;
-  int64_t i = 0;
-  float qx = 0.0f, qy = 0.0f, qz = 0.0f, nx = 0.0f, ny = 0.0f, nz = 0.0f;
-  bool want = false;
-  if (pos < Q.nq) {
-    read_query(Q, pos, i, qx, qy, qz);
-    want = need[i] != 0;
-  }
-  // (the grid path keeps every lane of the wave to the end: the fat rows are scanned by all 64)
-  if (kSrc != kRangeGrid && !want) return;
-  if (want) {
-    nx = normals[3 * i];
-    ny = normals[3 * i + 1];
-    nz = normals[3 * i + 2];
-  }
-  auto take = [&](const float4 &p) {
-    if (ref_dist_sq(p.x, p.y, p.z, qx, qy, qz) < bound) spfh_pair(s_cnt, lane, normals, p, qx, qy, qz, nx, ny, nz);
-  };
-  if constexpr (kSrc == kRangeGrid) {
-    __syncthreads();  // (one wave: the zeroes are in place before another lane's atomics land in this column)
-    grid_radius_scan(g, qx, qy, qz, bound, want, take, [&](int owner, uint32_t rf, uint32_t re, float ox, float oy, float oz) {
-      const float onx = __shfl(nx, owner), ony = __shfl(ny, owner), onz = __shfl(nz, owner);
-      for (uint32_t r = rf + (uint32_t)lane; r < re; r += 64u) {
-        const float4 p = g.pts[r];
-        if (ref_dist_sq(p.x, p.y, p.z, ox, oy, oz) < bound) spfh_pair(s_cnt, owner, normals, p, ox, oy, oz, onx, ony, onz);
-      }
-    });
-    __syncthreads();  // the other lanes' atomics before the owner reads its column
-    if (!want) return;
-  } else if constexpr (kSrc == kRangeWalk) {
-    range_walk_nodes<false>(tv, s_stack + threadIdx.x, kFpfhBlock, qx, qy, qz, bound, [=]() { return bound; },
-                            [&](const float4 &nd, float) {  // (range_walk_nodes reports only DistSq < bound)
-                              spfh_pair(s_cnt, lane, normals, nd, qx, qy, qz, nx, ny, nz);
-                            });
-  } else {
-    auto hit = [&](const float4 &nd, float) {
-      take(nd);
-      return true;
-    };
-    xwalk(xv, s_stack + threadIdx.x, kFpfhBlock, qx, qy, qz, guard, [&]() { return bound; }, hit, hit);
-  }
-  uint32_t c[kFpfhRec];
-#pragma unroll
-  for (int k = 0; k < kFpfhRec; k++) c[k] = k < kFpfhRows ? s_cnt[k * kFpfhBlock + lane] : 0u;
-#pragma unroll
-  for (int k = 0; k < kFpfhRec / 4; k++) rec[(kFpfhRec / 4) * i + k] = make_uint4(c[4 * k], c[4 * k + 1], c[4 * k + 2], c[4 * k + 3]);
-}
-
-__global__ __launch_bounds__(256) void fpfh_need_count_kernel(const uint8_t *__restrict__ need, int64_t n,
-                                                              uint32_t *__restrict__ tile_count) {
-  tile_flag_count(n, [&](int64_t j) { return need[j] != 0; }, tile_count);
-}
-__global__ __launch_bounds__(1024) void fpfh_need_scan_kernel(uint32_t *__restrict__ tile_count, int ntiles,
-                                                              uint32_t *__restrict__ total) {
-  tile_scan(tile_count, ntiles, total);
-}
-
-// fpfh_kernel, the queries the live slots' points; the row, the point's counts and its pairs go to the slot
-template <int kSrc>
-__global__ __launch_bounds__(kFpfhBlock) void fpfh_at_kernel(GridView g, TreeView tv, XTreeView xv, FpfhSlots S,
-                                                             float bound, const uint4 *rec, FpfhAtOut O, int64_t guard) {
-  extern __shared__ uint32_t s_stack[];
-  const int64_t s = (int64_t)blockIdx.x * kFpfhBlock + threadIdx.x;
-  int64_t i = 0;
-  float qx = 0.0f, qy = 0.0f, qz = 0.0f;
-  const bool live = read_slot<kSrc>(S, tv, s, i, qx, qy, qz);
-  if (kSrc != kRangeGrid && !live) return;
+  const int lane = (int)(threadIdx.x & 63u);
   FpfhAcc acc;
   acc.clear();
-  auto take = [&](const float4 &p) {
-    const float d = ref_dist_sq(p.x, p.y, p.z, qx, qy, qz);
-    if (d < bound) acc.add(rec, p, d);
-  };
-  if constexpr (kSrc == kRangeGrid) {
-    const int lane = (int)(threadIdx.x & 63u);
-    grid_radius_scan(g, qx, qy, qz, bound, live, take, [&](int owner, uint32_t rf, uint32_t re, float ox, float oy, float oz) {
-      FpfhAcc part;
-      part.clear();
-      for (uint32_t r = rf + (uint32_t)lane; r < re; r += 64u) {
-        const float4 p = g.pts[r];
-        const float d = ref_dist_sq(p.x, p.y, p.z, ox, oy, oz);
-        if (d < bound) part.add(rec, p, d);
-      }
-      part.wave_sum();
-      if (lane == owner) acc.merge(part);
-    });
-    if (!live) return;
-  } else if constexpr (kSrc == kRangeWalk) {
-    range_walk_nodes<false>(tv, s_stack + threadIdx.x, kFpfhBlock, qx, qy, qz, bound, [=]() { return bound; },
-                            [&](const float4 &nd, float d) {  // (range_walk_nodes reports only DistSq < bound)
-                              acc.add(rec, nd, d);
-                            });
-  } else {
-    auto hit = [&](const float4 &nd, float) {
-      take(nd);
-      return true;
-    };
-    xwalk(xv, s_stack + threadIdx.x, kFpfhBlock, qx, qy, qz, guard, [&]() { return bound; }, hit, hit);
-  }
+  radius_visit<kSrc>(
+      RadiusViews{g, tv, xv, guard}, s_stack + threadIdx.x, kFpfhBlock, qx, qy, qz, bound, live,
+      [&](const float4 &p, float d) { acc.add(rec, p, d); },
+      [&](int owner, float, float, float, auto rows) {
+        FpfhAcc part;
+        part.clear();
+        rows([&](const float4 &p, float d) { part.add(rec, p, d); });
+        part.wave_sum();
+        if (lane == owner) acc.merge(part);
+      });
+  if (!live) return;
   // F = S_q + 100 W / T per feature
   const uint4 *own = rec + (size_t)(kFpfhRec / 4) * (size_t)i;
   uint4 q[kFpfhRec / 4];
@@ -453,11 +247,53 @@ __global__ __launch_bounds__(kFpfhBlock) void fpfh_at_kernel(GridView g, TreeVie
       const int k = f * kFpfhBins + b;
       const uint4 &u = q[k / 4];
       const uint32_t ck = k % 4 == 0 ? u.x : (k % 4 == 1 ? u.y : (k % 4 == 2 ? u.z : u.w));
-      O.fpfh[(size_t)kFpfhLen * (size_t)s + k] = (float)((double)ck * sq + acc.a[k] * sc);
-      if (O.counts) O.counts[(size_t)kFpfhLen * (size_t)s + k] = (int32_t)ck;
+      O.fpfh[(size_t)kFpfhLen * (size_t)row + k] = (float)((double)ck * sq + acc.a[k] * sc);
+      if constexpr (kAt) {
+        if (O.counts) O.counts[(size_t)kFpfhLen * (size_t)row + k] = (int32_t)ck;
+      }
     }
   }
-  if (O.pairs) O.pairs[s] = (int32_t)m;
+  if constexpr (kAt) {
+    if (O.pairs) O.pairs[row] = (int32_t)m;
+  }
+}
+
+template <int kSrc>
+__global__ __launch_bounds__(kFpfhBlock) void fpfh_mark_kernel(GridView g, TreeView tv, XTreeView xv, FpfhSlots S,
+                                                               float bound, uint8_t *__restrict__ need, FpfhAtOut O,
+                                                               int64_t guard) {
+  extern __shared__ uint32_t s_stack[];
+  const int64_t s = (int64_t)blockIdx.x * kFpfhBlock + threadIdx.x;
+  int64_t i = 0;
+  float qx = 0.0f, qy = 0.0f, qz = 0.0f;
+  const bool live = read_slot<kSrc>(S, tv, s, i, qx, qy, qz);
+  if (s < (int64_t)S.cap) {
+    if (O.xyz) {
+      O.xyz[3 * s] = qx;
+      O.xyz[3 * s + 1] = qy;
+      O.xyz[3 * s + 2] = qz;
+    }
+    if (!live) {  // a dead slot: zeros (fpfh_kernel<., true> writes the live ones)
+      for (int k = 0; k < kFpfhLen; k++) {
+        O.fpfh[(size_t)kFpfhLen * (size_t)s + k] = 0.0f;
+        if (O.counts) O.counts[(size_t)kFpfhLen * (size_t)s + k] = 0;
+      }
+      if (O.pairs) O.pairs[s] = 0;
+    }
+  }
+  if (live) need[i] = (uint8_t)1;  // (a deleted id, a NaN coordinate: the point does not meet itself)
+  auto mark = [&](const float4 &p, float) { need[__float_as_uint(p.w)] = (uint8_t)1; };
+  radius_visit<kSrc>(RadiusViews{g, tv, xv, guard}, s_stack + threadIdx.x, kFpfhBlock, qx, qy, qz, bound, live, mark,
+                     [&](int, float, float, float, auto rows) { rows(mark); });
+}
+
+__global__ __launch_bounds__(256) void fpfh_need_count_kernel(const uint8_t *__restrict__ need, int64_t n,
+                                                              uint32_t *__restrict__ tile_count) {
+  tile_flag_count(n, [&](int64_t j) { return need[j] != 0; }, tile_count);
+}
+__global__ __launch_bounds__(1024) void fpfh_need_scan_kernel(uint32_t *__restrict__ tile_count, int ntiles,
+                                                              uint32_t *__restrict__ total) {
+  tile_scan(tile_count, ntiles, total);
 }
 
 }  // namespace pcgx
@@ -480,9 +316,9 @@ void fpfh_launch(const pcgx_kdtree *t, const TreeView &tv, const XTreeView &xv, 
   const dim3 grid(xcd_grid((unsigned)((Q.nq + kFpfhBlock - 1) / kFpfhBlock))), block(kFpfhBlock);
   const int64_t guard = xwalk_guard(t->n);
   const GridView g = kSrc == kRangeGrid ? t->grid : GridView{};
-  hipLaunchKernelGGL(spfh_kernel<kSrc>, grid, block, stack_bytes, st, g, tv, xv, Q, bound, O, guard);
-  hipLaunchKernelGGL(fpfh_kernel<kSrc>, grid, block, stack_bytes, st, g, tv, xv, Q, bound, (const uint4 *)O.rec, d_fpfh,
-                     guard);
+  hipLaunchKernelGGL((spfh_kernel<kSrc, false>), grid, block, stack_bytes, st, g, tv, xv, Q, bound, O, guard);
+  hipLaunchKernelGGL((fpfh_kernel<kSrc, false>), grid, block, stack_bytes, st, g, tv, xv, Q, bound, (const uint4 *)O.rec,
+                     FpfhAtOut{d_fpfh, nullptr, nullptr, nullptr}, guard);
 }
 
 // everything device resident; the SPFH records and the queries from ctx().arena
@@ -495,7 +331,7 @@ pcgx_status fpfh_enqueue(const pcgx_kdtree *t, const float *d_normals, float rad
   const TreeView tv = t->view();
   QuerySource Q;
   PCGX_TRY(query_source(t, src, nullptr, t->n, &Q, st));
-  SpfhOut O{d_normals, nullptr, d_counts, d_pairs};
+  SpfhOut O{d_normals, nullptr, d_counts, d_pairs, nullptr};
   PCGX_TRY(ctx().arena.alloc_n((size_t)t->n * (kFpfhRec / 4), &O.rec));
   const float bound = radius * radius;
   if (src == kRangeXWalk) fpfh_launch<kRangeXWalk>(t, tv, xv, Q, bound, O, d_fpfh, xwalk_stack_bytes(xv, kFpfhBlock), st);
@@ -528,10 +364,10 @@ void fpfh_at_launch(const pcgx_kdtree *t, const TreeView &tv, const XTreeView &x
   const int64_t guard = xwalk_guard(t->n);
   const GridView g = kSrc == kRangeGrid ? t->grid : GridView{};
   hipLaunchKernelGGL(fpfh_mark_kernel<kSrc>, slots, block, stack_bytes, st, g, tv, xv, S, bound, d_need, O, guard);
-  hipLaunchKernelGGL(spfh_need_kernel<kSrc>, points, block, stack_bytes, st, g, tv, xv, Q, bound, (const uint8_t *)d_need,
-                     d_normals, d_rec, guard);
-  hipLaunchKernelGGL(fpfh_at_kernel<kSrc>, slots, block, stack_bytes, st, g, tv, xv, S, bound, (const uint4 *)d_rec, O,
-                     guard);
+  hipLaunchKernelGGL((spfh_kernel<kSrc, true>), points, block, stack_bytes, st, g, tv, xv, Q, bound,
+                     SpfhOut{d_normals, d_rec, nullptr, nullptr, d_need}, guard);
+  hipLaunchKernelGGL((fpfh_kernel<kSrc, true>), slots, block, stack_bytes, st, g, tv, xv, S, bound, (const uint4 *)d_rec,
+                     O, guard);
 }
 
 // Len() > 0, cap > 0, everything device resident; the flags, the SPFH records and the tile counts from ctx().arena

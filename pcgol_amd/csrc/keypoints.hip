@@ -6,22 +6,19 @@
 // them out, on each of the three kinds of handle (grid, forced walk, patched tree after DeletePoint):
 //   eigenvalue stage (ISS)  normals_kernel itself (normals.hip): its moments and its Jacobi solve, the eigenvalues and the
 //                           saliency two more outputs of normals_finish.
-//   local_maxima_kernel     a fourth consumer of the shared enumeration (range_enum.h), one query per lane.  Per record
+//   local_maxima_kernel     a fourth consumer of the shared enumeration (radius_visit.h), one query per lane.  Per record
 //                           inside the bound: its score by id (4 bytes), and two bits -- "beaten" (keypoint_terms.h) and
 //                           "met myself" (a deleted id or a NaN coordinate never meets itself: no flags array needed).
 //                           A lane whose own score cannot qualify enumerates nothing.  One flag byte per id.
 //   compaction              the flags to ascending ids by bucket_grid.h's tile compaction (count, scan, write), then the
 //                           -1 tail.  The scan leaves the total in the caller's count word.
-// A fat row (kRangeFatRow) is the whole wave's work, as in normals_kernel: every lane takes every 64th record for the
-// owner's query, the two bits are combined over the wave by ballots, the owner merges them.
+// Of a fat row's shares the two bits are combined over the wave by ballots, and the owner merges them.
 #include <math.h>
 #include <stdlib.h>
 
 #include "bucket_grid.h"
 #include "keypoint_terms.h"
-#include "knn_grid.h"
-#include "knn_xwalk.h"
-#include "range_walk.h"
+#include "radius_visit.h"
 
 namespace pcgx {
 
@@ -50,9 +47,7 @@ __global__ __launch_bounds__(kKeyBlock) void local_maxima_kernel(GridView g, Tre
   extern __shared__ uint32_t s_stack[];
   const uint32_t n_tiles = (uint32_t)((Q.nq + kKeyBlock - 1) / kKeyBlock);
   const int64_t pos = (int64_t)xcd_tile(blockIdx.x, n_tiles) * kKeyBlock + threadIdx.x;
-  // (the grid path keeps every lane of the wave to the end: the fat rows are scanned by all 64)
   const bool live = pos < Q.nq;
-  if (kSrc != kRangeGrid && !live) return;
   int64_t i64 = 0;
   float qx = 0.0f, qy = 0.0f, qz = 0.0f, si = 0.0f;
   if (live) {
@@ -62,42 +57,22 @@ __global__ __launch_bounds__(kKeyBlock) void local_maxima_kernel(GridView g, Tre
   const int32_t i = (int32_t)i64;
   const bool cand = live && keypoint_candidate(si);  // nothing to enumerate for a score that cannot qualify
   MaxBits b{false, false};
-  auto take = [&](const float4 &p) {
-    if (ref_dist_sq(p.x, p.y, p.z, qx, qy, qz) < bound) b.take(score, p, si, i);  // kdtree.go:166,178
-  };
-  if constexpr (kSrc == kRangeGrid) {
-    const int lane = (int)(threadIdx.x & 63u);
-    grid_radius_scan(g, qx, qy, qz, bound, cand, take, [&](int owner, uint32_t rf, uint32_t re, float ox, float oy, float oz) {
-      const float osi = __shfl(si, owner);
-      const int32_t oi = __shfl(i, owner);
-      MaxBits part{false, false};
-      for (uint32_t r = rf + (uint32_t)lane; r < re; r += 64u) {
-        const float4 p = g.pts[r];
-        if (ref_dist_sq(p.x, p.y, p.z, ox, oy, oz) < bound) part.take(score, p, osi, oi);
-      }
-      const bool any_beaten = __ballot(part.beaten) != 0ull, any_met = __ballot(part.met) != 0ull;
-      if (lane == owner) {
-        b.beaten = b.beaten || any_beaten;
-        b.met = b.met || any_met;
-      }
-    });
-    if (!live) return;
-  } else {
-    if (cand) {
-      if constexpr (kSrc == kRangeWalk) {
-        range_walk_nodes<false>(tv, s_stack + threadIdx.x, kKeyBlock, qx, qy, qz, bound, [=]() { return bound; },
-                                [&](const float4 &nd, float) {  // (range_walk_nodes reports only DistSq < bound)
-                                  b.take(score, nd, si, i);
-                                });
-      } else {
-        auto hit = [&](const float4 &nd, float) {
-          take(nd);
-          return true;
-        };
-        xwalk(xv, s_stack + threadIdx.x, kKeyBlock, qx, qy, qz, guard, [&]() { return bound; }, hit, hit);
-      }
-    }
-  }
+  const int lane = (int)(threadIdx.x & 63u);
+  radius_visit<kSrc>(
+      RadiusViews{g, tv, xv, guard}, s_stack + threadIdx.x, kKeyBlock, qx, qy, qz, bound, cand,
+      [&](const float4 &p, float) { b.take(score, p, si, i); },
+      [&](int owner, float, float, float, auto rows) {  // the two bits, combined over the wave by ballots
+        const float osi = __shfl(si, owner);
+        const int32_t oi = __shfl(i, owner);
+        MaxBits part{false, false};
+        rows([&](const float4 &p, float) { part.take(score, p, osi, oi); });
+        const bool any_beaten = __ballot(part.beaten) != 0ull, any_met = __ballot(part.met) != 0ull;
+        if (lane == owner) {
+          b.beaten = b.beaten || any_beaten;
+          b.met = b.met || any_met;
+        }
+      });
+  if (!live) return;
   flag[i64] = (cand && b.met && !b.beaten) ? (uint8_t)1 : (uint8_t)0;
 }
 

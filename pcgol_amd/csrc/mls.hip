@@ -10,19 +10,16 @@
 //   pass 2 (order 2, count >= 6): N(q) is enumerated again for the 28 float64 sums of the Gauss-weighted normal
 //           equations of a quadratic height field over the plane; a 6 x 6 Cholesky in registers, and the query moves
 //           to the field's height at its own place (kind 2), with the field's normal.
-// Nothing is materialised; one query per lane, the three enumerations of range_enum.h (grid, walk, xwalk) as
-// normals_kernel takes them.  On the grid path a fat row is the whole wave's work in pass 2 as in pass 1: the other 63
-// lanes fetch the owner's frame, add their share of the row, and the partial sums are summed over the wave.  A lane
-// without a polynomial to fit (no query, kind 0, order 1's kind 1, fewer than 6 neighbours) scans nothing of its own in
-// pass 2 but stays for the wave's fat rows.  The order of every sum is fixed by the handle and the launch: the same
-// call gives the same bits.
+// Nothing is materialised; one query per lane, each pass one radius_visit (radius_visit.h) as normals_kernel's.  A fat
+// row is the whole wave's work in pass 2 as in pass 1: the other 63 lanes fetch the owner's frame, add their share of
+// the row, and the partial sums are summed over the wave.  A lane without a polynomial to fit (no query, kind 0, order
+// 1's kind 1, fewer than 6 neighbours) is not live in pass 2.  The order of every sum is fixed by the handle and the
+// launch: the same call gives the same bits.
 #include <math.h>
 #include <stdlib.h>
 
-#include "knn_grid.h"
-#include "knn_xwalk.h"
 #include "mls_terms.h"
-#include "range_walk.h"
+#include "radius_visit.h"
 
 namespace pcgx {
 
@@ -55,80 +52,45 @@ __global__ __launch_bounds__(kMlsBlock) void mls_kernel(GridView g, TreeView tv,
   extern __shared__ uint32_t s_stack[];
   const uint32_t n_tiles = (uint32_t)((Q.nq + kMlsBlock - 1) / kMlsBlock);
   const int64_t pos = (int64_t)xcd_tile(blockIdx.x, n_tiles) * kMlsBlock + threadIdx.x;
-  // (the grid path keeps every lane of the wave to the end: the fat rows of both passes are scanned and summed by all 64)
   const bool live = pos < Q.nq;
-  if (kSrc != kRangeGrid && !live) return;
   int64_t i = 0;
   float qx = 0.0f, qy = 0.0f, qz = 0.0f;
   if (live) read_query(Q, pos, i, qx, qy, qz);
   const int lane = (int)(threadIdx.x & 63u);
+  const RadiusViews V{g, tv, xv, guard};
 
   // pass 1: the moments, as normals_kernel sums them
   NormAcc acc;
   acc.clear();
-  {
-    auto take = [&](const float4 &p) {
-      if (ref_dist_sq(p.x, p.y, p.z, qx, qy, qz) < bound) acc.add(p.x, p.y, p.z, qx, qy, qz);  // kdtree.go:166,178
-    };
-    if constexpr (kSrc == kRangeGrid) {
-      grid_radius_scan(g, qx, qy, qz, bound, live, take, [&](int owner, uint32_t rf, uint32_t re, float ox, float oy, float oz) {
+  radius_visit<kSrc>(
+      V, s_stack + threadIdx.x, kMlsBlock, qx, qy, qz, bound, live,
+      [&](const float4 &p, float) { acc.add(p.x, p.y, p.z, qx, qy, qz); },
+      [&](int owner, float ox, float oy, float oz, auto rows) {
         NormAcc part;
         part.clear();
-        for (uint32_t r = rf + (uint32_t)lane; r < re; r += 64u) {
-          const float4 p = g.pts[r];
-          if (ref_dist_sq(p.x, p.y, p.z, ox, oy, oz) < bound) part.add(p.x, p.y, p.z, ox, oy, oz);
-        }
+        rows([&](const float4 &p, float) { part.add(p.x, p.y, p.z, ox, oy, oz); });
         part.wave_sum();
         if (lane == owner) acc.merge(part);
       });
-    } else if constexpr (kSrc == kRangeWalk) {
-      range_walk_nodes<false>(tv, s_stack + threadIdx.x, kMlsBlock, qx, qy, qz, bound, [=]() { return bound; },
-                              [&](const float4 &nd, float) {
-                                acc.add(nd.x, nd.y, nd.z, qx, qy, qz);  // (range_walk_nodes reports only DistSq < bound)
-                              });
-    } else {
-      auto hit = [&](const float4 &nd, float) {
-        take(nd);
-        return true;
-      };
-      xwalk(xv, s_stack + threadIdx.x, kMlsBlock, qx, qy, qz, guard, [&]() { return bound; }, hit, hit);
-    }
-  }
   MlsFrame F{};
   const bool framed = live && mls_frame(acc, O.min_nb, O.radius, O.sigma, F);
 
-  // pass 2: the normal equations of the lanes that fit a polynomial
+  // pass 2: the normal equations of the lanes that fit a polynomial (the others have nothing to enumerate)
   MlsAcc eq;
   eq.clear();
   const bool poly = kOrder == 2 && framed && acc.n >= kMlsBasis;
   if constexpr (kOrder == 2) {
-    auto take = [&](const float4 &p) {
-      if (ref_dist_sq(p.x, p.y, p.z, qx, qy, qz) < bound) eq.add(p.x, p.y, p.z, qx, qy, qz, F);
-    };
-    if constexpr (kSrc == kRangeGrid) {
-      // (a lane with nothing to fit passes live == false: it scans no row and owns no fat row, and shares in the others')
-      grid_radius_scan(g, qx, qy, qz, bound, poly, take, [&](int owner, uint32_t rf, uint32_t re, float ox, float oy, float oz) {
-        const MlsFrame G = mls_frame_of(F, owner);
-        MlsAcc part;
-        part.clear();
-        for (uint32_t r = rf + (uint32_t)lane; r < re; r += 64u) {
-          const float4 p = g.pts[r];
-          if (ref_dist_sq(p.x, p.y, p.z, ox, oy, oz) < bound) part.add(p.x, p.y, p.z, ox, oy, oz, G);
-        }
-        part.wave_sum();
-        if (lane == owner) eq.merge(part);
-      });
-    } else if constexpr (kSrc == kRangeWalk) {
-      if (poly)
-        range_walk_nodes<false>(tv, s_stack + threadIdx.x, kMlsBlock, qx, qy, qz, bound, [=]() { return bound; },
-                                [&](const float4 &nd, float) { eq.add(nd.x, nd.y, nd.z, qx, qy, qz, F); });
-    } else {
-      auto hit = [&](const float4 &nd, float) {
-        take(nd);
-        return true;
-      };
-      if (poly) xwalk(xv, s_stack + threadIdx.x, kMlsBlock, qx, qy, qz, guard, [&]() { return bound; }, hit, hit);
-    }
+    radius_visit<kSrc>(
+        V, s_stack + threadIdx.x, kMlsBlock, qx, qy, qz, bound, poly,
+        [&](const float4 &p, float) { eq.add(p.x, p.y, p.z, qx, qy, qz, F); },
+        [&](int owner, float ox, float oy, float oz, auto rows) {
+          const MlsFrame G = mls_frame_of(F, owner);
+          MlsAcc part;
+          part.clear();
+          rows([&](const float4 &p, float) { part.add(p.x, p.y, p.z, ox, oy, oz, G); });
+          part.wave_sum();
+          if (lane == owner) eq.merge(part);
+        });
   }
   if (!live) return;
   const MlsResult R = mls_finish(framed, F, poly, eq, O.radius, qx, qy, qz, O.vx, O.vy, O.vz);

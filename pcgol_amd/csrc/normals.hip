@@ -13,10 +13,8 @@
 // Nothing is materialised: each lane enumerates its query's neighbours exactly as the range kernels do and keeps
 // count, sum d (3), the upper triangle of sum d d^T (6) and the box of the neighbours (6 floats: "all coincide" is
 // exact, whatever the summation rounds) in registers, then solves the 3 x 3 eigenproblem in the same kernel by
-// cyclic Jacobi in double.  Three ways to enumerate, as pcgx_kdtree_range_count takes them (range_source, range_enum.h):
-//   grid  (kRangeGrid): grid_radius_scan over the cells grid_cover names, fat rows scanned by the whole wave;
-//   walk  (kRangeWalk: no grid, PCGX_RANGE_WALK=1): range_walk_nodes over the implicit tree;
-//   xwalk (kRangeXWalk: a handle that has seen DeletePoint): the patched tree's walk of knn_xwalk.h.
+// cyclic Jacobi in double.  The enumeration is radius_visit (radius_visit.h) over the source pcgx_kdtree_range_count
+// takes on that handle (range_source, range_enum.h): the grid, the implicit tree's walk, the patched tree's walk.
 // Queries: the caller's, or the tree's own points (q == NULL), as query_source (range_enum.h) lays them out.
 // ISS keypoints (keypoints.hip, pcgx_kdtree_iss_keypoints) take their eigenvalues from this kernel: the same moments and
 // the same solve, the eigenvalues scaled back by the trace and rounded to float32, and the saliency decided on them
@@ -26,9 +24,7 @@
 
 #include "cov3.h"
 #include "keypoint_terms.h"
-#include "knn_grid.h"
-#include "knn_xwalk.h"
-#include "range_walk.h"
+#include "radius_visit.h"
 
 namespace pcgx {
 
@@ -94,44 +90,24 @@ __global__ __launch_bounds__(kNormBlock) void normals_kernel(GridView g, TreeVie
   extern __shared__ uint32_t s_stack[];
   const uint32_t n_tiles = (uint32_t)((Q.nq + kNormBlock - 1) / kNormBlock);
   const int64_t pos = (int64_t)xcd_tile(blockIdx.x, n_tiles) * kNormBlock + threadIdx.x;
-  // (the grid path keeps every lane of the wave to the end: the fat rows are scanned and summed by all 64)
   const bool live = pos < Q.nq;
-  if (kSrc != kRangeGrid && !live) return;
   int64_t i = 0;
   float qx = 0.0f, qy = 0.0f, qz = 0.0f;
   if (live) read_query(Q, pos, i, qx, qy, qz);
+  const int lane = (int)(threadIdx.x & 63u);
   NormAcc acc;
   acc.clear();
-  auto take = [&](const float4 &p) {
-    if (ref_dist_sq(p.x, p.y, p.z, qx, qy, qz) < bound) acc.add(p.x, p.y, p.z, qx, qy, qz);  // kdtree.go:166,178
-  };
-  if constexpr (kSrc == kRangeGrid) {
-    // a fat row (one site of the cloud taken thousands of times) is the whole wave's work: every lane takes every 64th
-    // record of the owner's row, the partial moments are summed over the wave
-    const int lane = (int)(threadIdx.x & 63u);
-    grid_radius_scan(g, qx, qy, qz, bound, live, take, [&](int owner, uint32_t rf, uint32_t re, float ox, float oy, float oz) {
-      NormAcc part;
-      part.clear();
-      for (uint32_t r = rf + (uint32_t)lane; r < re; r += 64u) {
-        const float4 p = g.pts[r];
-        if (ref_dist_sq(p.x, p.y, p.z, ox, oy, oz) < bound) part.add(p.x, p.y, p.z, ox, oy, oz);
-      }
-      part.wave_sum();
-      if (lane == owner) acc.merge(part);
-    });
-    if (!live) return;
-  } else if constexpr (kSrc == kRangeWalk) {
-    range_walk_nodes<false>(tv, s_stack + threadIdx.x, kNormBlock, qx, qy, qz, bound, [=]() { return bound; },
-                            [&](const float4 &nd, float) {
-                              acc.add(nd.x, nd.y, nd.z, qx, qy, qz);  // (range_walk_nodes reports only DistSq < bound)
-                            });
-  } else {
-    auto hit = [&](const float4 &nd, float) {
-      take(nd);
-      return true;
-    };
-    xwalk(xv, s_stack + threadIdx.x, kNormBlock, qx, qy, qz, guard, [&]() { return bound; }, hit, hit);
-  }
+  radius_visit<kSrc>(
+      RadiusViews{g, tv, xv, guard}, s_stack + threadIdx.x, kNormBlock, qx, qy, qz, bound, live,
+      [&](const float4 &p, float) { acc.add(p.x, p.y, p.z, qx, qy, qz); },
+      [&](int owner, float ox, float oy, float oz, auto rows) {  // the partial moments, summed over the wave
+        NormAcc part;
+        part.clear();
+        rows([&](const float4 &p, float) { part.add(p.x, p.y, p.z, ox, oy, oz); });
+        part.wave_sum();
+        if (lane == owner) acc.merge(part);
+      });
+  if (!live) return;
   normals_finish(acc, qx, qy, qz, O, i);
 }
 

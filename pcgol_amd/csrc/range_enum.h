@@ -5,7 +5,8 @@
 // set pcgx_kdtree_range_count counts.  So what decides it is stated here once: the reference's float32 DistSq, which
 // source a handle's Range takes (range_source), the scan of the grid's rows with the wave-shared fat rows (grid_row,
 // RowScan, grid_radius_scan), and where a kernel's queries come from (QuerySource, query_source).  The walks
-// themselves are range_walk.h (implicit tree) and knn_xwalk.h (patched tree).
+// themselves are range_walk.h (implicit tree) and knn_xwalk.h (patched tree); radius_visit.h puts the three behind
+// one visitor for the kernels that only consume the set (normals, MLS, keypoints, FPFH).
 #pragma once
 #include <stdlib.h>
 

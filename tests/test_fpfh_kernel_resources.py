@@ -9,8 +9,8 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 import kernel_resources as KR  # noqa: E402
 
-FPFH_KERNELS = ["spfh_kernelILi0E", "spfh_kernelILi1E", "spfh_kernelILi2E",
-                "fpfh_kernelILi0E", "fpfh_kernelILi1E", "fpfh_kernelILi2E"]
+FPFH_KERNELS = ["spfh_kernelILi0ELb0E", "spfh_kernelILi1ELb0E", "spfh_kernelILi2ELb0E",
+                "fpfh_kernelILi0ELb0E", "fpfh_kernelILi1ELb0E", "fpfh_kernelILi2ELb0E"]
 
 
 def test_fpfh_kernels_use_no_scratch():

@@ -9,8 +9,11 @@ and may move.  What moves with that order is normalised away: the function index
 .Lfunc_end<i>, the comments' BB<i>_<n>), the padding behind whichever function is emitted last, and the
 __hip_cuid_<hash> symbol, which differs between two compiles of one source.
 
-    python tools/compare_device_code.py [--rev HEAD] [--jobs 8] [file.hip ...]
+    python tools/compare_device_code.py [--rev HEAD] [--jobs 8] [--rename OLD=NEW ...] [file.hip ...]
 
+A function that differs is listed with its instruction lines, REV's -> the tree's.  --rename: a kernel whose name
+changed between the two (substrings of the mangled names) is compared with its predecessor instead of being listed
+twice, once as missing and once as new.
 Needs hipcc, no GPU.  Exit status 0: every function of every file is textually identical."""
 import argparse
 import concurrent.futures
@@ -77,12 +80,34 @@ def split(asm):
     return {k: "\n".join(v) for k, v in out.items()}
 
 
-def compare(src, here, there):
+def instructions(text):
+    """the instruction lines of a function's text: neither directives, labels nor comments"""
+    lines = (ln.strip() for ln in text.splitlines())
+    return sum(1 for ln in lines if ln and ln[0] not in ".;" and not ln.split(";")[0].strip().endswith(":"))
+
+
+def rename(a, b, renames):
+    """A kernel of the other commit that has another name here is compared under its name here: OLD and NEW are
+    substrings of the mangled names, each naming one function of its side; the other side's symbol is rewritten."""
+    for old, new in renames:
+        olds = [k[3:] for k in b if k.startswith("fn ") and old in k]
+        news = [k[3:] for k in a if k.startswith("fn ") and new in k]
+        if len(olds) != 1 or len(news) != 1:
+            continue  # (another file's kernel)
+        b = {k.replace(olds[0], news[0]): v.replace(olds[0], news[0]) for k, v in b.items()}
+    return b
+
+
+def compare(src, here, there, renames=()):
     if not os.path.exists(os.path.join(there, "pcgol_amd", "csrc", src)):  # a file the other commit does not have
         a = split(device_asm(here, src))
         return src, sum(k.startswith("fn ") for k in a), sum(k.startswith("meta ") for k in a), None
     a, b = split(device_asm(here, src)), split(device_asm(there, src))
+    b = rename(a, b, renames)
     differing = sorted(k for k in set(a) | set(b) if a.get(k) != b.get(k))
+    # (a function that differs: its instruction lines there -> here; "-" where one side does not have it)
+    differing = [k + ("   instructions %s -> %s" % tuple(instructions(m[k]) if k in m else "-" for m in (b, a))
+                      if k.startswith("fn ") else "") for k in differing]
     return src, sum(k.startswith("fn ") for k in a), sum(k.startswith("meta ") for k in a), differing
 
 
@@ -90,15 +115,18 @@ def main():
     ap = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     ap.add_argument("--rev", default="HEAD", help="the commit to compare the working tree with (default HEAD)")
     ap.add_argument("--jobs", type=int, default=min(8, os.cpu_count() or 1))
+    ap.add_argument("--rename", action="append", default=[], metavar="OLD=NEW",
+                    help="compare REV's function whose mangled name contains OLD with the tree's that contains NEW")
     ap.add_argument("sources", nargs="*", help="files of pcgol_amd/csrc (default: all of build.SOURCES)")
     args = ap.parse_args()
+    renames = [tuple(r.split("=", 1)) for r in args.rename]
     sources = args.sources or B.SOURCES
     with tempfile.TemporaryDirectory() as there:
         tar = subprocess.run(["git", "-C", ROOT, "archive", args.rev, "pcgol_amd", "include"], check=True,
                              stdout=subprocess.PIPE).stdout
         tarfile.open(fileobj=io.BytesIO(tar)).extractall(there)
         with concurrent.futures.ThreadPoolExecutor(args.jobs) as pool:
-            results = list(pool.map(lambda s: compare(s, ROOT, there), sources))
+            results = list(pool.map(lambda s: compare(s, ROOT, there, renames), sources))
     n_fn = n_kernels = n_diff = 0
     for src, fns, kernels, differing in results:
         if differing is None:  # (nothing to compare with: every existing function is in the other files)

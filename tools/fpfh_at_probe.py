@@ -1,5 +1,5 @@
-"""GPU probe: FPFH at the keypoints only (pcgx_kdtree_fpfh_at_dev; csrc/fpfh.hip: fpfh_mark_kernel, spfh_need_kernel,
-fpfh_at_kernel) against the path it replaces, FPFHDev over every point plus a torch gather of the keypoints' rows, and
+"""GPU probe: FPFH at the keypoints only (pcgx_kdtree_fpfh_at_dev; csrc/fpfh.hip: fpfh_mark_kernel, spfh_kernel<., true>,
+fpfh_kernel<., true>) against the path it replaces, FPFHDev over every point plus a torch gather of the keypoints' rows, and
 the coarse-alignment chain both ways.
 
     python tools/fpfh_at_probe.py [--out profiles/fpfh_at_probe.json] [--reps 21]
@@ -28,7 +28,9 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-KERNELS = ("spfh_kernel", "fpfh_kernel", "fpfh_mark_kernel", "spfh_need_kernel", "fpfh_at_kernel", "fpfh_need_")
+# (spfh_kernel<k, true> and fpfh_kernel<k, true> are the stages over the needed points and the slots: the trace names
+# the template arguments, so the two forms of each kernel stay apart)
+KERNELS = ("spfh_kernel", "fpfh_kernel", "fpfh_mark_kernel", "fpfh_need_")
 CASES = {"a": ("iss_0.1_0.1", 0.1, 0.1), "b": ("iss_0.1_0.3", 0.1, 0.3)}
 R = 0.1
 
