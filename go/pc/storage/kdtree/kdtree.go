@@ -22,7 +22,8 @@ import (
 // at chosen ids only), and the keypoint detectors LocalMaxima(radius, score) and ISSKeypoints(salientRadius,
 // nonMaxRadius, gamma21, gamma32, minNeighbors) (include/pcgx.h, "keypoints"), and cluster extraction,
 // Clusters(radius, pcgx.ClusterParams{...}) (include/pcgx.h, "clusters"), with the geometry of its groups,
-// GroupStats(ids, sizes) (include/pcgx.h, "group geometry").
+// GroupStats(ids, sizes) (include/pcgx.h, "group geometry"), and what they stand on, GroupHulls(ids, sizes)
+// (include/pcgx.h, "group footprints").
 type KDTree = pcgx.KDTree
 
 // KDTreeOption is kdtree.KDTreeOption (kdtree.go:31).

@@ -626,6 +626,49 @@ func (k *KDTree) GroupStats(ids, sizes []int64) (*GroupGeometry, error) {
 	return r, nil
 }
 
+// GroupFootprints is the result of (*KDTree).GroupHulls: HullSizes per group; HullIDs, again a grouped id list (the
+// vertices of group g's exact 2-D convex hull counter-clockwise from the lexicographically least place, a place by its
+// smallest id, -1 behind the last hull); Area of each polygon; Rect: the minimum-area rectangle with a side along a hull
+// edge as centre x, y, the unit direction u of that edge, and the half-extents along u and (-u_y, u_x).
+type GroupFootprints struct {
+	HullSizes []int64
+	HullIDs   []int64
+	Area      []float64
+	Rect      [][6]float64
+}
+
+// GroupHulls returns what every group of a grouped id list stands on (extension: no reference parity; include/pcgx.h,
+// pcgx_kdtree_group_hulls); ids and sizes as GroupStats takes them, and the same inputs are ErrInvalid.
+func (k *KDTree) GroupHulls(ids, sizes []int64) (*GroupFootprints, error) {
+	runtime.LockOSThread() // the error text is thread-local on the C side: call and pcgx_last_error on one OS thread
+	defer runtime.UnlockOSThread()
+	defer runtime.KeepAlive(k) // the finalizer must not free the handle while a call is in flight
+	g := len(sizes)
+	r := &GroupFootprints{HullSizes: make([]int64, g), HullIDs: make([]int64, len(ids)), Area: make([]float64, g),
+		Rect: make([][6]float64, g)}
+	for i := range r.HullIDs {
+		r.HullIDs[i] = -1
+	}
+	if g == 0 {
+		return r, nil
+	}
+	var pi, ph *C.int64_t
+	if len(ids) > 0 {
+		pi = (*C.int64_t)(unsafe.Pointer(&ids[0]))
+		ph = (*C.int64_t)(unsafe.Pointer(&r.HullIDs[0]))
+	}
+	rc := C.pcgx_kdtree_group_hulls(k.t.h, pi, C.int64_t(len(ids)), (*C.int64_t)(unsafe.Pointer(&sizes[0])), C.int64_t(g),
+		(*C.int64_t)(unsafe.Pointer(&r.HullSizes[0])), ph, (*C.double)(unsafe.Pointer(&r.Area[0])),
+		(*C.double)(unsafe.Pointer(&r.Rect[0])))
+	runtime.KeepAlive(ids)
+	runtime.KeepAlive(sizes)
+	runtime.KeepAlive(r)
+	if err := status(rc); err != nil {
+		return nil, err
+	}
+	return r, nil
+}
+
 // FPFHMatch finds, for every row of a, the nearest usable row of b and the runner-up's distance (extension: no
 // reference parity; include/pcgx.h, "FPFH matching"): float32 squared distances over the 33 values, summed left to
 // right, ties to the smaller id.  ids[i] is -1 and both distances are +Inf where a's row is unusable (not finite, or

@@ -1106,6 +1106,71 @@ PCGX_API pcgx_status pcgx_kdtree_group_stats_dev(const pcgx_kdtree *t, const int
  * workgroup (the boundaries the tests put groups across). */
 PCGX_API int32_t pcgx_group_stats_tile(void);
 
+/* ------------------------------------------- group footprints (extension: no reference parity)
+ * NOT in the reference.  What a tracker or planner takes from a cluster of an upright scene: per group of a grouped id
+ * list, the polygon the group stands on -- the exact convex hull of its members' (x, y) -- that polygon's area, and the
+ * smallest upright rectangle with a side along one of its edges (a car seen from one corner is an L of points: the
+ * principal-axes box of "group geometry" runs along the L's diagonal, this one along the car).  This comment is the
+ * contract, tests/hull_oracle.py restates it.
+ *   pcgx_kdtree_group_hulls    (t, ids[n_ids] i64, n_ids, sizes[n_groups] i64, n_groups,
+ *                               hull_sizes[n_groups] i64, hull_ids[n_ids] i64, area[n_groups] f64, rect[6 n_groups] f64)
+ *   pcgx_kdtree_group_hulls_dev(t, d_ids[cap_ids] i32, cap_ids, d_sizes[cap_groups] i32, cap_groups, d_n_groups,
+ *                               d_hull_sizes[cap_groups] i32, d_hull_ids[cap_ids] i32, d_area, d_rect, stream)
+ * Inputs: the groups, the clip at cap_ids, the live-member test, G, the error codes and what the host form rejects are
+ *   those of pcgx_kdtree_group_stats[_dev] above, word for word (the same checks, the same messages under these names).
+ *   cap_groups = 0 is PCGX_OK.  A tree of no points gives all-zero rows and an all -1 hull_ids.  Every output may be
+ *   NULL, and a NULL output changes no bit of the others.
+ * Footprint: the set of (x, y) of the group's live members, as stored, z dropped (other up-axes are out of scope).
+ *   Two members are at the same place when both coordinates compare ==, so -0 equals +0.  A place is represented by the
+ *   smallest id among the group's live members at it.
+ * Vertices: a place is a vertex exactly when it is a strict extreme point of the convex hull of the group's places, in
+ *   exact real arithmetic on the float32 values.  A place on the boundary between two others is not a vertex.  A group
+ *   with one place has 1 vertex; a group whose places all lie on one line has 2, its lexicographically least and greatest
+ *   (x, then y); a group without a live member has 0.
+ *   hull_sizes[g]   h_g, the number of vertices of group g (int32 on the device, int64 on the host); 0 for rows >= G.
+ *   hull_ids        again a grouped id list: group g's vertices stand at [H_g, H_g + h_g), H_g the sum of the earlier
+ *                   hull_sizes, counter-clockwise, starting at the lexicographically least place; everything from the
+ *                   total to the capacity (cap_ids, n_ids) is -1.  (hull_ids, hull_sizes) can go straight into
+ *                   pcgx_kdtree_group_stats or back into this call, which returns them unchanged.
+ *   area[g]         float64: half the sum over k = 1 .. h - 2 of cross(v_k - v_0, v_{k+1} - v_0), the differences in
+ *                   float64, each term (a - v0)_x (b - v0)_y - (a - v0)_y (b - v0)_x (csrc/hull_terms.h), the terms added
+ *                   in that order; 0 for h < 3.  Within 2 h 2^-53 D^2 of the exact area, D the diagonal of the group's
+ *                   xy box (each term: two products and a difference of values bounded by D^2; h - 3 additions of
+ *                   partial sums bounded by D^2), the differences taken to be exact as in "group geometry".
+ *   rect[6 g ..]    float64: the minimum-area enclosing rectangle with one side along a hull edge: the centre x, y; the
+ *                   unit direction u of that edge; the half-extents along u and along n = (-u_y, u_x).  For every edge k
+ *                   in order (from v_k to v_{k+1}, the last one back to v_0): u = (v_{k+1} - v_k) / |v_{k+1} - v_k| in
+ *                   float64, the least and greatest of s = (p - v_k) . u and t = (p - v_k) . n over all h vertices p, and
+ *                   the product of the two widths; the first edge with the smallest product wins.  centre = v_k +
+ *                   ((s+ + s-) / 2) u + ((t+ + t-) / 2) n, half-extents (s+ - s-) / 2 and (t+ - t-) / 2.
+ *                   h = 2: u along the segment from vertex 0 to vertex 1, second half-extent 0.  h = 1: the centre at the
+ *                   point, u = (1, 0), half-extents 0.  h = 0: zeros.  The rectangle's area is within 32 2^-53 D^2 of
+ *                   the exact minimum over the edges (u: four roundings; a projection: three more; a width within
+ *                   13 2^-53 D; the product of two widths bounded by D).
+ * PCGX_E_INVALID: as pcgx_kdtree_group_stats[_dev].
+ * Determinism: the same input gives the same bits on every call.  No floating-point atomic feeds a result; the extremes
+ *   are combined with integer atomics on order-preserving keys, every other order is fixed by the input.
+ * Always computed on the device (csrc/group_hull.hip), nothing read back in the device form, which returns without
+ *   waiting.  A member is dropped from consideration only on exact evidence that it is no vertex: the sign of an
+ *   orientation determinant against real input points, from a float64 evaluation under a static error bound and, where
+ *   that does not certify it, from the exact sum of the six products (csrc/hull_terms.h).  Cost: two gathers of 16 B per
+ *   slot, four stable radix sorts of 32-bit pairs over cap_ids (id, y, x, group), 53 B of temporaries per slot and 80 B
+ *   per group; a group whose members are nearly all vertices is chained by one lane. */
+PCGX_API pcgx_status pcgx_kdtree_group_hulls(const pcgx_kdtree *t, const int64_t *ids /* [n_ids] */, int64_t n_ids,
+                                             const int64_t *sizes /* [n_groups] */, int64_t n_groups,
+                                             int64_t *hull_sizes /* [n_groups] */, int64_t *hull_ids /* [n_ids] */,
+                                             double *area /* [n_groups] */, double *rect /* [6 n_groups] */);
+/* Same, every array device resident (ids and sizes are int32 there), enqueued on `stream` (NULL: the library's);
+ * returns without waiting, reads nothing back. */
+PCGX_API pcgx_status pcgx_kdtree_group_hulls_dev(const pcgx_kdtree *t, const int32_t *d_ids /* [cap_ids] */,
+                                                 int64_t cap_ids, const int32_t *d_sizes /* [cap_groups] */,
+                                                 int64_t cap_groups, const int32_t *d_n_groups /* may be NULL */,
+                                                 int32_t *d_hull_sizes /* [cap_groups] */,
+                                                 int32_t *d_hull_ids /* [cap_ids] */, double *d_area, double *d_rect,
+                                                 void *stream);
+/* Survivors a lane of the hull's reduce rounds takes at a time (a boundary the tests put hulls across). */
+PCGX_API int32_t pcgx_group_hulls_chunk(void);
+
 /* ------------------------------------------- pose from correspondences (extension: no reference parity)
  * NOT in the reference.  The rigid motion (a proper rotation and a translation, no scale) that most pairs of a
  * correspondence list agree on, by sample consensus: the starting pose every Fit here needs, from what

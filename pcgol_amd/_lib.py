@@ -269,6 +269,9 @@ SIGNATURES = {
     "pcgx_kdtree_group_stats": (_i32, [_vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "pcgx_kdtree_group_stats_dev": (_i32, [_vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "pcgx_group_stats_tile": (_i32, []),
+    "pcgx_kdtree_group_hulls": (_i32, [_vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp]),
+    "pcgx_kdtree_group_hulls_dev": (_i32, [_vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "pcgx_group_hulls_chunk": (_i32, []),
     "pcgx_kdtree_iss_keypoints": (_i32, [_vp, _f32, _f32, _f32, _f32, _i32, _vp, _vp, _vp, C.POINTER(_i64)]),
     "pcgx_kdtree_iss_keypoints_dev": (_i32, [_vp, _f32, _f32, _f32, _f32, _i32, _vp, _vp, _vp, _vp, _vp]),
     "pcgx_pose_from_correspondences": (_i32, [_vp, _i64, _vp, _i64, _vp, _vp, _i64, _vp, _i64, _f32, _f32, _i32,

@@ -27,56 +27,12 @@
 #include <math.h>
 #include <stdlib.h>
 
-#include "group_terms.h"
-#include "range_walk.h"
+#include "group_list.h"
 
 namespace pcgx {
 
-constexpr int kGsBlock = 256, kGsRow = 64, kGsRowsPerWave = 4;
-constexpr int kGsTile = kGsBlock * kGsRowsPerWave;  // slots (and, in the scan, groups) per workgroup
-constexpr int kGsGatherRows = 16;                   // rows a wave of the gathers takes one after the other (four tiles a workgroup)
-constexpr int kGsGatherTile = kGsBlock / 64 * kGsGatherRows * kGsRow;
 constexpr int kGsLaneRows = 4;                      // a group of up to this many rows is summed by its own lane
 constexpr int kGsRec = 10;                          // doubles per record: nine sums and the count
-static_assert(kGsTile % kGsRow == 0 && kGsRow == 64, "a row is a wave");
-static_assert(kGsGatherTile % kGsTile == 0, "the map is made in whole tiles");
-
-// G = clamp(*d_n, 0, cap) read on the device; d_n == nullptr: cap
-__device__ __forceinline__ int32_t gs_groups(const int32_t *__restrict__ d_n, const int32_t cap) {
-  if (!d_n) return cap;
-  const int32_t v = *d_n;
-  return v < 0 ? 0 : (v > cap ? cap : v);
-}
-
-// the clamped size of entry g of the scan: [0, cap_ids] for a group below G, 0 from G on (entry cap_groups included)
-__device__ __forceinline__ uint64_t gs_size_at(const int32_t *__restrict__ sizes, const int64_t g, const int32_t G,
-                                               const int32_t cap_ids) {
-  if (g >= (int64_t)G) return 0ull;
-  const int32_t s = sizes[g];
-  return (uint64_t)(s < 0 ? 0 : (s > cap_ids ? cap_ids : s));
-}
-
-// exclusive prefix of t over the 256 lanes of the workgroup; total: the workgroup's sum.  All lanes call it.
-__device__ __forceinline__ uint64_t gs_block_excl_scan(const uint64_t t, uint64_t *s_w, uint64_t &total) {
-  const int lane = (int)(threadIdx.x & 63u), wave = (int)(threadIdx.x >> 6);
-  unsigned long long inc = t;
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const unsigned long long v = __shfl_up(inc, o);
-    if (lane >= o) inc += v;
-  }
-  if (lane == 63) s_w[wave] = inc;
-  __syncthreads();
-  uint64_t base = 0ull;
-  total = 0ull;
-#pragma unroll
-  for (int w = 0; w < kGsBlock / 64; w++) {
-    if (w < wave) base += s_w[w];
-    total += s_w[w];
-  }
-  __syncthreads();  // (s_w may be written again)
-  return base + inc - t;
-}
 
 // ------------------------------------------------------------------ offsets
 // entries: cap_groups + 1 (the last one is the total's place), kGsTile to a workgroup, four consecutive ones to a lane
@@ -207,109 +163,7 @@ __global__ __launch_bounds__(kGsBlock) void gs_map_kernel(const int32_t *__restr
   *reinterpret_cast<int4 *>(grp + lo + 4 * (int64_t)threadIdx.x) = out;
 }
 
-// ------------------------------------------------------------------ the gathers
-struct GroupList {
-  const float4 *nodes;    // the handle's tree, BFS slots
-  const uint32_t *inv;    // [n] id -> BFS slot
-  int64_t n;              // Len()
-  const int32_t *ids;     // [cap_ids]
-  const int32_t *grp;     // [whole tiles] slot -> group, -1 behind the list
-};
-
-// the slot of this lane in row `row`: its group (or -1) and, for a live member, its coordinates
-__device__ __forceinline__ bool gs_member(const GroupList &L, const int64_t slot, int32_t &g, float &x, float &y, float &z) {
-  g = L.grp[slot];
-  x = y = z = 0.0f;
-  if (g < 0) return false;
-  const int64_t id = (int64_t)L.ids[slot];  // (g >= 0: the slot is below the list's clipped end, so below cap_ids)
-  if (!group_id_ok(id, L.n)) return false;
-  const float4 nd = node_at(L.nodes, L.inv[id]);
-  x = nd.x;
-  y = nd.y;
-  z = nd.z;
-  return group_point_ok(x, y, z);
-}
-
-// is this lane the first of its run (the maximal stretch of one group inside the wave's row)?  All 64 lanes call it.
-__device__ __forceinline__ bool gs_run_head(const int32_t g, const int lane) {
-  const int32_t prev = __shfl_up(g, 1);
-  return lane == 0 || prev != g;
-}
-// does lane + o belong to this lane's run?  (groups never decrease along a row: the same group means the same run)
-__device__ __forceinline__ bool gs_same_run(const int32_t g, const int lane, const int o) {
-  const int32_t og = __shfl_down(g, o);
-  return lane + o < 64 && og == g;
-}
-
-// A wave's carry: rows that belong to one group from end to end are combined in registers (every lane holds the same
-// values) and reach memory once when the group changes or the wave is done -- the waves of one large group would
-// otherwise send an atomic per row to one address, and same-address atomics are served one after the other
-// (cluster.hip, cl_root_stats_kernel: 150k of them took 2 ms).
-template <class K>
-struct GroupCarry {
-  int32_t g;
-  K lo[3], hi[3];
-  __device__ __forceinline__ void flush(K *__restrict__ keys, const int lane, const K none) {
-    if (g >= 0 && lane == 0 && lo[0] != none) {
-#pragma unroll
-      for (int c = 0; c < 3; c++) {
-        atomicMin(keys + 6 * (size_t)g + c, lo[c]);
-        atomicMax(keys + 6 * (size_t)g + 3 + c, hi[c]);
-      }
-    }
-    g = -1;
-  }
-};
-
-// One row's keys (lo / hi of this lane's member, the neutral keys for a dead slot) reduced over the runs of the row and
-// combined into keys[6 g ..]: a row of one group goes into the carry, the runs of any other row straight to memory.
-// All 64 lanes call it.
-template <class K>
-__device__ __forceinline__ void gs_combine_row(const int32_t g, K (&lo)[3], K (&hi)[3], const int lane, GroupCarry<K> &carry,
-                                               K *__restrict__ keys, const K none) {
-#pragma unroll
-  for (int o = 1; o < 64; o <<= 1) {
-    const bool same = gs_same_run(g, lane, o);
-#pragma unroll
-    for (int c = 0; c < 3; c++) {
-      const K a = __shfl_down(lo[c], o), b = __shfl_down(hi[c], o);
-      if (same) {
-        lo[c] = a < lo[c] ? a : lo[c];
-        hi[c] = b > hi[c] ? b : hi[c];
-      }
-    }
-  }
-  const int32_t g0 = __shfl(g, 0);
-  if (__ballot(g != g0) == 0ull) {  // uniform: one group from end to end (g0 >= 0: the row is not behind the list), lane 0 has its keys
-    if (carry.g != g0) {
-      carry.flush(keys, lane, none);
-      carry.g = g0;
-#pragma unroll
-      for (int c = 0; c < 3; c++) {
-        carry.lo[c] = __shfl(lo[c], 0);
-        carry.hi[c] = __shfl(hi[c], 0);
-      }
-    } else {
-#pragma unroll
-      for (int c = 0; c < 3; c++) {
-        const K a = __shfl(lo[c], 0), b = __shfl(hi[c], 0);
-        carry.lo[c] = a < carry.lo[c] ? a : carry.lo[c];
-        carry.hi[c] = b > carry.hi[c] ? b : carry.hi[c];
-      }
-    }
-    return;
-  }
-  carry.flush(keys, lane, none);
-  const bool head = gs_run_head(g, lane);
-  if (head && g >= 0 && lo[0] != none) {  // (no value's key is all ones: the run has a live member)
-#pragma unroll
-    for (int c = 0; c < 3; c++) {
-      atomicMin(keys + 6 * (size_t)g + c, lo[c]);
-      atomicMax(keys + 6 * (size_t)g + 3 + c, hi[c]);
-    }
-  }
-}
-
+// ------------------------------------------------------------------ the gathers (GroupList, the runs, the carry: group_list.h)
 __global__ __launch_bounds__(kGsBlock) void gs_box_kernel(GroupList L, uint32_t *__restrict__ box) {
   const int lane = (int)(threadIdx.x & 63u), wave = (int)(threadIdx.x >> 6);
   GroupCarry<uint32_t> carry;
@@ -532,6 +386,18 @@ __global__ __launch_bounds__(kGsBlock) void gs_obb_kernel(int32_t cap_groups, co
 }
 
 // ------------------------------------------------------------------ the call
+void group_scan_launch(const int32_t *d_sizes, const int32_t *d_n_groups, int32_t cap_groups, int32_t cap_ids,
+                       uint64_t *tile_sum, unsigned scan_tiles, hipStream_t st) {
+  hipLaunchKernelGGL(gs_tile_sum_kernel, dim3(scan_tiles), dim3(kGsBlock), 0, st, d_sizes, d_n_groups, cap_groups, cap_ids,
+                     tile_sum);
+  hipLaunchKernelGGL(gs_tile_scan_kernel, dim3(1), dim3(kGsBlock), 0, st, tile_sum, (int32_t)scan_tiles);
+}
+
+void group_map_launch(const int32_t *off, const int32_t *d_n_groups, int32_t cap_groups, int32_t *grp, unsigned slot_tiles,
+                      hipStream_t st) {
+  hipLaunchKernelGGL(gs_map_kernel, dim3(slot_tiles), dim3(kGsBlock), 0, st, off, d_n_groups, cap_groups, grp);
+}
+
 static pcgx_status gs_zero_outputs(const GroupOut &O, int64_t cap_groups, hipStream_t st) {
   const size_t c = (size_t)cap_groups;
   if (O.count) PCGX_HIP_TRY(hipMemsetAsync(O.count, 0, c * 4, st));
@@ -571,13 +437,12 @@ static pcgx_status group_stats_enqueue(const pcgx_kdtree *t, const int32_t *d_id
   PCGX_TRY(ar.alloc_n((size_t)(rows + cap_groups) * kGsRec, &rec));
   PCGX_TRY(ar.alloc_n((size_t)cap_groups * 12, &frame));
   const int32_t cg = (int32_t)cap_groups, ci = (int32_t)cap_ids;
-  hipLaunchKernelGGL(gs_tile_sum_kernel, dim3(scan_tiles), dim3(kGsBlock), 0, st, d_sizes, d_n_groups, cg, ci, tile_sum);
-  hipLaunchKernelGGL(gs_tile_scan_kernel, dim3(1), dim3(kGsBlock), 0, st, tile_sum, (int32_t)scan_tiles);
+  group_scan_launch(d_sizes, d_n_groups, cg, ci, tile_sum, scan_tiles, st);
   hipLaunchKernelGGL(gs_offsets_kernel, dim3(scan_tiles), dim3(kGsBlock), 0, st, d_sizes, d_n_groups, cg, ci,
                      (const uint64_t *)tile_sum, off, box, ext);
   const GroupList L{t->d_nodes, inv, t->n, d_ids, grp};
   if (slot_tiles) {
-    hipLaunchKernelGGL(gs_map_kernel, dim3(slot_tiles), dim3(kGsBlock), 0, st, (const int32_t *)off, d_n_groups, cg, grp);
+    group_map_launch(off, d_n_groups, cg, grp, slot_tiles, st);
     hipLaunchKernelGGL(gs_box_kernel, dim3(gather_tiles), dim3(kGsBlock), 0, st, L, box);
     hipLaunchKernelGGL(gs_moment_kernel, dim3(gather_tiles), dim3(kGsBlock), 0, st, L, (const uint32_t *)box, rec);
   }

@@ -331,6 +331,26 @@ class KDTree {  // pc/storage/kdtree/kdtree.go:14-23
     return r;
   }
   GroupStatsResult GroupStats(const ClustersResult &c) const { return GroupStats(c.ids, c.sizes); }
+  // Per group of a grouped id list, what the group stands on: the exact convex hull of its (x, y), again a grouped id
+  // list (counter-clockwise from the lexicographically least place, -1 behind the last hull), the polygon's area and the
+  // minimum-area rectangle with a side along a hull edge (extension: no reference parity; include/pcgx.h,
+  // pcgx_kdtree_group_hulls).
+  struct GroupHullsResult {
+    std::vector<int64_t> hull_sizes, hull_ids;  // per group; per slot of ids
+    std::vector<double> area, rect;             // 1, 6 per group: centre x y, u x y, half-extents along u and (-u_y, u_x)
+  };
+  GroupHullsResult GroupHulls(const std::vector<int64_t> &ids, const std::vector<int64_t> &sizes) const {
+    const size_t g = sizes.size();
+    GroupHullsResult r;
+    r.hull_sizes.resize(g);
+    r.hull_ids.assign(ids.size(), -1);
+    r.area.resize(g);
+    r.rect.resize(6 * g);
+    check(pcgx_kdtree_group_hulls(h_.get(), ids.data(), (int64_t)ids.size(), sizes.data(), (int64_t)g, r.hull_sizes.data(),
+                                  r.hull_ids.data(), r.area.data(), r.rect.data()));
+    return r;
+  }
+  GroupHullsResult GroupHulls(const ClustersResult &c) const { return GroupHulls(c.ids, c.sizes); }
   // The k points with the smallest (DistSq, ID) among those with DistSq < maxRange^2, ascending (extension: no
   // reference parity; include/pcgx.h, pcgx_kdtree_knearest: ties go by ID).
   std::vector<Neighbor> KNearest(const Vec3 &p, int32_t k, float maxRange) const {

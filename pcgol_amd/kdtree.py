@@ -24,6 +24,12 @@ class Neighbor:  # pc/storage/search.go:8-11
 
 
 GroupGeometry = collections.namedtuple("GroupGeometry", "count aabb centroid cov eig axes obb")  # KDTree.GroupStats
+GroupFootprints = collections.namedtuple("GroupFootprints", "hull_sizes hull_ids area rect")  # KDTree.GroupHulls
+
+
+def GroupHullsChunk():
+    """Survivors a lane of GroupHulls' reduce rounds takes at a time (the boundary the tests put hulls across)."""
+    return int(L.lib().pcgx_group_hulls_chunk())
 
 
 def GroupStatsTile():
@@ -400,6 +406,33 @@ class KDTree:
         L.check(L.lib().pcgx_kdtree_group_stats_dev(
             self._h, opt(d_ids), int(cap_ids), opt(d_sizes), int(cap_groups), opt(d_n_groups), opt(d_count), opt(d_aabb),
             opt(d_centroid), opt(d_cov), opt(d_eig), opt(d_axes), opt(d_obb), L.ptr(stream) if stream else None))
+
+    # -- extension (no reference parity): group footprints, the exact 2-D hulls and upright boxes of a grouped id list
+    def GroupHulls(self, ids, sizes):
+        """Per group of a grouped id list (as GroupStats takes it) -> GroupFootprints(hull_sizes int64 (G,), hull_ids
+        int64 (len(ids),), area float64 (G,), rect float64 (G, 6)): the vertices of the exact convex hull of the group's
+        (x, y), again a grouped id list (counter-clockwise from the lexicographically least place, a place by its
+        smallest id, -1 behind the last hull), the polygon's area, and the minimum-area rectangle with a side along a
+        hull edge as centre x, y, the unit direction u of that edge and the half-extents along u and (-u_y, u_x)
+        (include/pcgx.h, pcgx_kdtree_group_hulls)."""
+        ids = np.ascontiguousarray(ids, np.int64).reshape(-1)
+        sizes = np.ascontiguousarray(sizes, np.int64).reshape(-1)
+        g = len(sizes)
+        out = GroupFootprints(np.zeros(g, np.int64), np.full(len(ids), -1, np.int64), np.zeros(g), np.zeros((g, 6)))
+        L.check(L.lib().pcgx_kdtree_group_hulls(self._h, L.ptr(ids) if len(ids) else None, len(ids),
+                                                L.ptr(sizes) if g else None, g,
+                                                *[L.ptr(a) if g and a.size else None for a in out]))
+        return out
+
+    def GroupHullsDev(self, d_ids, cap_ids, d_sizes, cap_groups, d_n_groups=0, d_hull_sizes=0, d_hull_ids=0, d_area=0,
+                      d_rect=0, stream=0):
+        """Device-resident GroupHulls: raw device addresses as GroupStatsDev takes them; the outputs (0: not wanted):
+        d_hull_sizes int32 [cap_groups], d_hull_ids int32 [cap_ids], d_area float64 [cap_groups], d_rect float64
+        [6 cap_groups].  Enqueued on `stream`, returns without waiting; nothing is read back."""
+        opt = lambda a: L.ptr(int(a)) if a else None  # noqa: E731
+        L.check(L.lib().pcgx_kdtree_group_hulls_dev(
+            self._h, opt(d_ids), int(cap_ids), opt(d_sizes), int(cap_groups), opt(d_n_groups), opt(d_hull_sizes),
+            opt(d_hull_ids), opt(d_area), opt(d_rect), L.ptr(stream) if stream else None))
 
     # -- extension (no reference parity): k nearest neighbours
     def KNearest(self, p, k, maxRange):

@@ -218,3 +218,11 @@ class ClusterExtraction:
         if self.sizes is None:
             raise RuntimeError("Boxes() needs Extract() first")
         return self.search.GroupStats(self.ids, self.sizes)
+
+    def Footprints(self):
+        """After Extract(): what the extracted clusters stand on, one row each -> KDTree.GroupHulls' tuple (hull_sizes,
+        hull_ids, area, rect): the exact convex hull of a cluster's (x, y) and the smallest upright rectangle with a side
+        along one of its edges."""
+        if self.sizes is None:
+            raise RuntimeError("Footprints() needs Extract() first")
+        return self.search.GroupHulls(self.ids, self.sizes)
