@@ -580,6 +580,46 @@ func (k *KDTree) Clusters(radius float32, p ClusterParams) (labels, sizes, ids [
 	return labels, sizes, ids[:int(total)], nil
 }
 
+// DBSCAN returns the density clusters of the tree's points (extension: no reference parity; include/pcgx.h,
+// pcgx_kdtree_dbscan): a point with at least minPts points within radius (DistSq < radius^2, itself included) is
+// core; a cluster is a component of core points plus its border points, each with its nearest core neighbour
+// (smallest DistSq, then smallest id); kept when max(minSize, 1) <= size, and size <= maxSize unless maxSize is 0.
+// labels, sizes and ids as Clusters returns them; kind per point: 0 noise, 1 border, 2 core.
+func (k *KDTree) DBSCAN(radius float32, minPts int32, minSize, maxSize int64) (labels, sizes, ids []int64, kind []uint8, err error) {
+	runtime.LockOSThread() // the error text is thread-local on the C side: call and pcgx_last_error on one OS thread
+	defer runtime.UnlockOSThread()
+	defer runtime.KeepAlive(k) // the finalizer must not free the handle while a call is in flight
+	var ln C.int64_t
+	if err := status(C.pcgx_kdtree_len(k.t.h, &ln)); err != nil {
+		return nil, nil, nil, nil, err
+	}
+	n := int(ln)
+	labels = make([]int64, n)
+	sizes = make([]int64, n)
+	ids = make([]int64, n)
+	kind = make([]uint8, n)
+	if n == 0 {
+		return labels, sizes, ids, kind, nil
+	}
+	var c C.int64_t
+	rc := C.pcgx_kdtree_dbscan(k.t.h, C.float(radius), C.int32_t(minPts), C.int64_t(minSize), C.int64_t(maxSize),
+		(*C.int64_t)(unsafe.Pointer(&labels[0])), &c, (*C.int64_t)(unsafe.Pointer(&sizes[0])),
+		(*C.int64_t)(unsafe.Pointer(&ids[0])), (*C.uint8_t)(unsafe.Pointer(&kind[0])))
+	runtime.KeepAlive(labels)
+	runtime.KeepAlive(sizes)
+	runtime.KeepAlive(ids)
+	runtime.KeepAlive(kind)
+	if err := status(rc); err != nil {
+		return nil, nil, nil, nil, err
+	}
+	sizes = sizes[:int(c)]
+	total := int64(0)
+	for _, s := range sizes {
+		total += s
+	}
+	return labels, sizes, ids[:int(total)], kind, nil
+}
+
 // GroupGeometry is the result of (*KDTree).GroupStats, one row per group: Count of live members; AABB lo x, y, z then
 // hi x, y, z; Centroid; Cov in the order xx, xy, xz, yy, yz, zz; Eig descending; Axes: the three unit eigenvectors as
 // rows (axis 2 is the fitted plane's normal); OBB: centre x, y, z, then the half-extents along the axes.  A group
@@ -1123,6 +1163,44 @@ func (f *SOR) FilterStats(pp *pc.PointCloud) (*pc.PointCloud, []float64, [3]floa
 	newPc := &pc.PointCloud{PointCloudHeader: pp.Clone(), Points: int(m), Data: out[:int(m)*stride]}
 	newPc.Width, newPc.Height = int(m), 1
 	return newPc, md, stats, nil
+}
+
+// ROR is a filter.Filter for radius outlier removal (no reference counterpart; PCL's RadiusOutlierRemoval;
+// include/pcgx.h, pcgx_ror_filter): keeps the finite points with at least MinNeighbors finite points within Radius,
+// themselves included (Negative: the other finite points), records byte for byte in input order.  Non-finite points
+// are dropped in both modes.
+type ROR struct {
+	Radius       float32
+	MinNeighbors int
+	Negative     bool
+}
+
+func (f *ROR) Filter(pp *pc.PointCloud) (*pc.PointCloud, error) {
+	runtime.LockOSThread() // the error text is thread-local on the C side: call and pcgx_last_error on one OS thread
+	defer runtime.UnlockOSThread()
+	stride, off, err := xyzLayout(pp)
+	if err != nil {
+		return nil, err
+	}
+	n := pp.Points
+	if n == 0 {
+		return nil, errors.New("no point")
+	}
+	out := make([]byte, n*stride)
+	neg := C.int32_t(0)
+	if f.Negative {
+		neg = 1
+	}
+	var m C.int64_t
+	rc := C.pcgx_ror_filter(unsafe.Pointer(&pp.Data[0]), C.int64_t(n), C.int32_t(stride), C.int32_t(off),
+		C.float(f.Radius), C.int32_t(f.MinNeighbors), neg, unsafe.Pointer(&out[0]), &m)
+	runtime.KeepAlive(pp)
+	if err := status(rc); err != nil {
+		return nil, err
+	}
+	newPc := &pc.PointCloud{PointCloudHeader: pp.Clone(), Points: int(m), Data: out[:int(m)*stride]}
+	newPc.Width, newPc.Height = int(m), 1
+	return newPc, nil
 }
 
 // FilterSharded is this rank's share of Filter(pp) over the ranks of c (SURVEY 8(e)): every rank

@@ -1032,6 +1032,61 @@ PCGX_API pcgx_status pcgx_kdtree_clusters_dev(const pcgx_kdtree *t, float radius
                                               int32_t *d_n_clusters, int32_t *d_sizes /* [Len()], may be NULL */,
                                               int32_t *d_ids /* [Len()], may be NULL */, void *stream);
 
+/* ------------------------------------------- density clusters (extension: no reference parity)
+ * NOT in the reference.  DBSCAN (Ester, Kriegel, Sander and Xu 1996; Open3D's cluster_dbscan, scikit-learn's DBSCAN)
+ * over the tree's own points: the components of the radius graph over the points whose neighbourhood is dense, plus the
+ * points on their rim.  A single stray return between two objects joins them in "clusters" above; here it joins nobody
+ * unless it has min_pts points around it.  Every array is in id order over the tree's own points, deleted ids included,
+ * as in "clusters".  This comment is the contract, tests/dbscan_oracle.py restates it.
+ * Neighbourhood: N(i) is the N(i) of "clusters": the points p of the tree with DistSq(p, point i) < radius^2, strict,
+ *   DistSq the reference's float32 expression: exactly the set pcgx_kdtree_range_count counts on that handle (grid,
+ *   forced walk, after DeletePoint).  Deleted points are nobody's neighbour and count for nobody.
+ * Usable point: i is usable iff i is in N(i) (this excludes a deleted id and a point with a NaN or infinite
+ *   coordinate).  There are no normals and no curvature in this call: no cut of either kind.
+ * Core point: i is core iff it is usable and |N(i)| >= min_pts.  The point counts itself (as in Open3D and
+ *   scikit-learn), and every member of N(i) counts, core or not.  min_pts >= 1.
+ * Core edge: {i, j} with i != j is an edge iff both points are core and j is in N(i) (symmetric bit for bit).
+ * Border point: a usable point that is not core and has at least one core point in N(i).  It belongs to the component
+ *   of its nearest core neighbour: the one of the smallest float32 DistSq, of equal ones the one of the smallest id.
+ *   (The textbook rule, "whichever cluster reaches it first", depends on the visit order and cannot be pinned; this one
+ *   is a property of the point set, and it is local: no component's name is needed to decide it.)  A border point
+ *   carries no edge and joins nobody else.
+ * Noise: every other point: the unusable ones, and the points that are not core and have no core point in N(i).
+ * Clusters: a cluster is a connected component of the core points under the core edges, plus its border points.  Its
+ *   size counts both, and its smallest member id is taken over both.  It is kept when max(min_size, 1) <= size, and
+ *   also size <= max_size when max_size > 0 (max_size == 0: no upper limit).  The clusters are numbered 0 .. C-1 by
+ *   decreasing size, equal sizes by the smallest member id, ascending.
+ * Outputs: labels[i] = the cluster's number, or -1 for a noise point or a point of a cluster outside the size range.
+ *   *n_clusters = C.  sizes[0 .. C) holds the sizes and is 0 in every remaining slot.  ids holds the members of cluster
+ *   0 in ascending id, then those of cluster 1, and so on, then -1 in every remaining slot; cluster c starts at the sum
+ *   of the sizes before it.  (Word for word the outputs of pcgx_kdtree_clusters[_dev], int64 in the host form, int32 in
+ *   the device form: d_ids, d_sizes and d_n_clusters can be passed on to pcgx_kdtree_group_stats_dev and
+ *   pcgx_kdtree_group_hulls_dev as they are.)
+ *   kind[i], uint8_t in both forms, optional: 0 noise or unusable, 1 border, 2 core.  kind does not depend on the size
+ *   range: a core point of a cluster that is dropped for its size keeps kind 2 and gets label -1.
+ * min_pts == 1: every usable point is core, and labels, *n_clusters, sizes and ids equal those of pcgx_kdtree_clusters
+ *   with normals == NULL and curvature == NULL on that handle bit for bit; no count pass runs.
+ * PCGX_E_INVALID: a radius that is not finite and > 0; min_size < 0 or max_size < 0; 0 < max_size < max(min_size, 1);
+ *   a NULL tree; NULL labels or n_clusters with Len() > 0; min_pts < 1.  Nothing is written then.  Len() == 0 is
+ *   PCGX_OK and writes only *n_clusters = 0.  The same input gives the same bits on every call.
+ * Always computed on the device.  Cost: what pcgx_kdtree_clusters costs, plus with min_pts >= 2 two more enumerations:
+ *   a flag pass (per point the records of the cells, or tree nodes, that its radius covers, on a grid only until min_pts
+ *   of them are in reach) and a border pass (the same records, whole, for the usable points that are not core).  There
+ *   is no wave-shared path for a grid row of thousands of coincident points, as in clusters: such a row is one lane's
+ *   loop for each of its points.  Temporaries: those of pcgx_kdtree_clusters and Len() more bytes of flags. */
+PCGX_API pcgx_status pcgx_kdtree_dbscan(const pcgx_kdtree *t, float radius, int32_t min_pts, int64_t min_size,
+                                        int64_t max_size, int64_t *labels /* [Len()] */, int64_t *n_clusters,
+                                        int64_t *sizes /* [Len()], may be NULL */,
+                                        int64_t *ids /* [Len()], may be NULL */,
+                                        uint8_t *kind /* [Len()], may be NULL */);
+/* Same, every array device resident (labels, sizes, ids and the count are int32 there, kind stays uint8_t), enqueued on
+ * `stream` (NULL: the library's); returns without waiting, reads nothing back. */
+PCGX_API pcgx_status pcgx_kdtree_dbscan_dev(const pcgx_kdtree *t, float radius, int32_t min_pts, int64_t min_size,
+                                            int64_t max_size, int32_t *d_labels /* [Len()] */, int32_t *d_n_clusters,
+                                            int32_t *d_sizes /* [Len()], may be NULL */,
+                                            int32_t *d_ids /* [Len()], may be NULL */,
+                                            uint8_t *d_kind /* [Len()], may be NULL */, void *stream);
+
 /* ------------------------------------------- group geometry (extension: no reference parity)
  * NOT in the reference.  What a user takes from clusters next: per group of a grouped id list over the tree's own
  * points -- the shape pcgx_kdtree_clusters writes, and what region growing's components, a plane's inliers or a keypoint
@@ -1445,6 +1500,29 @@ PCGX_API pcgx_status pcgx_sor_filter(const void *data, int64_t n, int32_t stride
 PCGX_API pcgx_status pcgx_sor_filter_dev(const void *d_data, int64_t n, int32_t stride, int32_t xyz_off,
                                          int32_t mean_k, float std_mul, int32_t negative, void *d_out,
                                          int64_t *out_n, double *d_mean_dist, double stats[3], void *stream);
+
+/* ------------------------------------------- radius outlier removal (extension: no reference parity)
+ * PCL's RadiusOutlierRemoval / Open3D's remove_radius_outlier over an AoS cloud (stride / xyz_off as
+ * pcgx_voxel_filter), in the shape of pcgx_sor_filter.
+ *   F = the points whose x, y, z are all finite (the others are dropped in both modes and are nobody's neighbour).
+ *   keep i of F iff |{p in F : DistSq(p, i) < radius^2}| >= min_neighbors, DistSq the reference's float32 expression,
+ *   strict.  The point itself is counted: PCL's radius search returns the query point too, so min_neighbors = k here
+ *   keeps what PCL's setMinNeighborsInRadius(k) keeps for a cloud without duplicates of the query; Open3D's nb_points
+ *   counts the same way.  min_neighbors == 1 keeps exactly F.
+ *   negative != 0 keeps the other points of F.
+ *   Output: the kept records, byte for byte, in input order; *out_n of them (out_data must hold n*stride bytes).
+ * By definition the kept set is kind == 2 of pcgx_kdtree_dbscan on a tree over F with min_pts = min_neighbors: one
+ * kernel decides both.  A tree over F is built inside the call (pcgx_kdtree_build).
+ * PCGX_E_INVALID: a radius that is not finite and > 0, or min_neighbors < 1; a stride / offset that does not hold an
+ * xyz triple -> PCGX_E_BAD_FIELD; n == 0 or F empty -> PCGX_E_NO_POINT. */
+PCGX_API pcgx_status pcgx_ror_filter(const void *data, int64_t n, int32_t stride, int32_t xyz_off, float radius,
+                                     int32_t min_neighbors, int32_t negative, void *out_data, int64_t *out_n);
+/* Device resident: d_data and d_out (>= n*stride bytes) are device buffers; out_n is host memory.  Returns when
+ * everything is done on `stream` (the tree build in between needs the finite count on the host, and the tree is freed
+ * before the call returns). */
+PCGX_API pcgx_status pcgx_ror_filter_dev(const void *d_data, int64_t n, int32_t stride, int32_t xyz_off, float radius,
+                                         int32_t min_neighbors, int32_t negative, void *d_out, int64_t *out_n,
+                                         void *stream);
 
 /* ------------------------------------------- Normal Distributions Transform (extension: no reference parity)
  * NOT in the reference: pcgol has nothing like it.  NDT registration (Biber and Strasser 2003; Magnusson 2009; PCL's

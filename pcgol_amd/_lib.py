@@ -266,6 +266,8 @@ SIGNATURES = {
     "pcgx_kdtree_local_maxima_dev": (_i32, [_vp, _f32, _vp, _vp, _vp, _vp]),
     "pcgx_kdtree_clusters": (_i32, [_vp, _f32, _vp, _f32, _i32, _vp, _f32, _i64, _i64, _vp, C.POINTER(_i64), _vp, _vp]),
     "pcgx_kdtree_clusters_dev": (_i32, [_vp, _f32, _vp, _f32, _i32, _vp, _f32, _i64, _i64, _vp, _vp, _vp, _vp, _vp]),
+    "pcgx_kdtree_dbscan": (_i32, [_vp, _f32, _i32, _i64, _i64, _vp, C.POINTER(_i64), _vp, _vp, _vp]),
+    "pcgx_kdtree_dbscan_dev": (_i32, [_vp, _f32, _i32, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
     "pcgx_kdtree_group_stats": (_i32, [_vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "pcgx_kdtree_group_stats_dev": (_i32, [_vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "pcgx_group_stats_tile": (_i32, []),
@@ -297,6 +299,8 @@ SIGNATURES = {
                                      C.POINTER(IcpStat), _vp]),
     "pcgx_sor_filter": (_i32, [_vp, _i64, _i32, _i32, _i32, _f32, _i32, _vp, C.POINTER(_i64), _vp, _vp]),
     "pcgx_sor_filter_dev": (_i32, [_vp, _i64, _i32, _i32, _i32, _f32, _i32, _vp, C.POINTER(_i64), _vp, _vp, _vp]),
+    "pcgx_ror_filter": (_i32, [_vp, _i64, _i32, _i32, _f32, _i32, _i32, _vp, C.POINTER(_i64)]),
+    "pcgx_ror_filter_dev": (_i32, [_vp, _i64, _i32, _i32, _f32, _i32, _i32, _vp, C.POINTER(_i64), _vp]),
     "pcgx_ndt_map_create": (_i32, [_vp, _vp, _i64, _i32, _i32, _i32, _i32, _f32, C.POINTER(_vp)]),
     "pcgx_ndt_map_free": (_i32, [_vp]),
     "pcgx_ndt_map_counts": (_i32, [_vp, C.POINTER(_i64), C.POINTER(_i64)]),

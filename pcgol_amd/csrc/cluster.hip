@@ -22,10 +22,16 @@
 //               ascending id: a seed's position is its cluster's number.  The count is where the seeds end.
 //   grouping    labels = rank[name]; a second stable sort of the labels with iota values gives the member lists.
 // Integer atomics only; the same input gives the same bits on every call.
+//
+// Density clustering (dbscan.hip; include/pcgx.h, "density clusters") comes through clusters_enqueue too: with min_pts
+// >= 2 a count pass writes core flags where the usable flags would lie, the component passes run on them unchanged, a
+// border pass stores every attached border point's core neighbour into its own parent word before the last pointer
+// jumping, and the tail counts core and border points alike.
 #include <math.h>
 #include <stdlib.h>
 
 #include "cluster_terms.h"
+#include "dbscan.h"
 #include "knn_grid.h"
 #include "range_walk.h"
 #include "uf.h"
@@ -317,20 +323,21 @@ static int cl_key_bits(int64_t n) {  // keys are 0 .. n
   return b;
 }
 
-// Len() > 0, everything device resident; temporaries from ctx().arena, which the caller has begun.
-// a: the tree the neighbourhoods come from (resolve_tree; nullptr: every point was deleted); n: the handle's Len().
-static pcgx_status clusters_enqueue(const pcgx_kdtree *a, int64_t n, float radius, const float *d_normals, float min_cos,
-                                    int32_t oriented, const float *d_curvature, float max_curvature, int64_t min_size,
-                                    int64_t max_size, int32_t *d_labels, int32_t *d_n_clusters, int32_t *d_sizes,
-                                    int32_t *d_ids, hipStream_t st) {
+// (dbscan.h says what the arguments are)
+pcgx_status clusters_enqueue(const pcgx_kdtree *a, int64_t n, float radius, const float *d_normals, float min_cos,
+                             int32_t oriented, const float *d_curvature, float max_curvature, int64_t min_size,
+                             int64_t max_size, const ClusterDensity *density, int32_t *d_labels, int32_t *d_n_clusters,
+                             int32_t *d_sizes, int32_t *d_ids, hipStream_t st) {
   Arena &ar = ctx().arena;
   const unsigned nb = (unsigned)((n + 255) / 256);
   const float bound = radius * radius;
   const ClusterCut cut{min_cos, oriented};
   uint32_t *parent = nullptr, *count = nullptr, *min_id = nullptr, *name = nullptr, *psize = nullptr;
   uint32_t *keys[2] = {nullptr, nullptr}, *vals[2] = {nullptr, nullptr};
-  uint8_t *usable = nullptr;
+  uint8_t *usable = nullptr, *core = nullptr;
   float4 *nrm = nullptr;
+  // dense: the edges join core points (core[]), and usable[] holds what the tail counts: 2 core, 1 attached border
+  const bool dense = density && density->min_pts > 1;
   void *ws = nullptr;
   PCGX_TRY(ar.alloc_n((size_t)n, &parent));
   PCGX_TRY(ar.alloc_n((size_t)n, &count));
@@ -344,47 +351,59 @@ static pcgx_status clusters_enqueue(const pcgx_kdtree *a, int64_t n, float radiu
   PCGX_TRY(ar.alloc(radix_sort_workspace_bytes(n), &ws));
   if (d_normals) PCGX_TRY(ar.alloc_n((size_t)n, &nrm));
   PCGX_TRY(ar.alloc_n((size_t)n, &usable));
+  if (dense) PCGX_TRY(ar.alloc_n((size_t)n, &core));
 
   hipLaunchKernelGGL(cl_init_kernel, dim3(nb), dim3(256), 0, st, parent, count, min_id, n);
   const bool on_grid = a && a->grid_ok && a->n == n && !range_walk_forced();  // (as region growing takes its source)
   const float4 *pts = on_grid ? a->grid.pts : nullptr;
   if (on_grid) {
     const GridView &g = a->grid;
-    hipLaunchKernelGGL(cl_stage_grid_kernel, dim3(nb), dim3(256), 0, st, g, n, bound, d_normals, d_curvature, max_curvature,
-                       usable, nrm);
-    const int read = d_normals ? kCutNormals : (d_curvature ? kCutFlags : kCutNone);
+    if (dense)
+      dbscan_flags_launch(a, true, n, bound, density->min_pts, density->count_all, core, st);
+    else
+      hipLaunchKernelGGL(cl_stage_grid_kernel, dim3(nb), dim3(256), 0, st, g, n, bound, d_normals, d_curvature,
+                         max_curvature, usable, nrm);
+    const int read = d_normals ? kCutNormals : (d_curvature || dense ? kCutFlags : kCutNone);
+    const uint8_t *joins = dense ? core : usable;  // the byte cl_joins reads of a neighbour
 #define PCGX_CL_GRID(HOOK)                                                                                             \
   do {                                                                                                                 \
     if (read == kCutNormals)                                                                                           \
       hipLaunchKernelGGL((cl_grid_kernel<HOOK, kCutNormals>), dim3(nb), dim3(256), 0, st, g, n, bound,                 \
-                         (const uint8_t *)usable, (const float4 *)nrm, cut, parent);                                   \
+                         joins, (const float4 *)nrm, cut, parent);                                                     \
     else if (read == kCutFlags)                                                                                        \
       hipLaunchKernelGGL((cl_grid_kernel<HOOK, kCutFlags>), dim3(nb), dim3(256), 0, st, g, n, bound,                   \
-                         (const uint8_t *)usable, (const float4 *)nrm, cut, parent);                                   \
+                         joins, (const float4 *)nrm, cut, parent);                                                     \
     else                                                                                                               \
       hipLaunchKernelGGL((cl_grid_kernel<HOOK, kCutNone>), dim3(nb), dim3(256), 0, st, g, n, bound,                    \
-                         (const uint8_t *)usable, (const float4 *)nrm, cut, parent);                                   \
+                         joins, (const float4 *)nrm, cut, parent);                                                     \
   } while (0)
     PCGX_CL_GRID(true);
     hipLaunchKernelGGL(uf_jump_kernel, dim3(nb), dim3(256), 0, st, parent, n);
     PCGX_CL_GRID(false);
 #undef PCGX_CL_GRID
+    if (dense) dbscan_border_launch(a, true, n, bound, core, usable, parent, st);
     hipLaunchKernelGGL(uf_jump_kernel, dim3(nb), dim3(256), 0, st, parent, n);
   } else {
     PCGX_HIP_TRY(hipMemsetAsync(usable, 0, (size_t)n, st));
+    if (dense) PCGX_HIP_TRY(hipMemsetAsync(core, 0, (size_t)n, st));
     if (a) {
       const TreeView tv = a->view();
       const uint32_t slots = 1u << tv.depth;
-      hipLaunchKernelGGL(cl_stage_tree_kernel, dim3((slots + 255u) / 256u), dim3(256), 0, st, tv, bound, d_normals,
-                         d_curvature, max_curvature, usable, nrm);
+      if (dense)
+        dbscan_flags_launch(a, false, n, bound, density->min_pts, density->count_all, core, st);
+      else
+        hipLaunchKernelGGL(cl_stage_tree_kernel, dim3((slots + 255u) / 256u), dim3(256), 0, st, tv, bound, d_normals,
+                           d_curvature, max_curvature, usable, nrm);
+      const uint8_t *joins = dense ? core : usable;
       const dim3 wgrid((slots + kRangeWalkBlock - 1) / kRangeWalkBlock), wblock(kRangeWalkBlock);
       const size_t lds = walk_stack_bytes(tv, kRangeWalkBlock);
       if (d_normals)
         hipLaunchKernelGGL(cl_walk_kernel<kCutNormals>, wgrid, wblock, lds, st, tv, bound, (const uint8_t *)usable,
                            (const float4 *)nrm, cut, parent);
       else
-        hipLaunchKernelGGL(cl_walk_kernel<kCutFlags>, wgrid, wblock, lds, st, tv, bound, (const uint8_t *)usable,
-                           (const float4 *)nrm, cut, parent);
+        hipLaunchKernelGGL(cl_walk_kernel<kCutFlags>, wgrid, wblock, lds, st, tv, bound, joins, (const float4 *)nrm, cut,
+                           parent);
+      if (dense) dbscan_border_launch(a, false, n, bound, core, usable, parent, st);
       hipLaunchKernelGGL(uf_jump_kernel, dim3(nb), dim3(256), 0, st, parent, n);
     }
   }
@@ -403,6 +422,7 @@ static pcgx_status clusters_enqueue(const pcgx_kdtree *a, int64_t n, float radiu
   hipLaunchKernelGGL(cl_label_kernel, dim3(nb), dim3(256), 0, st, (const uint32_t *)name, (const uint32_t *)psize,
                      (const uint32_t *)rank, n, min_size, max_size, d_labels, d_ids ? keys[0] : nullptr);
   PCGX_HIP_TRY(hipGetLastError());
+  if (density && density->d_kind) dbscan_kind_launch(pts, n, usable, !dense, density->d_kind, st);
   if (d_ids) {
     int r2 = 0;
     PCGX_TRY(radix_sort_pairs(keys, vals, n, bits, ws, &r2, st, true));
@@ -412,12 +432,6 @@ static pcgx_status clusters_enqueue(const pcgx_kdtree *a, int64_t n, float radiu
   }
   return PCGX_OK;
 }
-
-}  // namespace pcgx
-
-using namespace pcgx;
-
-namespace {
 
 constexpr int64_t kClusterMaxPoints = 0x7fffffff;  // ids are int32 on the device
 
@@ -436,7 +450,9 @@ pcgx_status clusters_check(const char *fn, const pcgx_kdtree *t, float radius, c
   return PCGX_OK;
 }
 
-}  // namespace
+}  // namespace pcgx
+
+using namespace pcgx;
 
 extern "C" pcgx_status pcgx_kdtree_clusters_dev(const pcgx_kdtree *t, float radius, const float *d_normals, float min_cos,
                                                 int32_t oriented, const float *d_curvature, float max_curvature,
@@ -457,7 +473,7 @@ extern "C" pcgx_status pcgx_kdtree_clusters_dev(const pcgx_kdtree *t, float radi
   PCGX_TRY(resolve_tree(t, &a, &empty));  // after DeletePoint: the tree over the remaining points, original ids
   PCGX_TRY(ctx().arena.begin(st));
   return clusters_enqueue(empty ? nullptr : a, n, radius, d_normals, min_cos, oriented, d_curvature, max_curvature, min_size,
-                          max_size, d_labels, d_n_clusters, d_sizes, d_ids, st);
+                          max_size, nullptr, d_labels, d_n_clusters, d_sizes, d_ids, st);
 }
 
 extern "C" pcgx_status pcgx_kdtree_clusters(const pcgx_kdtree *t, float radius, const float *normals, float min_cos,

@@ -15,6 +15,7 @@
 #include <memory>
 
 #include "bucket_grid.h"
+#include "dbscan.h"
 
 namespace pcgx {
 
@@ -206,9 +207,129 @@ pcgx_status sor_check(const char *fn, const void *data, int64_t n, int32_t strid
   return PCGX_OK;
 }
 
+// ------------------------------------------------------------------ radius outlier removal
+// pcgx_ror_filter: the same pipeline with a flag in place of the mean distance.  Steps 1, 2 and 5 are the ones above;
+// step 3 is density clustering's flag pass (dbscan.hip): the kept points are its core points at min_pts = min_neighbors.
+// flag by input index: 0 a dropped record, 1 a point of F with enough neighbours, 2 any other point of F.
+__global__ __launch_bounds__(256) void ror_place_kernel(const uint8_t *__restrict__ core, const int64_t *__restrict__ orig,
+                                                        int64_t m, uint8_t *__restrict__ flag) {
+  const int64_t j = (int64_t)blockIdx.x * 256 + threadIdx.x;
+  if (j < m) flag[orig[j]] = core[j] ? (uint8_t)1 : (uint8_t)2;
+}
+__global__ __launch_bounds__(256) void ror_keep_count_kernel(const uint8_t *__restrict__ flag, int64_t n, uint8_t want,
+                                                             uint32_t *__restrict__ tile_count) {
+  tile_flag_count(n, [&](int64_t j) { return flag[j] == want; }, tile_count);
+}
+__global__ __launch_bounds__(256) void ror_keep_write_kernel(const uint8_t *__restrict__ flag, int64_t n, uint8_t want,
+                                                             const uint32_t *__restrict__ tile_offset,
+                                                             const uint8_t *__restrict__ data, int32_t stride,
+                                                             uint8_t *__restrict__ out) {
+  const bool words = ((stride & 3) | ((uintptr_t)data & 3) | ((uintptr_t)out & 3)) == 0;
+  tile_flag_write(n, [&](int64_t j) { return flag[j] == want; }, tile_offset, [=](uint32_t slot, int64_t j) {
+    copy_record(data + j * stride, out + (int64_t)slot * stride, stride, words);
+  });
+}
+
+// The whole filter on device records; temporaries from `ka` (begun by the caller), the tree's and the flag pass's from
+// the context's arena.  Returns with st drained.
+pcgx_status ror_run(const uint8_t *d_data, int64_t n, int32_t stride, int32_t off, float radius, int32_t min_neighbors,
+                    int32_t negative, uint8_t *d_out, int64_t *out_n, hipStream_t st, Arena &ka) {
+  const int ntiles = (int)((n + kRunTile - 1) / kRunTile);
+  uint32_t *tile_count = nullptr, *d_total = nullptr;
+  float *d_xyz = nullptr;
+  int64_t *d_orig = nullptr;
+  uint8_t *d_core = nullptr, *d_flag = nullptr;
+  PCGX_TRY(ka.alloc_n((size_t)ntiles, &tile_count));
+  PCGX_TRY(ka.alloc_n(2, &d_total));
+  PCGX_TRY(ka.alloc_n((size_t)n * 3, &d_xyz));
+  PCGX_TRY(ka.alloc_n((size_t)n, &d_orig));
+  PCGX_TRY(ka.alloc_n((size_t)n, &d_core));
+  PCGX_TRY(ka.alloc_n((size_t)n, &d_flag));
+  // 1. finite records
+  hipLaunchKernelGGL(sor_finite_count_kernel, dim3(ntiles), dim3(256), 0, st, d_data, n, stride, off, tile_count);
+  hipLaunchKernelGGL(sor_scan_kernel, dim3(1), dim3(1024), 0, st, tile_count, ntiles, d_total);
+  hipLaunchKernelGGL(sor_finite_write_kernel, dim3(ntiles), dim3(256), 0, st, d_data, n, stride, off,
+                     (const uint32_t *)tile_count, d_xyz, d_orig);
+  PCGX_HIP_TRY(hipGetLastError());
+  uint32_t m32 = 0;
+  PCGX_HIP_TRY(hipMemcpyAsync(&m32, d_total, 4, hipMemcpyDeviceToHost, st));
+  PCGX_HIP_TRY(hipStreamSynchronize(st));
+  const int64_t m = m32;
+  if (m == 0) return fail(PCGX_E_NO_POINT, "pcgx_ror_filter: no finite point");
+  // 2. the tree
+  RawVector<float> h_xyz((size_t)m * 3);
+  PCGX_TRY(staged_download(h_xyz.data(), d_xyz, (size_t)m * 12, st));
+  pcgx_kdtree *raw = nullptr;
+  PCGX_TRY(pcgx_kdtree_build(h_xyz.data(), m, 12, 0, &raw));
+  std::unique_ptr<pcgx_kdtree, TreeFree> tree(raw);
+  // 3. the core flag per tree id
+  PCGX_TRY(ctx().arena.begin(st));
+  PCGX_TRY(dbscan_core_by_id_enqueue(tree.get(), radius, min_neighbors, d_core, st));
+  // by input index
+  PCGX_HIP_TRY(hipMemsetAsync(d_flag, 0, (size_t)n, st));
+  hipLaunchKernelGGL(ror_place_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, (const uint8_t *)d_core,
+                     (const int64_t *)d_orig, m, d_flag);
+  // 5. the kept records
+  const uint8_t want = negative ? (uint8_t)2 : (uint8_t)1;
+  hipLaunchKernelGGL(ror_keep_count_kernel, dim3(ntiles), dim3(256), 0, st, (const uint8_t *)d_flag, n, want, tile_count);
+  hipLaunchKernelGGL(sor_scan_kernel, dim3(1), dim3(1024), 0, st, tile_count, ntiles, d_total + 1);
+  hipLaunchKernelGGL(ror_keep_write_kernel, dim3(ntiles), dim3(256), 0, st, (const uint8_t *)d_flag, n, want,
+                     (const uint32_t *)tile_count, d_data, stride, d_out);
+  PCGX_HIP_TRY(hipGetLastError());
+  uint32_t kept = 0;
+  PCGX_HIP_TRY(hipMemcpyAsync(&kept, d_total + 1, 4, hipMemcpyDeviceToHost, st));
+  PCGX_HIP_TRY(hipStreamSynchronize(st));  // (the tree is freed below: its kernels must be done)
+  *out_n = kept;
+  return PCGX_OK;
+}
+
+pcgx_status ror_check(const char *fn, const void *data, int64_t n, int32_t stride, int32_t off, float radius,
+                      int32_t min_neighbors, const void *out, const int64_t *out_n) {
+  if (!out_n || n < 0 || (n > 0 && (!data || !out))) return fail(PCGX_E_INVALID, "%s: bad argument", fn);
+  if (!(radius > 0.0f && radius < __builtin_inff())) return fail(PCGX_E_INVALID, "%s: radius must be finite and > 0", fn);
+  if (min_neighbors < 1) return fail(PCGX_E_INVALID, "%s: min_neighbors must be >= 1", fn);
+  if (stride < 12 || off < 0 || off + 12 > stride)
+    return fail(PCGX_E_BAD_FIELD, "%s: stride %d / xyz offset %d do not hold an xyz triple", fn, (int)stride, (int)off);
+  if (n == 0) return fail(PCGX_E_NO_POINT, "%s: empty cloud", fn);
+  return PCGX_OK;
+}
+
 }  // namespace pcgx
 
 using namespace pcgx;
+
+extern "C" pcgx_status pcgx_ror_filter_dev(const void *d_data, int64_t n, int32_t stride, int32_t xyz_off, float radius,
+                                           int32_t min_neighbors, int32_t negative, void *d_out, int64_t *out_n,
+                                           void *stream) {
+  PCGX_API_LOCK();
+  PCGX_TRY(ror_check("pcgx_ror_filter_dev", d_data, n, stride, xyz_off, radius, min_neighbors, d_out, out_n));
+  PCGX_TRY(ensure_init());
+  hipStream_t st = pick_stream(stream);
+  Arena &ka = ctx().host_arena;
+  PCGX_TRY(ka.begin(st));
+  return ror_run((const uint8_t *)d_data, n, stride, xyz_off, radius, min_neighbors, negative, (uint8_t *)d_out, out_n, st,
+                 ka);
+}
+
+extern "C" pcgx_status pcgx_ror_filter(const void *data, int64_t n, int32_t stride, int32_t xyz_off, float radius,
+                                       int32_t min_neighbors, int32_t negative, void *out_data, int64_t *out_n) {
+  PCGX_API_CALL();
+  PCGX_TRY(ror_check("pcgx_ror_filter", data, n, stride, xyz_off, radius, min_neighbors, out_data, out_n));
+  PCGX_TRY(ensure_init());
+  hipStream_t st = ctx().stream;
+  Arena &ka = ctx().host_arena;
+  PCGX_TRY(ka.begin(st));
+  const size_t bytes = (size_t)n * (size_t)stride;
+  uint8_t *d_in = nullptr, *d_out = nullptr;
+  PCGX_TRY(ka.alloc_n(bytes, &d_in));
+  PCGX_TRY(ka.alloc_n(bytes, &d_out));
+  PCGX_TRY(staged_upload(d_in, data, bytes, st));
+  int64_t kept = 0;
+  PCGX_TRY(ror_run(d_in, n, stride, xyz_off, radius, min_neighbors, negative, d_out, &kept, st, ka));
+  if (kept > 0) PCGX_TRY(staged_download(out_data, d_out, (size_t)kept * (size_t)stride, st));
+  *out_n = kept;
+  return PCGX_OK;
+}
 
 extern "C" pcgx_status pcgx_sor_filter_dev(const void *d_data, int64_t n, int32_t stride, int32_t xyz_off, int32_t mean_k,
                                            float std_mul, int32_t negative, void *d_out, int64_t *out_n, double *d_mean_dist,

@@ -304,6 +304,30 @@ class KDTree {  // pc/storage/kdtree/kdtree.go:14-23
     r.ids.resize(total);
     return r;
   }
+  // Density clusters (extension: no reference parity; include/pcgx.h, pcgx_kdtree_dbscan): DBSCAN over the tree's own
+  // points.  A point with at least minPts points within radius (DistSq < radius^2, itself included) is core; a cluster
+  // is a component of core points plus its border points, each with its nearest core neighbour (smallest DistSq, then
+  // smallest id).  labels, sizes and ids as Clusters (a DBSCANResult is a ClustersResult: GroupStats and GroupHulls
+  // take it); kind: per point 0 noise, 1 border, 2 core, whatever the size range.
+  struct DBSCANResult : ClustersResult {
+    std::vector<uint8_t> kind;
+  };
+  DBSCANResult DBSCAN(float radius, int32_t minPts, int64_t minSize = 1, int64_t maxSize = 0) const {
+    const int64_t n = Len();
+    DBSCANResult r;
+    r.labels.resize((size_t)n);
+    r.sizes.resize((size_t)n);
+    r.ids.resize((size_t)n);
+    r.kind.resize((size_t)n);
+    int64_t c = 0;
+    check(pcgx_kdtree_dbscan(h_.get(), radius, minPts, minSize, maxSize, r.labels.data(), &c, r.sizes.data(), r.ids.data(),
+                             r.kind.data()));
+    r.sizes.resize((size_t)c);
+    size_t total = 0;
+    for (int64_t s : r.sizes) total += (size_t)s;
+    r.ids.resize(total);
+    return r;
+  }
   // Group geometry (extension: no reference parity; include/pcgx.h, pcgx_kdtree_group_stats): per group of a grouped id
   // list over the tree's own points -- ids: group 0's members, then group 1's, ...; sizes: per group; what Clusters
   // returns -- the count of live members, the axis-aligned box (lo xyz, hi xyz), centroid and covariance (xx, xy, xz,
@@ -554,6 +578,26 @@ class StatisticalOutlierRemoval {
     int64_t m = 0;
     check(pcgx_sor_filter(c.data, c.points, c.stride, c.xyz_offset, MeanK, StddevMul, Negative ? 1 : 0, out.data(), &m,
                           MeanDist.data(), Stats.data()));
+    out.resize((size_t)m * c.stride);
+    return out;
+  }
+};
+
+// Radius outlier removal (extension: no reference counterpart; PCL's RadiusOutlierRemoval; include/pcgx.h,
+// pcgx_ror_filter).  Keeps the finite points with at least MinNeighbors finite points within Radius, themselves
+// included (WithNegative(true): the other finite points); non-finite points are dropped.
+class RadiusOutlierRemoval {
+ public:
+  float Radius;
+  int32_t MinNeighbors;
+  bool Negative = false;
+  RadiusOutlierRemoval(float radius, int32_t minNeighbors) : Radius(radius), MinNeighbors(minNeighbors) {}
+  RadiusOutlierRemoval &WithNegative(bool negative) { Negative = negative; return *this; }
+  // Filter: returns the kept records in input order (Width = size()/stride, Height = 1).
+  std::vector<uint8_t> Filter(const CloudView &c) {
+    std::vector<uint8_t> out((size_t)c.points * c.stride);
+    int64_t m = 0;
+    check(pcgx_ror_filter(c.data, c.points, c.stride, c.xyz_offset, Radius, MinNeighbors, Negative ? 1 : 0, out.data(), &m));
     out.resize((size_t)m * c.stride);
     return out;
   }

@@ -1,7 +1,7 @@
 """pc/storage/kdtree mirror: KDTree on the GPU behind the storage.Search shape
 (pc/storage/search.go:13-17): Vec3At / Len / Nearest, plus batched NearestBatch, and extensions with no
 reference counterpart: surface normals (Normals), moving-least-squares smoothing (MLS), FPFH descriptors
-(FPFH, FPFHAt), keypoints (LocalMaxima, ISSKeypoints), cluster extraction (Clusters), per-group geometry
+(FPFH, FPFHAt), keypoints (LocalMaxima, ISSKeypoints), cluster extraction (Clusters), density clusters (DBSCAN), per-group geometry
 (GroupStats), k nearest neighbours (KNearest) and their covariances (Covariances)."""
 import collections
 import ctypes as C
@@ -377,6 +377,36 @@ class KDTree:
             self._h, float(radius), opt(d_normals), float(MinCos), int(bool(Oriented)), opt(d_curvature),
             float(MaxCurvature), int(MinSize), int(MaxSize), opt(d_labels), opt(d_n_clusters), opt(d_sizes), opt(d_ids),
             L.ptr(stream) if stream else None))
+
+    # -- extension (no reference parity): density clusters, DBSCAN over the same neighbourhoods
+    def DBSCAN(self, radius, MinPts, MinSize=1, MaxSize=0):
+        """DBSCAN over the tree's own points: a point is core when its neighbourhood (DistSq < radius^2, Range's set,
+        itself included) holds at least MinPts points; the clusters are the components of the core points plus the
+        border points, each with its nearest core neighbour (smallest DistSq, then smallest id); kept when MinSize <=
+        size (<= MaxSize unless 0), largest first, equal sizes by smallest id -> (labels int64 (n,), sizes int64 (C,),
+        ids int64 (sum(sizes),), kind uint8 (n,): 0 noise, 1 border, 2 core).  MinPts = 1 is Clusters(radius)
+        (include/pcgx.h, pcgx_kdtree_dbscan)."""
+        n = self.Len()
+        labels = np.empty(n, np.int64)
+        sizes = np.empty(n, np.int64)
+        ids = np.empty(n, np.int64)
+        kind = np.empty(n, np.uint8)
+        cnt = C.c_int64()
+        L.check(L.lib().pcgx_kdtree_dbscan(
+            self._h, float(radius), int(MinPts), int(MinSize), int(MaxSize), L.ptr(labels) if n else None, C.byref(cnt),
+            L.ptr(sizes) if n else None, L.ptr(ids) if n else None, L.ptr(kind) if n else None))
+        sizes = sizes[:cnt.value]
+        return labels, sizes, ids[:int(sizes.sum())], kind
+
+    def DBSCANDev(self, radius, MinPts, d_labels, d_n_clusters, d_sizes=0, d_ids=0, d_kind=0, MinSize=1, MaxSize=0,
+                  stream=0):
+        """Device-resident DBSCAN: raw device addresses (e.g. torch .data_ptr()); d_labels int32 [Len()], d_n_clusters
+        one int32, d_sizes int32 [Len()] (the sizes, then 0), d_ids int32 [Len()] (the members cluster by cluster, then
+        -1), d_kind uint8 [Len()].  Enqueued on `stream`, returns without waiting; nothing is read back."""
+        opt = lambda a: L.ptr(int(a)) if a else None  # noqa: E731
+        L.check(L.lib().pcgx_kdtree_dbscan_dev(
+            self._h, float(radius), int(MinPts), int(MinSize), int(MaxSize), opt(d_labels), opt(d_n_clusters),
+            opt(d_sizes), opt(d_ids), opt(d_kind), L.ptr(stream) if stream else None))
 
     # -- extension (no reference parity): group geometry, the moments, boxes and planes of a grouped id list
     def GroupStats(self, ids, sizes):

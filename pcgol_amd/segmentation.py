@@ -163,7 +163,42 @@ class RegionGrowing:
         return out[: cnt.value].copy()
 
 
-class ClusterExtraction:
+class _Grouped:
+    """What ClusterExtraction and DBSCAN share: Extract() splits one grouped id list, Boxes() and Footprints() pass it on.
+    A subclass says in _run() which call makes the list -> (labels, sizes, ids)."""
+    search = labels = sizes = ids = None
+
+    New = classmethod(lambda cls, search, *a, **k: cls(search, *a, **k))
+
+    def SetMinClusterSize(self, n):
+        self.min_size = int(n)
+
+    def SetMaxClusterSize(self, n):
+        """0: no upper limit"""
+        self.max_size = int(n)
+
+    def Extract(self):
+        """-> [ids of cluster 0, ids of cluster 1, ...]; .labels and .sizes hold the call's other two results"""
+        self.labels, self.sizes, self.ids = self._run()
+        return np.split(self.ids, np.cumsum(self.sizes)[:-1]) if len(self.sizes) else []
+
+    def Boxes(self):
+        """After Extract(): the geometry of the extracted clusters, one row each -> KDTree.GroupStats' tuple (count,
+        aabb, centroid, cov, eig, axes, obb): a centre, a box to track, a plane to test."""
+        if self.sizes is None:
+            raise RuntimeError("Boxes() needs Extract() first")
+        return self.search.GroupStats(self.ids, self.sizes)
+
+    def Footprints(self):
+        """After Extract(): what the extracted clusters stand on, one row each -> KDTree.GroupHulls' tuple (hull_sizes,
+        hull_ids, area, rect): the exact convex hull of a cluster's (x, y) and the smallest upright rectangle with a side
+        along one of its edges."""
+        if self.sizes is None:
+            raise RuntimeError("Footprints() needs Extract() first")
+        return self.search.GroupHulls(self.ids, self.sizes)
+
+
+class ClusterExtraction(_Grouped):
     """Cluster extraction in PCL's vocabulary (EuclideanClusterExtraction; with normals, its smooth variant), over
     KDTree.Clusters (extension: no reference parity; include/pcgx.h, "clusters").  search: a pcgol_amd KDTree.
 
@@ -180,17 +215,8 @@ class ClusterExtraction:
         self.min_cos, self.oriented, self.max_curvature = 0.0, False, 0.0
         self.labels = self.sizes = self.ids = None
 
-    New = classmethod(lambda cls, search, *a, **k: cls(search, *a, **k))
-
     def SetClusterTolerance(self, tolerance):
         self.tolerance = float(tolerance)
-
-    def SetMinClusterSize(self, n):
-        self.min_size = int(n)
-
-    def SetMaxClusterSize(self, n):
-        """0: no upper limit"""
-        self.max_size = int(n)
 
     def SetInputNormals(self, Normals, MinCos=0.0, Oriented=False):
         """an edge also needs |n_i . n_j| >= MinCos (n_i . n_j when Oriented); None: Euclidean clustering again"""
@@ -204,25 +230,36 @@ class ClusterExtraction:
         """a point whose curvature is above MaxCurvature (or NaN) belongs to no cluster; None: no such test"""
         self.curvature, self.max_curvature = Curvature, float(MaxCurvature)
 
-    def Extract(self):
-        """-> [ids of cluster 0, ids of cluster 1, ...]; .labels and .sizes hold the call's other two results"""
-        self.labels, self.sizes, ids = self.search.Clusters(
+    def _run(self):
+        return self.search.Clusters(
             self.tolerance, Normals=self.normals, MinCos=self.min_cos, Oriented=self.oriented, Curvature=self.curvature,
             MaxCurvature=self.max_curvature, MinSize=self.min_size, MaxSize=self.max_size)
-        self.ids = ids
-        return np.split(ids, np.cumsum(self.sizes)[:-1]) if len(self.sizes) else []
 
-    def Boxes(self):
-        """After Extract(): the geometry of the extracted clusters, one row each -> KDTree.GroupStats' tuple (count,
-        aabb, centroid, cov, eig, axes, obb): a centre, a box to track, a plane to test."""
-        if self.sizes is None:
-            raise RuntimeError("Boxes() needs Extract() first")
-        return self.search.GroupStats(self.ids, self.sizes)
 
-    def Footprints(self):
-        """After Extract(): what the extracted clusters stand on, one row each -> KDTree.GroupHulls' tuple (hull_sizes,
-        hull_ids, area, rect): the exact convex hull of a cluster's (x, y) and the smallest upright rectangle with a side
-        along one of its edges."""
-        if self.sizes is None:
-            raise RuntimeError("Footprints() needs Extract() first")
-        return self.search.GroupHulls(self.ids, self.sizes)
+class DBSCAN(_Grouped):
+    """Density clustering in Open3D's and scikit-learn's vocabulary, over KDTree.DBSCAN (extension: no reference parity;
+    include/pcgx.h, "density clusters").  search: a pcgol_amd KDTree.
+
+        db = DBSCAN(tree, Eps=0.05, MinPoints=10)
+        for ids in db.Extract(): ...
+
+    A point with at least MinPoints points within Eps (itself included) is core; a cluster is a component of core points
+    plus the border points beside it, each with its nearest core neighbour.  The clusters come largest first, equal sizes
+    by smallest id, each as ascending int64 ids; .kind says per point 0 noise, 1 border, 2 core."""
+
+    def __init__(self, search, Eps=0.0, MinPoints=1, MinClusterSize=1, MaxClusterSize=0):
+        self.search = search
+        self.eps, self.min_points = float(Eps), int(MinPoints)
+        self.min_size, self.max_size = int(MinClusterSize), int(MaxClusterSize)
+        self.labels = self.sizes = self.ids = self.kind = None
+
+    def SetEps(self, eps):
+        self.eps = float(eps)
+
+    def SetMinPoints(self, n):
+        self.min_points = int(n)
+
+    def _run(self):
+        labels, sizes, ids, self.kind = self.search.DBSCAN(self.eps, self.min_points, MinSize=self.min_size,
+                                                           MaxSize=self.max_size)
+        return labels, sizes, ids
