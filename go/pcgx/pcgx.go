@@ -620,6 +620,95 @@ func (k *KDTree) DBSCAN(radius float32, minPts int32, minSize, maxSize int64) (l
 	return labels, sizes, ids[:int(total)], kind, nil
 }
 
+// PlanesParams are the options of (*KDTree).Planes: NHyp hypotheses a round and at most MaxPlanes rounds; a round's best
+// needs max(MinInliers, 3) inliers; Axis (nil: none): only planes whose normal has |cos| >= MinAxisCos with it; Normals
+// (nil: none; 3 per point): an inlier's normal has |cos| >= MinNormalCos with the plane's; Refine: one least-squares
+// refit of the best to its inliers, kept where it loses no inlier.
+type PlanesParams struct {
+	NHyp         int64
+	MaxPlanes    int32
+	MinInliers   int64
+	Axis         *[3]float32
+	MinAxisCos   float32
+	Normals      []float32
+	MinNormalCos float32
+	Refine       bool
+}
+
+// PlaneSegments is the result of (*KDTree).Planes: Planes holds (nx, ny, nz, d) per plane found, Sizes, Refined and Best
+// one entry per plane, Labels per point the plane that took it or -1, IDs the inliers plane by plane (ascending inside
+// a plane): Sizes and IDs are a grouped list for GroupStats and GroupHulls.
+type PlaneSegments struct {
+	Planes  []float32
+	Sizes   []int64
+	Refined []int32
+	Best    []int64
+	Labels  []int64
+	IDs     []int64
+}
+
+// Planes segments the tree's live points into planes (extension: no reference parity; include/pcgx.h,
+// pcgx_kdtree_planes): the plane most points lie within maxDist of, by sample consensus over the caller's random words
+// (samples: 3 per hypothesis and round, 3 * NHyp * MaxPlanes in all), its inliers taken out, then the next.
+func (k *KDTree) Planes(maxDist float32, samples []uint32, p PlanesParams) (*PlaneSegments, error) {
+	runtime.LockOSThread() // the error text is thread-local on the C side: call and pcgx_last_error on one OS thread
+	defer runtime.UnlockOSThread()
+	defer runtime.KeepAlive(k) // the finalizer must not free the handle while a call is in flight
+	var ln C.int64_t
+	if err := status(C.pcgx_kdtree_len(k.t.h, &ln)); err != nil {
+		return nil, err
+	}
+	n := int(ln)
+	if p.Normals != nil && len(p.Normals) != 3*n {
+		return nil, errors.New("pcgx: one normal per point of the tree is required")
+	}
+	if p.NHyp > 0 && p.MaxPlanes > 0 && int64(len(samples)) != 3*p.NHyp*int64(p.MaxPlanes) {
+		return nil, errors.New("pcgx: three sample words per hypothesis and round are required")
+	}
+	mp := int(p.MaxPlanes)
+	if mp < 1 {
+		mp = 1 // (the call refuses MaxPlanes < 1; the outputs must exist all the same)
+	}
+	r := &PlaneSegments{Planes: make([]float32, 4*mp), Sizes: make([]int64, mp), Refined: make([]int32, mp),
+		Best: make([]int64, mp), Labels: make([]int64, n+1), IDs: make([]int64, n+1)}
+	var smp *C.uint32_t
+	if len(samples) > 0 {
+		smp = (*C.uint32_t)(unsafe.Pointer(&samples[0]))
+	}
+	var axis, nrm *C.float
+	if p.Axis != nil {
+		axis = (*C.float)(unsafe.Pointer(&p.Axis[0]))
+	}
+	if len(p.Normals) > 0 {
+		nrm = (*C.float)(unsafe.Pointer(&p.Normals[0]))
+	}
+	refine := C.int32_t(0)
+	if p.Refine {
+		refine = 1
+	}
+	var c C.int64_t
+	rc := C.pcgx_kdtree_planes(k.t.h, smp, C.int64_t(p.NHyp), C.int32_t(p.MaxPlanes), C.float(maxDist), C.int64_t(p.MinInliers),
+		axis, C.float(p.MinAxisCos), nrm, C.float(p.MinNormalCos), refine, &c, (*C.float)(unsafe.Pointer(&r.Planes[0])),
+		(*C.int64_t)(unsafe.Pointer(&r.Sizes[0])), (*C.int32_t)(unsafe.Pointer(&r.Refined[0])),
+		(*C.int64_t)(unsafe.Pointer(&r.Best[0])), (*C.int64_t)(unsafe.Pointer(&r.Labels[0])),
+		(*C.int64_t)(unsafe.Pointer(&r.IDs[0])), nil, nil, nil)
+	runtime.KeepAlive(samples)
+	runtime.KeepAlive(p.Normals)
+	runtime.KeepAlive(p.Axis)
+	runtime.KeepAlive(r)
+	if err := status(rc); err != nil {
+		return nil, err
+	}
+	found := int(c)
+	total := int64(0)
+	for _, s := range r.Sizes[:found] {
+		total += s
+	}
+	r.Planes, r.Sizes, r.Refined, r.Best = r.Planes[:4*found], r.Sizes[:found], r.Refined[:found], r.Best[:found]
+	r.Labels, r.IDs = r.Labels[:n], r.IDs[:int(total)]
+	return r, nil
+}
+
 // GroupGeometry is the result of (*KDTree).GroupStats, one row per group: Count of live members; AABB lo x, y, z then
 // hi x, y, z; Centroid; Cov in the order xx, xy, xz, yy, yz, zz; Eig descending; Axes: the three unit eigenvectors as
 // rows (axis 2 is the fitted plane's normal); OBB: centre x, y, z, then the half-extents along the axes.  A group

@@ -1299,6 +1299,86 @@ PCGX_API pcgx_status pcgx_pose_from_correspondences_dev(const float *d_src_xyz, 
  * across. */
 PCGX_API int32_t pcgx_pose_tile(void);
 
+/* ------------------------------------------- planes (extension: no reference parity)
+ * NOT in the reference (its plane detector is the voxel-grid surface patch, pcgx_sac_plane_compute).  Plane segmentation
+ * as Open3D's segment_plane or PCL's SACSegmentation in a loop with ExtractIndices: the infinite plane most points lie
+ * within max_dist of, optionally roughly perpendicular to an axis and agreeing with the points' normals; its inliers are
+ * taken out and the next plane is looked for, up to max_planes times.  As in pcgx_pose_from_correspondences the caller
+ * draws every random word first; one call fits and scores all hypotheses of every round, the first best of a round wins.
+ * This comment is the contract, tests/plane_oracle.py restates it.
+ *   pcgx_kdtree_planes    (t, samples[3 n_hyp max_planes] u32, n_hyp, max_planes, max_dist, min_inliers,
+ *                          axis[3] | NULL, min_axis_cos, normals[3 Len()] | NULL, min_normal_cos, refine,
+ *                          n_planes*, planes[4 max_planes] f32, sizes[max_planes] i64, refined[max_planes] i32,
+ *                          best[max_planes] i64, labels[Len()] i64, ids[Len()] i64 | NULL,
+ *                          status[max_planes n_hyp] i32 | NULL, counts[...] i64 | NULL, hyp_planes[4 ...] f32 | NULL)
+ *   pcgx_kdtree_planes_dev(... every array device resident, ids / sizes / labels / counts / best int32,
+ *                          d_n_planes one int32, stream)
+ * Live point: not deleted (pcgx_kdtree_delete_point[s]), its three coordinates finite and, with normals != NULL, its three
+ *   normal components finite and not all zero (the zero normal is pcgx_kdtree_normals' answer for a degenerate
+ *   neighbourhood).  A point that is not live is never sampled and never an inlier; its label is -1.
+ * Rounds: A_0 = the live ids in ascending order, R_r = |A_r|.  Round r runs iff r < max_planes, every earlier round
+ *   found a plane and R_r >= 3.  Hypothesis h of round r uses samples[3 (r n_hyp + h) + j], j = 0, 1, 2; word u names the
+ *   point A_r[(uint64(u) * R_r) >> 32], computed on the device: one sample array serves both forms.
+ * Hypothesis, in this order: status 1 (bad sample): two of the three indices are equal.  Status 2 (degenerate): the
+ *   triangle test of pcgx_pose_from_correspondences on the three points (the same expression, the same 1e-12).  Status 3
+ *   (axis): `axis` is given and the plane fails the axis test.  Status 0 otherwise.  A rejected hypothesis has count 0 and
+ *   a zero plane; the rows of a round that did not run hold status -1, count 0 and a zero plane.
+ * Plane of a status-0 hypothesis, in float64 from the float32 points, each operation rounded once, nothing contracted:
+ *   e1 = p1 - p0, e2 = p2 - p0, c = e1 x e2, n = c / sqrt((cx cx + cy cy) + cz cz).  Axis test, on this n:
+ *   |(nx ax + ny ay) + nz az| >= (double)min_axis_cos * |a|, |a| = sqrt((ax ax + ay ay) + az az) in float64 from the
+ *   float32 axis.  Sign: with an axis n is turned so that (nx ax + ny ay) + nz az >= 0; where that expression is 0, and
+ *   without an axis, so that its component of largest magnitude is positive, the first such component on a tie (the rule
+ *   of pcgx_kdtree_group_stats' axes).  d = -((nx p0x + ny p0y) + nz p0z).  The four numbers are rounded once to float32.
+ * Inlier of plane (n, d): a point of A_r with fabsf(((nx px + ny py) + nz pz) + d) < max_dist, all float32, nothing
+ *   fused, the comparison strict; with normals also fabsf((nx mx + ny my) + nz mz) >= min_normal_cos for the point's
+ *   normal m as given.  A NaN is not an inlier.  Given the plane's bits the count has no tolerance.
+ * Best of a round: the status-0 hypothesis with the largest count, the smallest h among equals.  The round FINDS a plane
+ *   iff that count >= max(min_inliers, 3); otherwise this round and all later ones did not.  n_planes = the number of
+ *   rounds that found one.
+ * Refinement (refine != 0, the round found a plane): I = the best's inliers in ascending id.  The refitted plane has the
+ *   centroid c and axis 2, a, that pcgx_kdtree_group_stats returns for the one-group list I (the same kernels: the same
+ *   bits); a is signed by the rule above, n = float32(a), d = float32(-((ax cx + ay cy) + az cz)) in float64.  No refit
+ *   when group geometry answers the degenerate frame (eig[0] is not > 0) or the refitted normal fails the axis test.  The
+ *   points of A_r are counted again under the refitted plane; it replaces the hypothesis's iff its count >= the best's
+ *   count: then refined[r] = 1 and the round's inliers are its own.  One refit, not an iteration.
+ * Outputs: planes[4 r ..] the kept plane, best[r] the winning h, sizes[r] the kept plane's inlier count, labels[i] the
+ *   round that took point i or -1, ids: round 0's inliers ascending, then round 1's, ..., -1 in the remaining slots (what
+ *   pcgx_kdtree_group_stats[_dev] and pcgx_kdtree_group_hulls[_dev] take, with sizes and n_planes).  From n_planes on,
+ *   sizes, planes and refined are 0 and best is -1.  A_{r+1} = A_r minus the inliers of round r's kept plane.  Every row
+ *   of every output is written on every call.
+ * PCGX_E_INVALID (nothing is written): a NULL tree, n_hyp < 0, max_planes outside [1, 256], max_dist not finite or not
+ *   > 0, min_inliers < 0, an axis that is not finite or all zero, min_axis_cos (with an axis) or min_normal_cos (with
+ *   normals) outside [0, 1] or NaN, NULL samples with n_hyp > 0, a NULL mandatory output (labels only where Len() > 0),
+ *   n_hyp * max_planes above 2^31 - 1.  n_hyp == 0 or Len() == 0 is PCGX_OK with n_planes = 0.
+ * Always computed on the device (csrc/planes.hip).  The same input gives the same bits on every call: no float atomic
+ *   anywhere, counts are added by integer atomics.  The points are split into chunks to fill the chip (the library's
+ *   choice; PCGX_PLANES_SPLIT=<n> in the environment, read per call, forces it -- any n gives the same bits). */
+PCGX_API pcgx_status pcgx_kdtree_planes(const pcgx_kdtree *t, const uint32_t *samples /* [3 n_hyp max_planes] */,
+                                        int64_t n_hyp, int32_t max_planes, float max_dist, int64_t min_inliers,
+                                        const float *axis /* [3] or NULL */, float min_axis_cos,
+                                        const float *normals /* [3 Len()] or NULL */, float min_normal_cos, int32_t refine,
+                                        int64_t *n_planes, float *planes, int64_t *sizes, int32_t *refined, int64_t *best,
+                                        int64_t *labels, int64_t *ids /* may be NULL */, int32_t *status /* may be NULL */,
+                                        int64_t *counts /* may be NULL */, float *hyp_planes /* may be NULL */);
+/* Same, every array device resident (`axis` alone stays three floats in HOST memory: it is an argument, checked before
+ * anything is enqueued), enqueued on `stream` (NULL: the library's); returns without waiting and reads nothing back.
+ * Ids, sizes, labels, counts and best are int32, d_n_planes is one int32.  All max_planes rounds are enqueued at once; a
+ * round reads from device words how many points are left and whether an earlier round failed.  d_ids, d_sizes and
+ * d_n_planes can be passed on to pcgx_kdtree_group_stats_dev and pcgx_kdtree_group_hulls_dev as they are (cap_ids =
+ * Len(), cap_groups = max_planes).  A handle with deleted points has its deleted flags copied to the device first, and
+ * that copy alone is waited for. */
+PCGX_API pcgx_status pcgx_kdtree_planes_dev(const pcgx_kdtree *t, const uint32_t *d_samples, int64_t n_hyp,
+                                            int32_t max_planes, float max_dist, int64_t min_inliers,
+                                            const float *axis /* HOST [3] or NULL */, float min_axis_cos,
+                                            const float *d_normals /* may be NULL */, float min_normal_cos, int32_t refine,
+                                            int32_t *d_n_planes, float *d_planes, int32_t *d_sizes, int32_t *d_refined,
+                                            int32_t *d_best, int32_t *d_labels, int32_t *d_ids /* may be NULL */,
+                                            int32_t *d_status /* may be NULL */, int32_t *d_counts /* may be NULL */,
+                                            float *d_hyp_planes /* may be NULL */, void *stream);
+/* Hypotheses per workgroup of the count kernel (a wave, two hypotheses per lane): the boundary the tests put n_hyp
+ * across. */
+PCGX_API int32_t pcgx_planes_tile(void);
+
 /* ------------------------------------------- score poses (extension: no reference parity)
  * NOT in the reference.  pcgx_pose_from_correspondences picks its pose by the inliers among the CORRESPONDENCES; on a
  * scene with repeated structure a wrong pose can collect more of them than the right one.  This call counts, for each of

@@ -163,5 +163,10 @@ void group_scan_launch(const int32_t *d_sizes, const int32_t *d_n_groups, int32_
 // ... and grp[slot] = the slot's group (-1 from the list's clipped end on) over slot_tiles whole tiles, from the offsets
 void group_map_launch(const int32_t *off, const int32_t *d_n_groups, int32_t cap_groups, int32_t *grp, unsigned slot_tiles,
                       hipStream_t st);
+// ... and group geometry itself for a caller inside a call of its own (planes.hip): centroid [3], eig [3] and axes [9]
+// per group, the bits pcgx_kdtree_group_stats_dev gives; Len() > 0, cap_groups > 0; the temporaries come from
+// ctx().arena WITHOUT restarting it
+pcgx_status group_frames_enqueue(const pcgx_kdtree *t, const int32_t *d_ids, int64_t cap_ids, const int32_t *d_sizes,
+                                 int64_t cap_groups, double *d_centroid, double *d_eig, double *d_axes, hipStream_t st);
 
 }  // namespace pcgx

@@ -412,9 +412,10 @@ static pcgx_status gs_zero_outputs(const GroupOut &O, int64_t cap_groups, hipStr
 
 // Len() > 0, cap_groups > 0, everything device resident; temporaries from ctx().arena
 static pcgx_status group_stats_enqueue(const pcgx_kdtree *t, const int32_t *d_ids, int64_t cap_ids, const int32_t *d_sizes,
-                                       int64_t cap_groups, const int32_t *d_n_groups, const GroupOut &O, hipStream_t st) {
+                                       int64_t cap_groups, const int32_t *d_n_groups, const GroupOut &O, hipStream_t st,
+                                       bool restart = true) {
   Arena &ar = ctx().arena;
-  PCGX_TRY(ar.begin(st));
+  if (restart) PCGX_TRY(ar.begin(st));
   const uint32_t *inv = nullptr;
   PCGX_TRY(range_inverse_map(t, &inv, st));
   const int64_t entries = cap_groups + 1;
@@ -456,6 +457,12 @@ static pcgx_status group_stats_enqueue(const pcgx_kdtree *t, const int32_t *d_id
   }
   PCGX_HIP_TRY(hipGetLastError());
   return PCGX_OK;
+}
+
+pcgx_status group_frames_enqueue(const pcgx_kdtree *t, const int32_t *d_ids, int64_t cap_ids, const int32_t *d_sizes,
+                                 int64_t cap_groups, double *d_centroid, double *d_eig, double *d_axes, hipStream_t st) {
+  const GroupOut O{nullptr, nullptr, d_centroid, nullptr, d_eig, d_axes, nullptr};
+  return group_stats_enqueue(t, d_ids, cap_ids, d_sizes, cap_groups, nullptr, O, st, false);
 }
 
 }  // namespace pcgx

@@ -72,6 +72,16 @@ class Arena {
     return alloc(count * sizeof(T), (void **)out);
   }
   void release_all();
+  // A caller that enqueues the same callee several times in one call (planes.hip: group geometry once per round) takes a
+  // mark before and rewinds behind it: the callee's temporaries are handed out again, and the stream orders their
+  // users.  Nothing is given back where the callee made the arena add a block.
+  struct Mark {
+    size_t blocks, used;
+  };
+  Mark mark() const { return Mark{blocks_.size(), blocks_.empty() ? 0 : blocks_.back().used}; }
+  void rewind(const Mark &m) {
+    if (m.blocks && blocks_.size() == m.blocks) blocks_.back().used = m.used;
+  }
   // `count` zeroed words that LIVE ACROSS calls (same ordering rules as the temporaries: touched only behind begin()):
   // counters a call's kernels leave at zero again for the next call -- a hipMemsetAsync per call is a launch of its
   // own (4.5 us at the head of a 0.11 ms Nearest batch).  One region per arena; `count` may not grow.

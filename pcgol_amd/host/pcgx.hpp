@@ -328,6 +328,51 @@ class KDTree {  // pc/storage/kdtree/kdtree.go:14-23
     r.ids.resize(total);
     return r;
   }
+  // Plane segmentation (extension: no reference parity; include/pcgx.h, pcgx_kdtree_planes): the plane most live points
+  // lie within maxDist of, by sample consensus over the caller's random words (samples: 3 per hypothesis and round,
+  // nHyp * maxPlanes hypotheses), its inliers taken out, then the next, until a round's best has fewer than
+  // max(minInliers, 3).  axis (nullptr: none): only planes whose normal has |cos| >= minAxisCos with it; normals (empty:
+  // none): an inlier's normal has |cos| >= minNormalCos with the plane's.  labels, sizes and ids as Clusters (a
+  // PlanesResult is a ClustersResult: GroupStats and GroupHulls take it), one group a plane in the order found; planes:
+  // (nx, ny, nz, d) per plane; refined, best: per plane; status, counts, hypPlanes: per round and hypothesis.
+  struct PlanesResult : ClustersResult {
+    std::vector<float> planes, hypPlanes;
+    std::vector<int32_t> refined, status;
+    std::vector<int64_t> best, counts;
+  };
+  PlanesResult Planes(float maxDist, const std::vector<uint32_t> &samples, int64_t nHyp, int32_t maxPlanes = 1,
+                      int64_t minInliers = 3, const float *axis = nullptr, float minAxisCos = 0.0f,
+                      const std::vector<Vec3> &normals = {}, float minNormalCos = 0.0f, bool refine = true) const {
+    const int64_t n = Len();
+    if (!normals.empty() && (int64_t)normals.size() != n)
+      throw Error(PCGX_E_INVALID, "one normal per point of the tree is required");
+    if (nHyp > 0 && maxPlanes > 0 && (int64_t)samples.size() != 3 * nHyp * maxPlanes)
+      throw Error(PCGX_E_INVALID, "three sample words per hypothesis and round are required");
+    const size_t mp = maxPlanes > 0 ? (size_t)maxPlanes : 0, rows = nHyp > 0 ? mp * (size_t)nHyp : 0;
+    PlanesResult r;
+    r.labels.resize((size_t)n);
+    r.ids.resize((size_t)n);
+    r.sizes.resize(mp);
+    r.planes.resize(4 * mp);
+    r.refined.resize(mp);
+    r.best.resize(mp);
+    r.status.resize(rows);
+    r.counts.resize(rows);
+    r.hypPlanes.resize(4 * rows);
+    int64_t c = 0;
+    check(pcgx_kdtree_planes(h_.get(), samples.empty() ? nullptr : samples.data(), nHyp, maxPlanes, maxDist, minInliers, axis,
+                             minAxisCos, normals.empty() ? nullptr : normals[0].data(), minNormalCos, refine ? 1 : 0, &c,
+                             r.planes.data(), r.sizes.data(), r.refined.data(), r.best.data(), r.labels.data(), r.ids.data(),
+                             r.status.data(), r.counts.data(), r.hypPlanes.data()));
+    r.sizes.resize((size_t)c);
+    r.planes.resize(4 * (size_t)c);
+    r.refined.resize((size_t)c);
+    r.best.resize((size_t)c);
+    size_t total = 0;
+    for (int64_t s : r.sizes) total += (size_t)s;
+    r.ids.resize(total);
+    return r;
+  }
   // Group geometry (extension: no reference parity; include/pcgx.h, pcgx_kdtree_group_stats): per group of a grouped id
   // list over the tree's own points -- ids: group 0's members, then group 1's, ...; sizes: per group; what Clusters
   // returns -- the count of live members, the axis-aligned box (lo xyz, hi xyz), centroid and covariance (xx, xy, xz,

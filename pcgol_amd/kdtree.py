@@ -1,8 +1,8 @@
 """pc/storage/kdtree mirror: KDTree on the GPU behind the storage.Search shape
 (pc/storage/search.go:13-17): Vec3At / Len / Nearest, plus batched NearestBatch, and extensions with no
 reference counterpart: surface normals (Normals), moving-least-squares smoothing (MLS), FPFH descriptors
-(FPFH, FPFHAt), keypoints (LocalMaxima, ISSKeypoints), cluster extraction (Clusters), density clusters (DBSCAN), per-group geometry
-(GroupStats), k nearest neighbours (KNearest) and their covariances (Covariances)."""
+(FPFH, FPFHAt), keypoints (LocalMaxima, ISSKeypoints), cluster extraction (Clusters), density clusters (DBSCAN), plane segmentation (Planes), per-group
+geometry (GroupStats), k nearest neighbours (KNearest) and their covariances (Covariances)."""
 import collections
 import ctypes as C
 
@@ -25,6 +25,15 @@ class Neighbor:  # pc/storage/search.go:8-11
 
 GroupGeometry = collections.namedtuple("GroupGeometry", "count aabb centroid cov eig axes obb")  # KDTree.GroupStats
 GroupFootprints = collections.namedtuple("GroupFootprints", "hull_sizes hull_ids area rect")  # KDTree.GroupHulls
+
+
+PlaneSegments = collections.namedtuple("PlaneSegments",  # KDTree.Planes
+                                       "n_planes planes sizes refined best labels ids status counts hyp_planes")
+
+
+def PlanesTile():
+    """Hypotheses per workgroup of Planes' count kernel (the boundary the tests put NHyp across)."""
+    return int(L.lib().pcgx_planes_tile())
 
 
 def GroupHullsChunk():
@@ -463,6 +472,77 @@ class KDTree:
         L.check(L.lib().pcgx_kdtree_group_hulls_dev(
             self._h, opt(d_ids), int(cap_ids), opt(d_sizes), int(cap_groups), opt(d_n_groups), opt(d_hull_sizes),
             opt(d_hull_ids), opt(d_area), opt(d_rect), L.ptr(stream) if stream else None))
+
+    # -- extension (no reference parity): plane segmentation, consensus planes peeled one by one
+    def Planes(self, MaxDist, NHyp=256, MaxPlanes=1, MinInliers=3, Axis=None, MinAxisCos=0.0, Normals=None,
+               MinNormalCos=0.0, Refine=True, Samples=None, Seed=0):
+        """The plane most of the tree's live points lie within MaxDist of, by sample consensus over NHyp three-point
+        hypotheses; its inliers are taken out and the next plane is looked for, up to MaxPlanes times, until a round's
+        best has fewer than max(MinInliers, 3) inliers -> PlaneSegments(n_planes, planes float32 (MaxPlanes, 4) as
+        (nx, ny, nz, d), sizes int64, refined int32, best int64, labels int64 (n,), ids int64 (sum(sizes),), status
+        int32 (MaxPlanes, NHyp), counts int64, hyp_planes float32 (MaxPlanes, NHyp, 4)).  Axis: only planes whose
+        normal has |cos| >= MinAxisCos with it; Normals (n, 3): an inlier's normal has |cos| >= MinNormalCos with the
+        plane's, and a point with a zero or non-finite normal takes no part; Refine: the best is refitted once to its
+        inliers by GroupStats' least-squares plane and kept where that loses no inlier.  Samples: uint32 (MaxPlanes,
+        NHyp, 3) random words, drawn from np.random.default_rng(Seed) when None (include/pcgx.h, pcgx_kdtree_planes)."""
+        n, nh, mp = self.Len(), int(NHyp), int(MaxPlanes)
+        if Samples is None:
+            Samples = np.random.default_rng(Seed).integers(0, 2 ** 32, (max(mp, 0), max(nh, 0), 3),
+                                                           dtype=np.uint64).astype(np.uint32)
+        smp = np.ascontiguousarray(Samples, np.uint32).reshape(-1)
+        if nh > 0 and mp > 0 and len(smp) != 3 * nh * mp:
+            raise ValueError("three sample words per hypothesis and round are required")
+        nrm = axis = None
+        if Normals is not None:
+            nrm = L.f32c(Normals).reshape(-1, 3)
+            if len(nrm) != n:
+                raise ValueError("one normal per point of the tree is required")
+        if Axis is not None:
+            axis = L.f32c(Axis).reshape(3)
+        rows = max(nh, 0) * max(mp, 0)
+        out = PlaneSegments(0, np.zeros((max(mp, 0), 4), np.float32), np.zeros(max(mp, 0), np.int64),
+                            np.zeros(max(mp, 0), np.int32), np.full(max(mp, 0), -1, np.int64), np.full(n, -1, np.int64),
+                            np.full(n, -1, np.int64), np.full(rows, -1, np.int32), np.zeros(rows, np.int64),
+                            np.zeros((rows, 4), np.float32))
+        cnt = C.c_int64()
+        opt = lambda a: L.ptr(a) if a is not None and a.size else None  # noqa: E731
+        L.check(L.lib().pcgx_kdtree_planes(
+            self._h, opt(smp), nh, mp, float(MaxDist), int(MinInliers), opt(axis), float(MinAxisCos),
+            L.ptr(nrm) if nrm is not None else None, float(MinNormalCos), int(bool(Refine)), C.byref(cnt),
+            opt(out.planes), opt(out.sizes), opt(out.refined), opt(out.best), opt(out.labels), opt(out.ids),
+            opt(out.status), opt(out.counts), opt(out.hyp_planes)))
+        k = int(out.sizes[:cnt.value].sum())
+        return out._replace(n_planes=int(cnt.value), ids=out.ids[:k], status=out.status.reshape(mp, nh),
+                            counts=out.counts.reshape(mp, nh), hyp_planes=out.hyp_planes.reshape(mp, nh, 4))
+
+    def PlanesDev(self, MaxDist, d_samples, NHyp, d_n_planes, d_planes, d_sizes, d_refined, d_best, d_labels, d_ids=0,
+                  d_status=0, d_counts=0, d_hyp_planes=0, MaxPlanes=1, MinInliers=3, Axis=None, MinAxisCos=0.0,
+                  d_normals=0, MinNormalCos=0.0, Refine=True, stream=0):
+        """Device-resident Planes: raw device addresses (e.g. torch .data_ptr()); d_samples uint32 [3 NHyp MaxPlanes],
+        d_n_planes one int32, d_planes float32 [4 MaxPlanes], d_sizes / d_refined / d_best int32 [MaxPlanes], d_labels
+        int32 [Len()], d_ids int32 [Len()] (the inliers plane by plane, then -1), d_status / d_counts int32 [MaxPlanes
+        NHyp], d_hyp_planes float32 [4 MaxPlanes NHyp], d_normals float32 [3 Len()] (what NormalsDev writes); Axis stays
+        a host value.  Enqueued on `stream`, returns without waiting; nothing is read back: every round is enqueued at
+        once and reads from device words what the rounds before it left.  d_ids, d_sizes and d_n_planes are a grouped
+        list for GroupStatsDev and GroupHullsDev (cap_ids = Len(), cap_groups = MaxPlanes).
+
+        What is NOT on a plane, clustered without a rebuild, all on one stream and with nothing read back:
+
+            t.PlanesDev(0.02, smp.data_ptr(), 256, n_planes.data_ptr(), planes.data_ptr(), sizes.data_ptr(),
+                        refined.data_ptr(), best.data_ptr(), labels.data_ptr(), d_ids=ids.data_ptr(), MaxPlanes=4,
+                        MinInliers=500, stream=s)
+            with torch.cuda.stream(stream):              # the torch stream that wraps s
+                on_plane = (labels >= 0).float()         # 1.0 on a plane, 0.0 off it
+            t.ClustersDev(0.1, c_labels.data_ptr(), c_n.data_ptr(), d_curvature=on_plane.data_ptr(), MaxCurvature=0.5,
+                          stream=s)                      # a point "above MaxCurvature" is unusable: the planes' points
+        """
+        opt = lambda a: L.ptr(int(a)) if a else None  # noqa: E731
+        axis = L.f32c(Axis).reshape(3) if Axis is not None else None
+        L.check(L.lib().pcgx_kdtree_planes_dev(
+            self._h, opt(d_samples), int(NHyp), int(MaxPlanes), float(MaxDist), int(MinInliers),
+            L.ptr(axis) if axis is not None else None, float(MinAxisCos), opt(d_normals), float(MinNormalCos),
+            int(bool(Refine)), opt(d_n_planes), opt(d_planes), opt(d_sizes), opt(d_refined), opt(d_best), opt(d_labels),
+            opt(d_ids), opt(d_status), opt(d_counts), opt(d_hyp_planes), L.ptr(stream) if stream else None))
 
     # -- extension (no reference parity): k nearest neighbours
     def KNearest(self, p, k, maxRange):

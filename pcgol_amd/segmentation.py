@@ -263,3 +263,59 @@ class DBSCAN(_Grouped):
         labels, sizes, ids, self.kind = self.search.DBSCAN(self.eps, self.min_points, MinSize=self.min_size,
                                                            MaxSize=self.max_size)
         return labels, sizes, ids
+
+
+class PlaneSegmentation(_Grouped):
+    """Plane segmentation in PCL's vocabulary (SACSegmentation with SACMODEL_PLANE / PERPENDICULAR_PLANE / NORMAL_PLANE,
+    run in a loop with ExtractIndices), over KDTree.Planes (extension: no reference parity; include/pcgx.h, "planes").
+    search: a pcgol_amd KDTree.
+
+        ps = PlaneSegmentation(tree, DistanceThreshold=0.02, MaxPlanes=4, MinInliers=500)
+        ps.SetAxis((0, 0, 1)); ps.SetEpsAngle(np.radians(10))      # the floor first: only planes within 10 degrees of it
+        for ids in ps.Extract(): ...                               # ps.planes[k] = (nx, ny, nz, d) of plane k
+
+    The planes come in the order they were found (the one with most inliers among what is left), each as ascending int64
+    ids; Boxes() and Footprints() give their geometry.  .result holds everything KDTree.Planes returned."""
+
+    def __init__(self, search, DistanceThreshold=0.0, MaxPlanes=1, MinInliers=3, MaxIterations=256, Refine=True, Seed=0):
+        self.search = search
+        self.max_dist, self.max_planes, self.min_inliers = float(DistanceThreshold), int(MaxPlanes), int(MinInliers)
+        self.n_hyp, self.refine, self.seed = int(MaxIterations), bool(Refine), Seed
+        self.axis, self.min_axis_cos = None, 0.0
+        self.normals, self.min_normal_cos = None, 0.0
+        self.labels = self.sizes = self.ids = self.planes = self.result = None
+
+    def SetDistanceThreshold(self, d):
+        self.max_dist = float(d)
+
+    def SetMaxIterations(self, n):
+        """hypotheses a round draws (all of them are scored: there is no early stop)"""
+        self.n_hyp = int(n)
+
+    def SetMaxPlanes(self, n):
+        self.max_planes = int(n)
+
+    def SetMinInliers(self, n):
+        self.min_inliers = int(n)
+
+    def SetAxis(self, axis):
+        """only planes whose normal lies within the angle of SetEpsAngle of this axis (PCL's perpendicular plane: the
+        plane is perpendicular to the axis); None: any plane"""
+        self.axis = None if axis is None else np.asarray(axis, np.float32).reshape(3)
+
+    def SetEpsAngle(self, angle):
+        """the largest angle (radians) between a plane's normal and the axis, either way round"""
+        self.min_axis_cos = float(np.cos(angle))
+
+    def SetInputNormals(self, Normals, MinCos=0.0):
+        """an inlier's normal also needs |n . m| >= MinCos with the plane's, and a point with a zero or non-finite
+        normal takes no part; None: distances alone"""
+        self.normals, self.min_normal_cos = Normals, float(MinCos)
+
+    def _run(self):
+        r = self.result = self.search.Planes(
+            self.max_dist, NHyp=self.n_hyp, MaxPlanes=self.max_planes, MinInliers=self.min_inliers, Axis=self.axis,
+            MinAxisCos=self.min_axis_cos, Normals=self.normals, MinNormalCos=self.min_normal_cos, Refine=self.refine,
+            Seed=self.seed)
+        self.planes = r.planes[:r.n_planes]
+        return r.labels, r.sizes[:r.n_planes], r.ids
