@@ -35,6 +35,8 @@ def test_nearest_table_golden(golden):
 @pytest.mark.parametrize("n,ties", [(1, False), (2, False), (3, False), (6, False), (100, False),
                                     (1000, True), (4097, False), (50000, True)])
 def test_build_matches_oracle(n, ties):
+    """Only the 50 000-point case is built on the device; test_gpu_tree_build.py forces the device build at sizes from 2
+    points up (PCGX_BUILD=gpu) and compares it with the host build and the oracle there."""
     rng = np.random.default_rng(n)
     if ties:  # integer grid coordinates: many equal split keys -> exercises the stable order
         pts = rng.integers(0, 8, size=(n, 3)).astype(f32)
