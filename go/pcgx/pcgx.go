@@ -709,6 +709,110 @@ func (k *KDTree) Planes(maxDist float32, samples []uint32, p PlanesParams) (*Pla
 	return r, nil
 }
 
+// The kinds of shape (*KDTree).Shapes looks for.
+const (
+	ShapeSphere   int32 = 0
+	ShapeCylinder int32 = 1
+)
+
+// ShapesParams are the options of (*KDTree).Shapes: NHyp hypotheses a round and at most MaxShapes rounds; a round's best
+// needs max(MinInliers, 2) inliers; SampleRadius: a hypothesis's second point comes out of this radius about its first
+// (0: out of everything left); RMin <= r <= RMax (RMax 0 stands for no upper limit); Axis (nil: none): only cylinders
+// whose axis has |cos| >= MinAxisCos with it; an inlier's normal has |cos| >= MinNormalCos with the shape's; Refine: one
+// least-squares refit of the best's centre and radius to its inliers, kept where it loses no inlier.
+type ShapesParams struct {
+	NHyp         int64
+	MaxShapes    int32
+	MinInliers   int64
+	SampleRadius float32
+	RMin, RMax   float32
+	Axis         *[3]float32
+	MinAxisCos   float32
+	MinNormalCos float32
+	Refine       bool
+}
+
+// ShapeSegments is the result of (*KDTree).Shapes: Shapes holds 8 numbers per shape found, (cx, cy, cz, r, 0, 0, 0, 0)
+// for a sphere and (qx, qy, qz, r, ax, ay, az, 0) for a cylinder (q the axis point nearest the origin); Sizes, Refined
+// and Best one entry per shape, Labels per point the shape that took it or -1, IDs the inliers shape by shape (ascending
+// inside a shape): Sizes and IDs are a grouped list for GroupStats and GroupHulls.
+type ShapeSegments struct {
+	Shapes  []float32
+	Sizes   []int64
+	Refined []int32
+	Best    []int64
+	Labels  []int64
+	IDs     []int64
+}
+
+// Shapes segments the tree's live points into spheres or cylinders (extension: no reference parity; include/pcgx.h,
+// pcgx_kdtree_shapes): the shape most points lie within maxDist of, by sample consensus over hypotheses made from two
+// oriented points drawn by the caller's random words (samples: 2 per hypothesis and round, 2 * NHyp * MaxShapes in all),
+// its inliers taken out, then the next.  normals: 3 per point of the tree.
+func (k *KDTree) Shapes(kind int32, maxDist float32, normals []float32, samples []uint32, p ShapesParams) (*ShapeSegments, error) {
+	runtime.LockOSThread() // the error text is thread-local on the C side: call and pcgx_last_error on one OS thread
+	defer runtime.UnlockOSThread()
+	defer runtime.KeepAlive(k) // the finalizer must not free the handle while a call is in flight
+	var ln C.int64_t
+	if err := status(C.pcgx_kdtree_len(k.t.h, &ln)); err != nil {
+		return nil, err
+	}
+	n := int(ln)
+	if len(normals) != 3*n {
+		return nil, errors.New("pcgx: one normal per point of the tree is required")
+	}
+	if p.NHyp > 0 && p.MaxShapes > 0 && int64(len(samples)) != 2*p.NHyp*int64(p.MaxShapes) {
+		return nil, errors.New("pcgx: two sample words per hypothesis and round are required")
+	}
+	mp := int(p.MaxShapes)
+	if mp < 1 {
+		mp = 1 // (the call refuses MaxShapes < 1; the outputs must exist all the same)
+	}
+	r := &ShapeSegments{Shapes: make([]float32, 8*mp), Sizes: make([]int64, mp), Refined: make([]int32, mp),
+		Best: make([]int64, mp), Labels: make([]int64, n+1), IDs: make([]int64, n+1)}
+	var smp *C.uint32_t
+	if len(samples) > 0 {
+		smp = (*C.uint32_t)(unsafe.Pointer(&samples[0]))
+	}
+	var axis, nrm *C.float
+	if p.Axis != nil {
+		axis = (*C.float)(unsafe.Pointer(&p.Axis[0]))
+	}
+	if len(normals) > 0 {
+		nrm = (*C.float)(unsafe.Pointer(&normals[0]))
+	}
+	refine := C.int32_t(0)
+	if p.Refine {
+		refine = 1
+	}
+	rMax := p.RMax
+	if rMax == 0 {
+		rMax = float32(math.Inf(1))
+	}
+	var c C.int64_t
+	rc := C.pcgx_kdtree_shapes(k.t.h, C.int32_t(kind), smp, C.int64_t(p.NHyp), C.int32_t(p.MaxShapes), C.float(maxDist),
+		C.int64_t(p.MinInliers), C.float(p.SampleRadius), C.float(p.RMin), C.float(rMax), axis, C.float(p.MinAxisCos), nrm,
+		C.float(p.MinNormalCos), refine, &c, (*C.float)(unsafe.Pointer(&r.Shapes[0])),
+		(*C.int64_t)(unsafe.Pointer(&r.Sizes[0])), (*C.int32_t)(unsafe.Pointer(&r.Refined[0])),
+		(*C.int64_t)(unsafe.Pointer(&r.Best[0])), (*C.int64_t)(unsafe.Pointer(&r.Labels[0])),
+		(*C.int64_t)(unsafe.Pointer(&r.IDs[0])), nil, nil, nil)
+	runtime.KeepAlive(samples)
+	runtime.KeepAlive(normals)
+	runtime.KeepAlive(p.Axis)
+	runtime.KeepAlive(r)
+	if err := status(rc); err != nil {
+		return nil, err
+	}
+	found := int(c)
+	total := int64(0)
+	for _, s := range r.Sizes[:found] {
+		total += s
+	}
+	r.Shapes, r.Sizes, r.Refined, r.Best = r.Shapes[:8*found], r.Sizes[:found], r.Refined[:found], r.Best[:found]
+	r.Labels, r.IDs = r.Labels[:n], r.IDs[:int(total)]
+	return r, nil
+}
+
 // GroupGeometry is the result of (*KDTree).GroupStats, one row per group: Count of live members; AABB lo x, y, z then
 // hi x, y, z; Centroid; Cov in the order xx, xy, xz, yy, yz, zz; Eig descending; Axes: the three unit eigenvectors as
 // rows (axis 2 is the fitted plane's normal); OBB: centre x, y, z, then the half-extents along the axes.  A group

@@ -1379,6 +1379,95 @@ PCGX_API pcgx_status pcgx_kdtree_planes_dev(const pcgx_kdtree *t, const uint32_t
  * across. */
 PCGX_API int32_t pcgx_planes_tile(void);
 
+/* ------------------------------------------- shapes (extension: no reference parity)
+ * NOT in the reference.  Cylinder and sphere segmentation as PCL's SACSegmentationFromNormals with SACMODEL_CYLINDER /
+ * SACMODEL_SPHERE in a loop with ExtractIndices, the hypotheses made from TWO oriented points (Schnabel, Wahl, Klein
+ * 2007), the second drawn from the first's radius neighbourhood: a pole holds a thousandth of a cloud, and two points
+ * drawn from all of it lie on the same pole once in a million draws.  The rounds, the samples, the first best, the
+ * peeling and the outputs are pcgx_kdtree_planes'; where a point is not stated here, that contract holds word for word.
+ * This comment is the contract, tests/shape_oracle.py restates it.
+ *   pcgx_kdtree_shapes    (t, kind, samples[2 n_hyp max_shapes] u32, n_hyp, max_shapes, max_dist, min_inliers,
+ *                          sample_radius, r_min, r_max, axis[3] | NULL, min_axis_cos, normals[3 Len()], min_normal_cos,
+ *                          refine, n_shapes*, shapes[8 max_shapes] f32, sizes[max_shapes] i64, refined[max_shapes] i32,
+ *                          best[max_shapes] i64, labels[Len()] i64, ids[Len()] i64 | NULL,
+ *                          status[max_shapes n_hyp] i32 | NULL, counts[...] i64 | NULL, hyp_shapes[8 ...] f32 | NULL)
+ *   pcgx_kdtree_shapes_dev(... every array device resident, ids / sizes / labels / counts / best int32,
+ *                          d_n_shapes one int32, stream; axis stays a host argument)
+ * kind: PCGX_SHAPE_SPHERE (0) or PCGX_SHAPE_CYLINDER (1).  Normals are mandatory: the hypotheses are made from them.
+ * Live point, A_r, R_r and how a word names an index: pcgx_kdtree_planes' with normals given.  Round r runs iff
+ *   r < max_shapes, every earlier round found a shape and R_r >= 2.
+ * Sampling: hypothesis h of round r uses u0 = samples[2 (r n_hyp + h)] and u1 = samples[2 (r n_hyp + h) + 1].  The seed
+ *   is i0 = A_r[(u0 R_r) >> 32].  With sample_radius == 0 the partner is i1 = A_r[(u1 R_r) >> 32]; status 1 if i1 == i0.
+ *   With sample_radius > 0 the candidates are the points of A_r other than i0 in the set pcgx_kdtree_range_count counts
+ *   for the seed and that radius on that handle (strict bound, deleted points absent; points taken by earlier rounds are
+ *   not in A_r).  The partner is the candidate with the smallest (x, id), x in uint32 arithmetic:
+ *   x = u1 ^ (id * 0x9E3779B1); x ^= x >> 16; x *= 0x85EBCA6B; x ^= x >> 13; x *= 0xC2B2AE35; x ^= x >> 16.  No candidate:
+ *   status 1.  The choice is a property of the set, not of the order it is enumerated in: the grid, the tree walk
+ *   (PCGX_RANGE_WALK=1) and the patched walk of a handle with deletions give the same partner.
+ * Hypothesis of (p0, n0), (p1, n1), in float64 from the float32 numbers, each operation rounded once, nothing contracted,
+ *   dots as (x x + y y) + z z:  w = p0 - p1, A = n0.n0, B = n0.n1, C = n1.n1, D = n0.w, E = n1.w, den = A C - B B.
+ *   Status 2 (degenerate) unless den > 1e-12 (A C) (a comparison that fails on NaN is degenerate).  s = (B E - C D) / den,
+ *   t = (A E - B D) / den: c0 = p0 + s n0 and c1 = p1 + t n1 are the closest points of the two normal lines,
+ *   m = 0.5 (c0 + c1).  Sphere: the centre is m, r = 0.5 (|p0 - m| + |p1 - m|).  Cylinder: a = n0 x n1 divided by
+ *   sqrt((ax ax + ay ay) + az az); axis test, status 3, as the planes' on this a: |a . axis| >= (double)min_axis_cos |axis|
+ *   (the cylinder's axis PARALLEL to `axis`: poles along z); a is signed by the planes' rule; q = m - (m.a) a, the axis
+ *   point nearest the origin; r = 0.5 (rho(p0) + rho(p1)), rho(p) = sqrt(max(0, |v|^2 - (v.a)^2)), v = p - q (max(0, x)
+ *   is x where x > 0, else 0).  Status 4 (radius): !(r >= r_min && r <= r_max) on the float64 r, or a number of the
+ *   record is not finite once rounded to float32.  Status 0 otherwise.
+ * Record, 8 float32, each number rounded once: sphere {cx, cy, cz, r, 0, 0, 0, 0}, cylinder {qx, qy, qz, r, ax, ay, az,
+ *   0}.  A rejected hypothesis has count 0 and a zero record; rows of a round that did not run hold status -1.
+ * Inlier: float32 throughout, nothing fused, no square root: given the record's bits the count has no tolerance.  Once
+ *   per record lo = r - max_dist, hi = r + max_dist, hi2 = hi hi, lo2 = lo lo if lo > 0 else -1,
+ *   c2 = min_normal_cos min_normal_cos.  Per point p with normal m, v = p - centre (or p - q):
+ *   sphere d2 = (vx vx + vy vy) + vz vz, g = (mx vx + my vy) + mz vz; cylinder t = (vx ax + vy ay) + vz az,
+ *   d2 = ((vx vx + vy vy) + vz vz) - t t, g = ((mx vx + my vy) + mz vz) - t ((mx ax + my ay) + mz az).  Inlier iff
+ *   d2 < hi2 && d2 > lo2 and, unless min_normal_cos == 0, g g >= c2 d2.  A NaN is not an inlier.
+ * Best, found (count >= max(min_inliers, 2)), peeling, labels, sizes, ids and their padding: pcgx_kdtree_planes'.  Every
+ *   row of every output is written on every call.
+ * Refinement (refine != 0, the round found a shape): I = the best's inliers in ascending id, the pivot the record's own
+ *   centre (sphere) or q (cylinder) widened to float64.  x = p - pivot in three dimensions (sphere), or
+ *   x = ((p - pivot).e1, (p - pivot).e2) in two (cylinder: the record's axis a is kept; e1 = the unit vector of a x the
+ *   coordinate axis of a's smallest |component|, the first on a tie; e2 = a x e1).  |x|^2 - 2 x.u - k is fitted to zero by
+ *   linear least squares (Kasa) in float64: unknowns (u, k), rows (2 x, 1), so the normal matrix is
+ *   [[4 sum x x^T, 2 sum x], [2 sum x^T, n]] and the right side (2 sum |x|^2 x, sum |x|^2), solved by Cholesky in that
+ *   order of unknowns.  The sums are added in a fixed order with no float atomic: the same bits on every call and under
+ *   every split.  No refit when a pivot of the factorisation is not > 1e-12 times the largest diagonal entry, k + |u|^2 is
+ *   not > 0, the new radius r = sqrt(k + |u|^2) fails the radius test, or a number of the new record is not finite.  The
+ *   new centre is the pivot plus u (plus u1 e1 + u2 e2, q made canonical again).  The points of A_r are counted again
+ *   under the refitted record; it replaces the hypothesis's iff its count >= the best's count.  One refit, not an
+ *   iteration; the cylinder's axis is not refitted.
+ * PCGX_E_INVALID (nothing is written): pcgx_kdtree_planes' list (min_normal_cos always checked), and kind not 0 or 1,
+ *   NULL normals with Len() > 0, sample_radius negative or not finite, r_min or r_max NaN or negative, r_min > r_max
+ *   (r_max may be +inf).  n_hyp == 0 or Len() == 0 is PCGX_OK with n_shapes = 0.
+ * Always computed on the device (csrc/shapes.hip).  The points are split into chunks to fill the chip (the library's
+ *   choice; PCGX_SHAPES_SPLIT=<n> in the environment, read per call, forces it -- any n gives the same bits). */
+#define PCGX_SHAPE_SPHERE 0
+#define PCGX_SHAPE_CYLINDER 1
+PCGX_API pcgx_status pcgx_kdtree_shapes(const pcgx_kdtree *t, int32_t kind,
+                                        const uint32_t *samples /* [2 n_hyp max_shapes] */, int64_t n_hyp,
+                                        int32_t max_shapes, float max_dist, int64_t min_inliers, float sample_radius,
+                                        float r_min, float r_max, const float *axis /* [3] or NULL */, float min_axis_cos,
+                                        const float *normals /* [3 Len()] */, float min_normal_cos, int32_t refine,
+                                        int64_t *n_shapes, float *shapes, int64_t *sizes, int32_t *refined, int64_t *best,
+                                        int64_t *labels, int64_t *ids /* may be NULL */, int32_t *status /* may be NULL */,
+                                        int64_t *counts /* may be NULL */, float *hyp_shapes /* may be NULL */);
+/* Same, every array device resident (`axis` alone stays three floats in HOST memory), enqueued on `stream` (NULL: the
+ * library's); returns without waiting and reads nothing back.  Ids, sizes, labels, counts and best are int32, d_n_shapes
+ * is one int32.  d_ids, d_sizes and d_n_shapes can be passed on to pcgx_kdtree_group_stats_dev and
+ * pcgx_kdtree_group_hulls_dev as they are (cap_ids = Len(), cap_groups = max_shapes).  A handle with deleted points has
+ * its deleted flags copied to the device first, and that copy alone is waited for. */
+PCGX_API pcgx_status pcgx_kdtree_shapes_dev(const pcgx_kdtree *t, int32_t kind, const uint32_t *d_samples, int64_t n_hyp,
+                                            int32_t max_shapes, float max_dist, int64_t min_inliers, float sample_radius,
+                                            float r_min, float r_max, const float *axis /* HOST [3] or NULL */,
+                                            float min_axis_cos, const float *d_normals, float min_normal_cos,
+                                            int32_t refine, int32_t *d_n_shapes, float *d_shapes, int32_t *d_sizes,
+                                            int32_t *d_refined, int32_t *d_best, int32_t *d_labels,
+                                            int32_t *d_ids /* may be NULL */, int32_t *d_status /* may be NULL */,
+                                            int32_t *d_counts /* may be NULL */, float *d_hyp_shapes /* may be NULL */,
+                                            void *stream);
+/* Hypotheses per workgroup of the count kernel (a wave, two hypotheses per lane). */
+PCGX_API int32_t pcgx_shapes_tile(void);
+
 /* ------------------------------------------- score poses (extension: no reference parity)
  * NOT in the reference.  pcgx_pose_from_correspondences picks its pose by the inliers among the CORRESPONDENCES; on a
  * scene with repeated structure a wrong pose can collect more of them than the right one.  This call counts, for each of

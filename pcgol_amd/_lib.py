@@ -287,6 +287,11 @@ SIGNATURES = {
     "pcgx_kdtree_planes_dev": (_i32, [_vp, _vp, _i64, _i32, _f32, _i64, _vp, _f32, _vp, _f32, _i32, _vp, _vp, _vp, _vp, _vp,
                                       _vp, _vp, _vp, _vp, _vp, _vp]),
     "pcgx_planes_tile": (_i32, []),
+    "pcgx_kdtree_shapes": (_i32, [_vp, _i32, _vp, _i64, _i32, _f32, _i64, _f32, _f32, _f32, _vp, _f32, _vp, _f32, _i32,
+                                  C.POINTER(_i64), _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "pcgx_kdtree_shapes_dev": (_i32, [_vp, _i32, _vp, _i64, _i32, _f32, _i64, _f32, _f32, _f32, _vp, _f32, _vp, _f32, _i32,
+                                      _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "pcgx_shapes_tile": (_i32, []),
     "pcgx_kdtree_score_poses": (_i32, [_vp, _vp, _i64, _vp, _i64, _f32, _vp, _vp, C.POINTER(_i64), _vp]),
     "pcgx_kdtree_score_poses_dev": (_i32, [_vp, _vp, _i64, _vp, _i64, _f32, _vp, _vp, _vp, _vp]),
     "pcgx_score_tile": (_i32, []),

@@ -373,6 +373,54 @@ class KDTree {  // pc/storage/kdtree/kdtree.go:14-23
     r.ids.resize(total);
     return r;
   }
+  // Cylinder and sphere segmentation (extension: no reference parity; include/pcgx.h, pcgx_kdtree_shapes): the sphere
+  // (kind PCGX_SHAPE_SPHERE) or cylinder (PCGX_SHAPE_CYLINDER) most live points lie within maxDist of, by sample
+  // consensus over hypotheses made from two oriented points -- a seed and a partner out of its sampleRadius
+  // neighbourhood (0: out of everything left) -- drawn by the caller's random words (samples: 2 per hypothesis and round);
+  // its inliers taken out, then the next, until a round's best has fewer than max(minInliers, 2).  normals: one per
+  // point; rMin <= r <= rMax; axis (nullptr: none): only cylinders whose axis has |cos| >= minAxisCos with it; an
+  // inlier's normal has |cos| >= minNormalCos with the shape's.  A ShapesResult is a ClustersResult (GroupStats and
+  // GroupHulls take it), one group a shape in the order found; shapes: 8 floats per shape, (cx, cy, cz, r, 0, 0, 0, 0) or
+  // (qx, qy, qz, r, ax, ay, az, 0); refined, best: per shape; status, counts, hypShapes: per round and hypothesis.
+  struct ShapesResult : ClustersResult {
+    std::vector<float> shapes, hypShapes;
+    std::vector<int32_t> refined, status;
+    std::vector<int64_t> best, counts;
+  };
+  ShapesResult Shapes(int32_t kind, float maxDist, const std::vector<Vec3> &normals, const std::vector<uint32_t> &samples,
+                      int64_t nHyp, int32_t maxShapes = 1, int64_t minInliers = 2, float sampleRadius = 0.0f,
+                      float rMin = 0.0f, float rMax = __builtin_inff(), const float *axis = nullptr, float minAxisCos = 0.0f,
+                      float minNormalCos = 0.0f, bool refine = true) const {
+    const int64_t n = Len();
+    if ((int64_t)normals.size() != n) throw Error(PCGX_E_INVALID, "one normal per point of the tree is required");
+    if (nHyp > 0 && maxShapes > 0 && (int64_t)samples.size() != 2 * nHyp * maxShapes)
+      throw Error(PCGX_E_INVALID, "two sample words per hypothesis and round are required");
+    const size_t mp = maxShapes > 0 ? (size_t)maxShapes : 0, rows = nHyp > 0 ? mp * (size_t)nHyp : 0;
+    ShapesResult r;
+    r.labels.resize((size_t)n);
+    r.ids.resize((size_t)n);
+    r.sizes.resize(mp);
+    r.shapes.resize(8 * mp);
+    r.refined.resize(mp);
+    r.best.resize(mp);
+    r.status.resize(rows);
+    r.counts.resize(rows);
+    r.hypShapes.resize(8 * rows);
+    int64_t c = 0;
+    check(pcgx_kdtree_shapes(h_.get(), kind, samples.empty() ? nullptr : samples.data(), nHyp, maxShapes, maxDist, minInliers,
+                             sampleRadius, rMin, rMax, axis, minAxisCos, normals.empty() ? nullptr : normals[0].data(),
+                             minNormalCos, refine ? 1 : 0, &c, r.shapes.data(), r.sizes.data(), r.refined.data(),
+                             r.best.data(), r.labels.data(), r.ids.data(), r.status.data(), r.counts.data(),
+                             r.hypShapes.data()));
+    r.sizes.resize((size_t)c);
+    r.shapes.resize(8 * (size_t)c);
+    r.refined.resize((size_t)c);
+    r.best.resize((size_t)c);
+    size_t total = 0;
+    for (int64_t s : r.sizes) total += (size_t)s;
+    r.ids.resize(total);
+    return r;
+  }
   // Group geometry (extension: no reference parity; include/pcgx.h, pcgx_kdtree_group_stats): per group of a grouped id
   // list over the tree's own points -- ids: group 0's members, then group 1's, ...; sizes: per group; what Clusters
   // returns -- the count of live members, the axis-aligned box (lo xyz, hi xyz), centroid and covariance (xx, xy, xz,

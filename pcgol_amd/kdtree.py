@@ -1,7 +1,7 @@
 """pc/storage/kdtree mirror: KDTree on the GPU behind the storage.Search shape
 (pc/storage/search.go:13-17): Vec3At / Len / Nearest, plus batched NearestBatch, and extensions with no
 reference counterpart: surface normals (Normals), moving-least-squares smoothing (MLS), FPFH descriptors
-(FPFH, FPFHAt), keypoints (LocalMaxima, ISSKeypoints), cluster extraction (Clusters), density clusters (DBSCAN), plane segmentation (Planes), per-group
+(FPFH, FPFHAt), keypoints (LocalMaxima, ISSKeypoints), cluster extraction (Clusters), density clusters (DBSCAN), plane segmentation (Planes), cylinder and sphere segmentation (Shapes), per-group
 geometry (GroupStats), k nearest neighbours (KNearest) and their covariances (Covariances)."""
 import collections
 import ctypes as C
@@ -29,6 +29,16 @@ GroupFootprints = collections.namedtuple("GroupFootprints", "hull_sizes hull_ids
 
 PlaneSegments = collections.namedtuple("PlaneSegments",  # KDTree.Planes
                                        "n_planes planes sizes refined best labels ids status counts hyp_planes")
+
+
+ShapeSegments = collections.namedtuple("ShapeSegments",  # KDTree.Shapes
+                                       "n_shapes shapes sizes refined best labels ids status counts hyp_shapes")
+SHAPE_SPHERE, SHAPE_CYLINDER = 0, 1
+
+
+def ShapesTile():
+    """Hypotheses per workgroup of Shapes' count kernel (the boundary the tests put NHyp across)."""
+    return int(L.lib().pcgx_shapes_tile())
 
 
 def PlanesTile():
@@ -543,6 +553,68 @@ class KDTree:
             L.ptr(axis) if axis is not None else None, float(MinAxisCos), opt(d_normals), float(MinNormalCos),
             int(bool(Refine)), opt(d_n_planes), opt(d_planes), opt(d_sizes), opt(d_refined), opt(d_best), opt(d_labels),
             opt(d_ids), opt(d_status), opt(d_counts), opt(d_hyp_planes), L.ptr(stream) if stream else None))
+
+    # -- extension (no reference parity): cylinder and sphere segmentation from oriented pairs
+    def Shapes(self, Kind, MaxDist, Normals, NHyp=256, MaxShapes=1, MinInliers=2, SampleRadius=0.0, RMin=0.0,
+               RMax=float("inf"), Axis=None, MinAxisCos=0.0, MinNormalCos=0.0, Refine=True, Samples=None, Seed=0):
+        """The sphere (Kind 0) or cylinder (Kind 1) most of the tree's live points lie within MaxDist of, by sample
+        consensus over NHyp hypotheses made from two oriented points -- a seed and a partner out of its SampleRadius
+        neighbourhood (0: out of everything that is left); its inliers are taken out and the next shape is looked for,
+        up to MaxShapes times, until a round's best has fewer than max(MinInliers, 2) inliers -> ShapeSegments(n_shapes,
+        shapes float32 (MaxShapes, 8) as (cx, cy, cz, r, 0, 0, 0, 0) or (qx, qy, qz, r, ax, ay, az, 0), sizes int64,
+        refined int32, best int64, labels int64 (n,), ids int64 (sum(sizes),), status int32 (MaxShapes, NHyp), counts
+        int64, hyp_shapes float32 (MaxShapes, NHyp, 8)).  Normals (n, 3) are mandatory; RMin <= r <= RMax; Axis: only
+        cylinders whose axis has |cos| >= MinAxisCos with it; an inlier's normal has |cos| >= MinNormalCos with the
+        shape's; Refine: the best's centre and radius are refitted once to its inliers and kept where that loses no
+        inlier.  Samples: uint32 (MaxShapes, NHyp, 2) random words, drawn from np.random.default_rng(Seed) when None
+        (include/pcgx.h, pcgx_kdtree_shapes)."""
+        n, nh, mp = self.Len(), int(NHyp), int(MaxShapes)
+        if Samples is None:
+            Samples = np.random.default_rng(Seed).integers(0, 2 ** 32, (max(mp, 0), max(nh, 0), 2),
+                                                           dtype=np.uint64).astype(np.uint32)
+        smp = np.ascontiguousarray(Samples, np.uint32).reshape(-1)
+        if nh > 0 and mp > 0 and len(smp) != 2 * nh * mp:
+            raise ValueError("two sample words per hypothesis and round are required")
+        nrm = axis = None
+        if Normals is not None:
+            nrm = L.f32c(Normals).reshape(-1, 3)
+            if len(nrm) != n:
+                raise ValueError("one normal per point of the tree is required")
+        if Axis is not None:
+            axis = L.f32c(Axis).reshape(3)
+        rows = max(nh, 0) * max(mp, 0)
+        out = ShapeSegments(0, np.zeros((max(mp, 0), 8), np.float32), np.zeros(max(mp, 0), np.int64),
+                            np.zeros(max(mp, 0), np.int32), np.full(max(mp, 0), -1, np.int64), np.full(n, -1, np.int64),
+                            np.full(n, -1, np.int64), np.full(rows, -1, np.int32), np.zeros(rows, np.int64),
+                            np.zeros((rows, 8), np.float32))
+        cnt = C.c_int64()
+        opt = lambda a: L.ptr(a) if a is not None and a.size else None  # noqa: E731
+        L.check(L.lib().pcgx_kdtree_shapes(
+            self._h, int(Kind), opt(smp), nh, mp, float(MaxDist), int(MinInliers), float(SampleRadius), float(RMin),
+            float(RMax), opt(axis), float(MinAxisCos), L.ptr(nrm) if nrm is not None else None, float(MinNormalCos),
+            int(bool(Refine)), C.byref(cnt), opt(out.shapes), opt(out.sizes), opt(out.refined), opt(out.best),
+            opt(out.labels), opt(out.ids), opt(out.status), opt(out.counts), opt(out.hyp_shapes)))
+        k = int(out.sizes[:cnt.value].sum())
+        return out._replace(n_shapes=int(cnt.value), ids=out.ids[:k], status=out.status.reshape(mp, nh),
+                            counts=out.counts.reshape(mp, nh), hyp_shapes=out.hyp_shapes.reshape(mp, nh, 8))
+
+    def ShapesDev(self, Kind, MaxDist, d_normals, d_samples, NHyp, d_n_shapes, d_shapes, d_sizes, d_refined, d_best,
+                  d_labels, d_ids=0, d_status=0, d_counts=0, d_hyp_shapes=0, MaxShapes=1, MinInliers=2, SampleRadius=0.0,
+                  RMin=0.0, RMax=float("inf"), Axis=None, MinAxisCos=0.0, MinNormalCos=0.0, Refine=True, stream=0):
+        """Device-resident Shapes: raw device addresses (e.g. torch .data_ptr()); d_normals float32 [3 Len()] (what
+        NormalsDev writes), d_samples uint32 [2 NHyp MaxShapes], d_n_shapes one int32, d_shapes float32 [8 MaxShapes],
+        d_sizes / d_refined / d_best int32 [MaxShapes], d_labels int32 [Len()], d_ids int32 [Len()] (the inliers shape
+        by shape, then -1), d_status / d_counts int32 [MaxShapes NHyp], d_hyp_shapes float32 [8 MaxShapes NHyp]; Axis
+        stays a host value.  Enqueued on `stream`, returns without waiting; nothing is read back.  d_ids, d_sizes and
+        d_n_shapes are a grouped list for GroupStatsDev and GroupHullsDev (cap_ids = Len(), cap_groups = MaxShapes)."""
+        opt = lambda a: L.ptr(int(a)) if a else None  # noqa: E731
+        axis = L.f32c(Axis).reshape(3) if Axis is not None else None
+        L.check(L.lib().pcgx_kdtree_shapes_dev(
+            self._h, int(Kind), opt(d_samples), int(NHyp), int(MaxShapes), float(MaxDist), int(MinInliers),
+            float(SampleRadius), float(RMin), float(RMax), L.ptr(axis) if axis is not None else None, float(MinAxisCos),
+            opt(d_normals), float(MinNormalCos), int(bool(Refine)), opt(d_n_shapes), opt(d_shapes), opt(d_sizes),
+            opt(d_refined), opt(d_best), opt(d_labels), opt(d_ids), opt(d_status), opt(d_counts), opt(d_hyp_shapes),
+            L.ptr(stream) if stream else None))
 
     # -- extension (no reference parity): k nearest neighbours
     def KNearest(self, p, k, maxRange):

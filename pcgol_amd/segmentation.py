@@ -319,3 +319,72 @@ class PlaneSegmentation(_Grouped):
             Seed=self.seed)
         self.planes = r.planes[:r.n_planes]
         return r.labels, r.sizes[:r.n_planes], r.ids
+
+
+class ShapeSegmentation(_Grouped):
+    """Cylinder and sphere segmentation in PCL's vocabulary (SACSegmentationFromNormals with SACMODEL_CYLINDER /
+    SACMODEL_SPHERE, run in a loop with ExtractIndices), over KDTree.Shapes (extension: no reference parity;
+    include/pcgx.h, "shapes").  search: a pcgol_amd KDTree; Normals: one per point, e.g. what KDTree.Normals returns.
+
+        ss = ShapeSegmentation(tree, normals, Model="cylinder", DistanceThreshold=0.02, MaxShapes=4, MinInliers=500)
+        ss.SetRadiusLimits(0.03, 0.3); ss.SetSampleRadius(0.3)
+        ss.SetAxis((0, 0, 1)); ss.SetEpsAngle(np.radians(15))     # upright poles only
+        for ids in ss.Extract(): ...                              # ss.shapes[k] = (qx, qy, qz, r, ax, ay, az, 0)
+
+    The shapes come in the order they were found, each as ascending int64 ids; Boxes() and Footprints() give their
+    geometry.  .result holds everything KDTree.Shapes returned."""
+
+    MODELS = {"sphere": 0, "cylinder": 1}
+
+    def __init__(self, search, Normals, Model="cylinder", DistanceThreshold=0.0, MaxShapes=1, MinInliers=2,
+                 MaxIterations=256, SampleRadius=0.0, RadiusLimits=(0.0, float("inf")), NormalMinCos=0.0, Refine=True,
+                 Seed=0):
+        self.search, self.normals = search, Normals
+        self.kind = self.MODELS[Model] if isinstance(Model, str) else int(Model)
+        self.max_dist, self.max_shapes, self.min_inliers = float(DistanceThreshold), int(MaxShapes), int(MinInliers)
+        self.n_hyp, self.refine, self.seed = int(MaxIterations), bool(Refine), Seed
+        self.sample_radius = float(SampleRadius)
+        self.r_min, self.r_max = float(RadiusLimits[0]), float(RadiusLimits[1])
+        self.axis, self.min_axis_cos, self.min_normal_cos = None, 0.0, float(NormalMinCos)
+        self.labels = self.sizes = self.ids = self.shapes = self.result = None
+
+    def SetDistanceThreshold(self, d):
+        self.max_dist = float(d)
+
+    def SetMaxIterations(self, n):
+        """hypotheses a round draws (all of them are scored: there is no early stop)"""
+        self.n_hyp = int(n)
+
+    def SetMaxShapes(self, n):
+        self.max_shapes = int(n)
+
+    def SetMinInliers(self, n):
+        self.min_inliers = int(n)
+
+    def SetSampleRadius(self, r):
+        """the second point of a hypothesis comes out of this radius about the first; 0: out of everything left"""
+        self.sample_radius = float(r)
+
+    def SetRadiusLimits(self, r_min, r_max):
+        self.r_min, self.r_max = float(r_min), float(r_max)
+
+    def SetAxis(self, axis):
+        """only cylinders whose axis lies within the angle of SetEpsAngle of this one; None: any"""
+        self.axis = None if axis is None else np.asarray(axis, np.float32).reshape(3)
+
+    def SetEpsAngle(self, angle):
+        self.min_axis_cos = float(np.cos(angle))
+
+    def SetInputNormals(self, Normals, MinCos=None):
+        """an inlier's normal also needs |cos| >= MinCos with the shape's at that point (0: distances alone)"""
+        self.normals = Normals
+        if MinCos is not None:
+            self.min_normal_cos = float(MinCos)
+
+    def _run(self):
+        r = self.result = self.search.Shapes(
+            self.kind, self.max_dist, self.normals, NHyp=self.n_hyp, MaxShapes=self.max_shapes,
+            MinInliers=self.min_inliers, SampleRadius=self.sample_radius, RMin=self.r_min, RMax=self.r_max, Axis=self.axis,
+            MinAxisCos=self.min_axis_cos, MinNormalCos=self.min_normal_cos, Refine=self.refine, Seed=self.seed)
+        self.shapes = r.shapes[:r.n_shapes]
+        return r.labels, r.sizes[:r.n_shapes], r.ids
