@@ -813,6 +813,70 @@ func (k *KDTree) Shapes(kind int32, maxDist float32, normals []float32, samples 
 	return r, nil
 }
 
+// GroundGrid is the grid (*KDTree).Ground works on: its corner (x, y), its size in cells (nx, ny) and the cell's side.
+type GroundGrid struct {
+	Origin [2]float32
+	Dims   [2]int32
+	Cell   float32
+}
+
+// GroundSegments is the result of (*KDTree).Ground: Labels per point (0 ground, 1 not ground, -1 no part), Sizes of the
+// two groups, IDs the ground ascending, then the rest (a grouped list for GroupStats and GroupHulls), Window the first
+// window a point failed (-1: ground), Surface the terrain model (Dims[1] rows of Dims[0], +Inf at an empty cell) and HAG
+// the height above it per point (NaN where the point takes no part).
+type GroundSegments struct {
+	Labels  []int64
+	Sizes   []int64
+	IDs     []int64
+	Window  []int32
+	Surface []float32
+	HAG     []float32
+}
+
+// Ground segments the tree's live points into ground and the rest by a progressive morphological filter (extension: no
+// reference parity; include/pcgx.h, pcgx_kdtree_ground): the minimum z surface over the grid is opened with squares of
+// half[k] cells one after the other, and a point is ground iff z - surface_k < height[k] after every window k.
+func (k *KDTree) Ground(g GroundGrid, half []int32, height []float32) (*GroundSegments, error) {
+	runtime.LockOSThread() // the error text is thread-local on the C side: call and pcgx_last_error on one OS thread
+	defer runtime.UnlockOSThread()
+	defer runtime.KeepAlive(k) // the finalizer must not free the handle while a call is in flight
+	var ln C.int64_t
+	if err := status(C.pcgx_kdtree_len(k.t.h, &ln)); err != nil {
+		return nil, err
+	}
+	n := int(ln)
+	if len(half) != len(height) {
+		return nil, errors.New("pcgx: one height per window is required")
+	}
+	cells := 1
+	if g.Dims[0] >= 1 && g.Dims[0] <= 8192 && g.Dims[1] >= 1 && g.Dims[1] <= 8192 {
+		cells = int(g.Dims[0]) * int(g.Dims[1]) // (the call refuses other sizes; the output must exist all the same)
+	}
+	r := &GroundSegments{Labels: make([]int64, n+1), Sizes: make([]int64, 2), IDs: make([]int64, n+1),
+		Window: make([]int32, n+1), Surface: make([]float32, cells), HAG: make([]float32, n+1)}
+	var hf *C.int32_t
+	var ht *C.float
+	if len(half) > 0 {
+		hf = (*C.int32_t)(unsafe.Pointer(&half[0]))
+		ht = (*C.float)(unsafe.Pointer(&height[0]))
+	}
+	var c C.int64_t
+	rc := C.pcgx_kdtree_ground(k.t.h, (*C.float)(unsafe.Pointer(&g.Origin[0])), (*C.int32_t)(unsafe.Pointer(&g.Dims[0])),
+		C.float(g.Cell), C.int32_t(len(half)), hf, ht, (*C.int64_t)(unsafe.Pointer(&r.Labels[0])),
+		(*C.int64_t)(unsafe.Pointer(&r.Sizes[0])), (*C.int64_t)(unsafe.Pointer(&r.IDs[0])), &c,
+		(*C.int32_t)(unsafe.Pointer(&r.Window[0])), (*C.float)(unsafe.Pointer(&r.Surface[0])),
+		(*C.float)(unsafe.Pointer(&r.HAG[0])))
+	runtime.KeepAlive(half)
+	runtime.KeepAlive(height)
+	runtime.KeepAlive(r)
+	if err := status(rc); err != nil {
+		return nil, err
+	}
+	r.Labels, r.IDs = r.Labels[:n], r.IDs[:int(r.Sizes[0]+r.Sizes[1])]
+	r.Window, r.HAG = r.Window[:n], r.HAG[:n]
+	return r, nil
+}
+
 // GroupGeometry is the result of (*KDTree).GroupStats, one row per group: Count of live members; AABB lo x, y, z then
 // hi x, y, z; Centroid; Cov in the order xx, xy, xz, yy, yz, zz; Eig descending; Axes: the three unit eigenvectors as
 // rows (axis 2 is the fitted plane's normal); OBB: centre x, y, z, then the half-extents along the axes.  A group

@@ -1468,6 +1468,63 @@ PCGX_API pcgx_status pcgx_kdtree_shapes_dev(const pcgx_kdtree *t, int32_t kind, 
 /* Hypotheses per workgroup of the count kernel (a wave, two hypotheses per lane). */
 PCGX_API int32_t pcgx_shapes_tile(void);
 
+/* ------------------------------------------- ground (extension: no reference parity)
+ * NOT in the reference.  Ground segmentation for terrain that no plane holds: the grid form of the progressive
+ * morphological filter (Zhang et al. 2003; PCL's ApproximateProgressiveMorphologicalFilter).  The minimum surface of the
+ * points over the caller's grid is opened with squares that grow by the caller's schedule; a point is ground while it
+ * stays within the schedule's height of every opened surface.  The up axis is z.  The caller gives the grid (as
+ * StorageVoxelGrid's resolution, size and origin) and the window schedule (as it gives the random words elsewhere): this
+ * contract holds no floating-point formula for either.  Every step is a min, a max or one float32 subtraction, so the
+ * result is a property of the point set.  This comment is the contract, tests/ground_oracle.py restates it.
+ *   pcgx_kdtree_ground    (t, origin[2] f32, dims[2] i32 (nx, ny), cell, n_win, half[n_win] i32, height[n_win] f32,
+ *                          labels[Len()] i64, sizes[2] i64, ids[Len()] i64, n_groups*, window[Len()] i32 | NULL,
+ *                          surface[nx ny] f32 | NULL, hag[Len()] f32 | NULL)
+ *   pcgx_kdtree_ground_dev(... origin, dims, half and height stay in HOST memory; labels, sizes, ids int32, d_n_groups
+ *                          one int32, every output device resident, stream)
+ * Cell of a point, all float32, each operation rounded once: fx = floorf((x - ox) / cell), fy = floorf((y - oy) / cell).
+ * Live point: not deleted (pcgx_kdtree_delete_point[s]), x, y and z finite, 0 <= fx < nx and 0 <= fy < ny compared as
+ *   floats before any conversion; then c = (int)fy * nx + (int)fx.  A point that is not live has label -1 and takes no part.
+ * Minimum surface: S_0[c] = the smallest z of the live points of cell c, by the order-preserving key of group geometry's
+ *   min / max combines, so -0.0 lies below +0.0.  A cell without a live point is EMPTY.
+ * Window k = 0 .. n_win - 1, h = half[k]; the window of cell (i, j) is the in-grid cells with |di| <= h and |dj| <= h:
+ *   E[c] = the key-minimum of S_k over the non-empty cells of c's window, empty if there are none;
+ *   S_{k+1}[c] = the key-maximum of E over the non-empty cells of c's window, empty if there are none
+ *   (a grey opening with a (2 h + 1)^2 square; the next window opens the opened surface; empty cells take no part in
+ *   either half).
+ * Ground test: a live point survives window k iff z - S_{k+1}[c] < height[k] (float32, one subtraction, strict).  It is
+ *   GROUND iff it survives every window; window[i] = the first k it fails, -1 for ground points and points that are not
+ *   live.  The surfaces depend on S_0 alone, not on which points have failed so far.
+ * Outputs, every row written on every call: labels[i] 0 ground, 1 not ground, -1 not live; sizes[2] their counts; ids:
+ *   the ground ascending, then the rest ascending, then -1 in the remaining slots; n_groups = 2 (a grouped list for
+ *   pcgx_kdtree_group_stats[_dev] and pcgx_kdtree_group_hulls[_dev]); surface = S_{n_win}, +inf at an empty cell (the
+ *   terrain model); hag[i] = z - S_{n_win}[c], bits 0x7fc00000 where the point is not live (the height above ground).
+ * PCGX_E_INVALID (nothing is written): a NULL tree, origin or dims; cell not finite or not > 0; an origin that is not
+ *   finite; nx or ny outside [1, 8192]; n_win outside [0, 64]; a half[k] outside [1, 8192]; a height[k] not finite or
+ *   not > 0; NULL half or height with n_win > 0; a NULL mandatory output (labels and ids only where Len() > 0).
+ *   n_win == 0 is PCGX_OK: every live point is ground and surface = S_0.  Len() == 0 is PCGX_OK with sizes 0, 0.
+ * Always computed on the device (csrc/ground.hip).  The same input gives the same bits on every call: no float atomic
+ *   anywhere, the minimum surface is an unsigned atomicMin over keys. */
+PCGX_API pcgx_status pcgx_kdtree_ground(const pcgx_kdtree *t, const float *origin /* [2] */, const int32_t *dims /* [2] */,
+                                        float cell, int32_t n_win, const int32_t *half, const float *height,
+                                        int64_t *labels, int64_t *sizes /* [2] */, int64_t *ids, int64_t *n_groups,
+                                        int32_t *window /* may be NULL */, float *surface /* may be NULL */,
+                                        float *hag /* may be NULL */);
+/* Same, every output device resident (origin, dims, half and height stay in HOST memory: they are arguments, checked
+ * before anything is enqueued), enqueued on `stream` (NULL: the library's); returns without waiting and reads nothing
+ * back: every window is enqueued at once.  d_ids, d_sizes and d_n_groups can be passed on to pcgx_kdtree_group_stats_dev
+ * and pcgx_kdtree_group_hulls_dev as they are (cap_ids = Len(), cap_groups = 2).  A handle with deleted points has its
+ * deleted flags copied to the device first, and that copy alone is waited for. */
+PCGX_API pcgx_status pcgx_kdtree_ground_dev(const pcgx_kdtree *t, const float *origin /* HOST [2] */,
+                                            const int32_t *dims /* HOST [2] */, float cell, int32_t n_win,
+                                            const int32_t *half /* HOST */, const float *height /* HOST */,
+                                            int32_t *d_labels, int32_t *d_sizes, int32_t *d_ids, int32_t *d_n_groups,
+                                            int32_t *d_window /* may be NULL */, float *d_surface /* may be NULL */,
+                                            float *d_hag /* may be NULL */, void *stream);
+/* Cells of a grid row that one pass of the morphology kernel's workgroup handles at once, and the largest half-width
+ * that takes its plain loop (above it: doubling in LDS): the boundaries the tests put nx, ny and half across. */
+PCGX_API int32_t pcgx_ground_tile(void);
+PCGX_API int32_t pcgx_ground_loop_max(void);
+
 /* ------------------------------------------- score poses (extension: no reference parity)
  * NOT in the reference.  pcgx_pose_from_correspondences picks its pose by the inliers among the CORRESPONDENCES; on a
  * scene with repeated structure a wrong pose can collect more of them than the right one.  This call counts, for each of

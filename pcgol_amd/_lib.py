@@ -292,6 +292,10 @@ SIGNATURES = {
     "pcgx_kdtree_shapes_dev": (_i32, [_vp, _i32, _vp, _i64, _i32, _f32, _i64, _f32, _f32, _f32, _vp, _f32, _vp, _f32, _i32,
                                       _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "pcgx_shapes_tile": (_i32, []),
+    "pcgx_kdtree_ground": (_i32, [_vp, _vp, _vp, _f32, _i32, _vp, _vp, _vp, _vp, _vp, C.POINTER(_i64), _vp, _vp, _vp]),
+    "pcgx_kdtree_ground_dev": (_i32, [_vp, _vp, _vp, _f32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "pcgx_ground_tile": (_i32, []),
+    "pcgx_ground_loop_max": (_i32, []),
     "pcgx_kdtree_score_poses": (_i32, [_vp, _vp, _i64, _vp, _i64, _f32, _vp, _vp, C.POINTER(_i64), _vp]),
     "pcgx_kdtree_score_poses_dev": (_i32, [_vp, _vp, _i64, _vp, _i64, _f32, _vp, _vp, _vp, _vp]),
     "pcgx_score_tile": (_i32, []),

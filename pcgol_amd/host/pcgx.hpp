@@ -421,6 +421,39 @@ class KDTree {  // pc/storage/kdtree/kdtree.go:14-23
     r.ids.resize(total);
     return r;
   }
+  // Ground segmentation (extension: no reference parity; include/pcgx.h, pcgx_kdtree_ground): a progressive
+  // morphological filter.  The minimum z surface of the live points over the grid (origin (x, y), dims (nx, ny), cells
+  // of `cell`) is opened with squares of half[k] cells one after the other; a point is ground iff z - surface_k <
+  // height[k] after every window k.  A GroundResult is a ClustersResult (GroupStats and GroupHulls take it) of two
+  // groups, the ground and the rest: labels 0 / 1 / -1 (no part), ids the ground ascending, then the rest.  window: the
+  // first window a point failed, -1 for ground; surface: the terrain model, ny rows of nx, +inf at an empty cell; hag:
+  // the height above it, NaN where a point takes no part.
+  struct GroundResult : ClustersResult {
+    std::vector<int32_t> window;
+    std::vector<float> surface, hag;
+  };
+  GroundResult Ground(const float (&origin)[2], const int32_t (&dims)[2], float cell, const std::vector<int32_t> &half,
+                      const std::vector<float> &height) const {
+    const int64_t n = Len();
+    if (half.size() != height.size()) throw Error(PCGX_E_INVALID, "one height per window is required");
+    const bool grid = dims[0] >= 1 && dims[0] <= 8192 && dims[1] >= 1 && dims[1] <= 8192;
+    GroundResult r;
+    r.labels.resize((size_t)n);
+    r.ids.resize((size_t)n);
+    r.sizes.resize(2);
+    r.window.resize((size_t)n);
+    r.hag.resize((size_t)n);
+    r.surface.resize(grid ? (size_t)dims[0] * (size_t)dims[1] : 0);
+    int64_t g = 0;
+    check(pcgx_kdtree_ground(h_.get(), origin, dims, cell, (int32_t)half.size(), half.empty() ? nullptr : half.data(),
+                             height.empty() ? nullptr : height.data(), r.labels.data(), r.sizes.data(), r.ids.data(), &g,
+                             r.window.data(), r.surface.empty() ? nullptr : r.surface.data(), r.hag.data()));
+    r.sizes.resize((size_t)g);
+    size_t total = 0;
+    for (int64_t s : r.sizes) total += (size_t)s;
+    r.ids.resize(total);
+    return r;
+  }
   // Group geometry (extension: no reference parity; include/pcgx.h, pcgx_kdtree_group_stats): per group of a grouped id
   // list over the tree's own points -- ids: group 0's members, then group 1's, ...; sizes: per group; what Clusters
   // returns -- the count of live members, the axis-aligned box (lo xyz, hi xyz), centroid and covariance (xx, xy, xz,

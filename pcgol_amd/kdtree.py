@@ -1,7 +1,7 @@
 """pc/storage/kdtree mirror: KDTree on the GPU behind the storage.Search shape
 (pc/storage/search.go:13-17): Vec3At / Len / Nearest, plus batched NearestBatch, and extensions with no
 reference counterpart: surface normals (Normals), moving-least-squares smoothing (MLS), FPFH descriptors
-(FPFH, FPFHAt), keypoints (LocalMaxima, ISSKeypoints), cluster extraction (Clusters), density clusters (DBSCAN), plane segmentation (Planes), cylinder and sphere segmentation (Shapes), per-group
+(FPFH, FPFHAt), keypoints (LocalMaxima, ISSKeypoints), cluster extraction (Clusters), density clusters (DBSCAN), plane segmentation (Planes), cylinder and sphere segmentation (Shapes), ground segmentation (Ground), per-group
 geometry (GroupStats), k nearest neighbours (KNearest) and their covariances (Covariances)."""
 import collections
 import ctypes as C
@@ -34,6 +34,20 @@ PlaneSegments = collections.namedtuple("PlaneSegments",  # KDTree.Planes
 ShapeSegments = collections.namedtuple("ShapeSegments",  # KDTree.Shapes
                                        "n_shapes shapes sizes refined best labels ids status counts hyp_shapes")
 SHAPE_SPHERE, SHAPE_CYLINDER = 0, 1
+
+
+GroundSegments = collections.namedtuple("GroundSegments",  # KDTree.Ground
+                                        "labels sizes ids n_groups window surface hag origin dims")
+
+
+def GroundTile():
+    """Cells of a grid row one pass of Ground's morphology workgroup handles (the boundary the tests put nx, ny across)."""
+    return int(L.lib().pcgx_ground_tile())
+
+
+def GroundLoopMax():
+    """The largest half-width Ground's morphology kernel takes with its plain loop (above it: doubling in LDS)."""
+    return int(L.lib().pcgx_ground_loop_max())
 
 
 def ShapesTile():
@@ -615,6 +629,73 @@ class KDTree:
             opt(d_normals), float(MinNormalCos), int(bool(Refine)), opt(d_n_shapes), opt(d_shapes), opt(d_sizes),
             opt(d_refined), opt(d_best), opt(d_labels), opt(d_ids), opt(d_status), opt(d_counts), opt(d_hyp_shapes),
             L.ptr(stream) if stream else None))
+
+    # -- extension (no reference parity): ground segmentation, a progressive morphological filter on a grid
+    def GroundGrid(self, CellSize):
+        """The grid Ground takes when none is given: origin = (min x, min y) of the live points (not deleted, finite),
+        dims = floor((max - origin) / CellSize) + 1, in float32 -> (origin float32 (2,), dims int32 (2,))."""
+        ids = self.InOrder()
+        pts = np.empty((len(ids), 3), np.float32)
+        if len(ids):
+            L.check(L.lib().pcgx_kdtree_points(self._h, L.ptr(ids), len(ids), L.ptr(pts)))
+        pts = pts[np.isfinite(pts).all(axis=1)]
+        if not len(pts):
+            return np.zeros(2, np.float32), np.ones(2, np.int32)
+        lo, hi = pts[:, :2].min(axis=0), pts[:, :2].max(axis=0)
+        with np.errstate(over="ignore"):
+            dims = np.floor((hi - lo) / np.float32(CellSize)) + np.float32(1)
+        return lo, np.clip(dims, 1, 2.0 ** 30).astype(np.int32)
+
+    def Ground(self, CellSize, Half, Height, Origin=None, Dims=None):
+        """Ground segmentation by a progressive morphological filter: the minimum z surface of the live points over a
+        grid of CellSize cells (Origin (x, y), Dims (nx, ny); left out: GroundGrid's) is opened with squares of
+        half-widths Half[k] cells one after the other, and a point is ground iff z - surface_k < Height[k] after every
+        window k (segmentation.pmf_windows makes such a schedule) -> GroundSegments(labels int64 (n,) 0 ground, 1 not,
+        -1 no part; sizes int64 (2,); ids int64 (sum(sizes),) the ground ascending, then the rest; n_groups 2; window
+        int32 (n,) the first window failed or -1; surface float32 (ny, nx) the terrain model, +inf at an empty cell;
+        hag float32 (n,) the height above it; origin, dims as used) (include/pcgx.h, pcgx_kdtree_ground)."""
+        n = self.Len()
+        half = np.ascontiguousarray(Half, np.int32).reshape(-1)
+        height = np.ascontiguousarray(Height, np.float32).reshape(-1)
+        if len(half) != len(height):
+            raise ValueError("one height per window is required")
+        if Origin is None or Dims is None:
+            o, d = self.GroundGrid(CellSize)
+            Origin = o if Origin is None else Origin
+            Dims = d if Dims is None else Dims
+        origin = np.ascontiguousarray(Origin, np.float32).reshape(2)
+        dims = np.ascontiguousarray(Dims, np.int32).reshape(2)
+        cells = int(dims[0]) * int(dims[1]) if 0 < dims[0] <= 8192 and 0 < dims[1] <= 8192 else 0
+        out = GroundSegments(np.full(n, -1, np.int64), np.zeros(2, np.int64), np.full(n, -1, np.int64), 0,
+                             np.full(n, -1, np.int32), np.full(cells, np.inf, np.float32), np.full(n, np.nan, np.float32),
+                             origin, dims)
+        cnt = C.c_int64()
+        opt = lambda a: L.ptr(a) if a.size else None  # noqa: E731
+        L.check(L.lib().pcgx_kdtree_ground(
+            self._h, L.ptr(origin), L.ptr(dims), float(CellSize), len(half), opt(half), opt(height), opt(out.labels),
+            L.ptr(out.sizes), opt(out.ids), C.byref(cnt), opt(out.window), opt(out.surface), opt(out.hag)))
+        return out._replace(ids=out.ids[:int(out.sizes.sum())], n_groups=int(cnt.value),
+                            surface=out.surface.reshape(int(dims[1]), int(dims[0])))
+
+    def GroundDev(self, CellSize, Half, Height, Origin, Dims, d_labels, d_sizes, d_ids, d_n_groups, d_window=0,
+                  d_surface=0, d_hag=0, stream=0):
+        """Device-resident Ground: raw device addresses (e.g. torch .data_ptr()); Half, Height, Origin and Dims stay
+        host values (the caller gives the grid, so nothing is read back); d_labels and d_ids int32 [Len()], d_sizes
+        int32 [2], d_n_groups one int32 (always 2), d_window int32 [Len()], d_surface float32 [nx ny], d_hag float32
+        [Len()] (0: not wanted).  Enqueued on `stream`, returns without waiting: every window is enqueued at once.
+        d_ids, d_sizes and d_n_groups are a grouped list for GroupStatsDev and GroupHullsDev (cap_ids = Len(),
+        cap_groups = 2)."""
+        half = np.ascontiguousarray(Half, np.int32).reshape(-1)
+        height = np.ascontiguousarray(Height, np.float32).reshape(-1)
+        if len(half) != len(height):
+            raise ValueError("one height per window is required")
+        origin = np.ascontiguousarray(Origin, np.float32).reshape(2)
+        dims = np.ascontiguousarray(Dims, np.int32).reshape(2)
+        opt = lambda a: L.ptr(int(a)) if a else None  # noqa: E731
+        L.check(L.lib().pcgx_kdtree_ground_dev(
+            self._h, L.ptr(origin), L.ptr(dims), float(CellSize), len(half), L.ptr(half) if len(half) else None,
+            L.ptr(height) if len(height) else None, opt(d_labels), opt(d_sizes), opt(d_ids), opt(d_n_groups),
+            opt(d_window), opt(d_surface), opt(d_hag), L.ptr(stream) if stream else None))
 
     # -- extension (no reference parity): k nearest neighbours
     def KNearest(self, p, k, maxRange):

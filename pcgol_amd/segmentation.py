@@ -388,3 +388,81 @@ class ShapeSegmentation(_Grouped):
             MinAxisCos=self.min_axis_cos, MinNormalCos=self.min_normal_cos, Refine=self.refine, Seed=self.seed)
         self.shapes = r.shapes[:r.n_shapes]
         return r.labels, r.sizes[:r.n_shapes], r.ids
+
+
+def pmf_windows(CellSize, MaxWindowSize, Slope=1.0, InitialDistance=0.5, MaxDistance=3.0, Base=2, Exponential=True):
+    """The window schedule of the progressive morphological filter (Zhang et al. 2003, PCL's parameters) ->
+    (half int32 (k,), height float32 (k,)), what KDTree.Ground takes.  Widths in cells: w_i = 2 Base^i + 1
+    (Exponential) or 2 (i + 1) Base + 1, for every i = 0, 1, ... with w_i CellSize <= MaxWindowSize; half_i =
+    (w_i - 1) / 2; height_0 = InitialDistance, height_i = min(Slope (w_i - w_{i-1}) CellSize + InitialDistance,
+    MaxDistance), computed in float64 and rounded once to float32.  A pure function: nothing here touches the GPU."""
+    cell, max_w, base = float(CellSize), float(MaxWindowSize), int(Base)
+    if not cell > 0.0 or base < 1 or (Exponential and base < 2):
+        raise ValueError("CellSize must be > 0 and Base at least 1 (2 for an exponential schedule)")
+    half, height, prev = [], [], None
+    i = 0
+    while True:
+        w = 2 * base ** i + 1 if Exponential else 2 * (i + 1) * base + 1
+        if not w * cell <= max_w:
+            break
+        half.append((w - 1) // 2)
+        height.append(float(InitialDistance) if prev is None else
+                      min(float(Slope) * (w - prev) * cell + float(InitialDistance), float(MaxDistance)))
+        prev = w
+        i += 1
+    return np.asarray(half, np.int32), np.asarray(height, np.float64).astype(np.float32)
+
+
+class GroundSegmentation(_Grouped):
+    """Ground segmentation in PCL's vocabulary (ApproximateProgressiveMorphologicalFilter), over KDTree.Ground
+    (extension: no reference parity; include/pcgx.h, "ground").  search: a pcgol_amd KDTree; the up axis is z.
+
+        gs = GroundSegmentation(tree, CellSize=0.5, MaxWindowSize=16.5, Slope=0.3, InitialDistance=0.15, MaxDistance=2.5)
+        ground, other = gs.Extract()                               # gs.hag: every point's height above the terrain
+        keep = np.flatnonzero((gs.hag > 0.3) & (gs.hag < 2.5))     # "between 0.3 and 2.5 m above ground"
+
+    Extract() returns [ground ids, other ids], each ascending int64; .surface is the terrain model (ny, nx), +inf where
+    a cell holds no point, .hag the height above it per point (NaN where a point takes no part), .window the first
+    window a point failed (-1: ground).  Boxes() and Footprints() give the geometry of the two groups.  .result holds
+    everything KDTree.Ground returned.  Origin and Dims: the grid; left out, the box of the live points."""
+
+    def __init__(self, search, CellSize=1.0, MaxWindowSize=33.0, Slope=1.0, InitialDistance=0.5, MaxDistance=3.0, Base=2,
+                 Exponential=True, Origin=None, Dims=None):
+        self.search = search
+        self.cell, self.max_window = float(CellSize), float(MaxWindowSize)
+        self.slope, self.initial, self.max_dist = float(Slope), float(InitialDistance), float(MaxDistance)
+        self.base, self.exponential = int(Base), bool(Exponential)
+        self.origin, self.dims = Origin, Dims
+        self.labels = self.sizes = self.ids = self.surface = self.hag = self.window = self.result = None
+
+    def SetCellSize(self, c):
+        self.cell = float(c)
+
+    def SetMaxWindowSize(self, w):
+        self.max_window = float(w)
+
+    def SetSlope(self, s):
+        self.slope = float(s)
+
+    def SetInitialDistance(self, d):
+        self.initial = float(d)
+
+    def SetMaxDistance(self, d):
+        self.max_dist = float(d)
+
+    def SetBase(self, b):
+        self.base = int(b)
+
+    def SetExponential(self, e):
+        self.exponential = bool(e)
+
+    def SetGrid(self, Origin, Dims):
+        """the grid's corner (x, y) and its size (nx, ny) in cells; None, None: the box of the live points"""
+        self.origin, self.dims = Origin, Dims
+
+    def _run(self):
+        half, height = pmf_windows(self.cell, self.max_window, self.slope, self.initial, self.max_dist, self.base,
+                                   self.exponential)
+        r = self.result = self.search.Ground(self.cell, half, height, Origin=self.origin, Dims=self.dims)
+        self.surface, self.hag, self.window = r.surface, r.hag, r.window
+        return r.labels, r.sizes, r.ids
