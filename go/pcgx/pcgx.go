@@ -477,6 +477,48 @@ func (k *KDTree) LocalMaxima(radius float32, score []float32) ([]int64, error) {
 	return ids[:int(m)], nil
 }
 
+// BoundaryPoints is what (*KDTree).Boundary returns: the boundary points' ids ascending, and per point in id order the
+// longest cyclic run of empty sectors (64 for an empty mask, -1 where the point is not evaluated), the mask of the
+// sectors a neighbour falls in, and the neighbourhood's size.
+type BoundaryPoints struct {
+	IDs    []int64
+	Gaps   []int32
+	Masks  []uint64
+	Counts []int32
+}
+
+// Boundary returns the points whose radius neighbours leave an angular gap of at least minGap sectors of 5.625 degrees
+// (1..64; 16 is PCL's pi / 2) in the tangent plane of normals, one per point in id order (extension: no reference
+// parity; include/pcgx.h, pcgx_kdtree_boundary).  A true opening of g sectors gives g - 2 < gap < g.
+func (k *KDTree) Boundary(radius float32, normals []mat.Vec3, minGap, minNeighbors int) (*BoundaryPoints, error) {
+	runtime.LockOSThread() // the error text is thread-local on the C side: call and pcgx_last_error on one OS thread
+	defer runtime.UnlockOSThread()
+	defer runtime.KeepAlive(k) // the finalizer must not free the handle while a call is in flight
+	var ln C.int64_t
+	if err := status(C.pcgx_kdtree_len(k.t.h, &ln)); err != nil {
+		return nil, err
+	}
+	n := int(ln)
+	if len(normals) != n {
+		return nil, errors.New("pcgx: one normal per point of the tree is required")
+	}
+	res := &BoundaryPoints{IDs: make([]int64, n), Gaps: make([]int32, n), Masks: make([]uint64, n), Counts: make([]int32, n)}
+	if n == 0 {
+		return res, nil
+	}
+	var m C.int64_t
+	rc := C.pcgx_kdtree_boundary(k.t.h, C.float(radius), (*C.float)(unsafe.Pointer(&normals[0])), C.int32_t(minGap),
+		C.int32_t(minNeighbors), (*C.int64_t)(unsafe.Pointer(&res.IDs[0])), &m, (*C.int32_t)(unsafe.Pointer(&res.Gaps[0])),
+		(*C.uint64_t)(unsafe.Pointer(&res.Masks[0])), (*C.int32_t)(unsafe.Pointer(&res.Counts[0])))
+	runtime.KeepAlive(normals)
+	runtime.KeepAlive(res)
+	if err := status(rc); err != nil {
+		return nil, err
+	}
+	res.IDs = res.IDs[:int(m)]
+	return res, nil
+}
+
 // ISSKeypoints returns the ISS keypoints of the tree's points (Zhong 2009, Open3D's form; extension: no reference
 // parity; include/pcgx.h, pcgx_kdtree_iss_keypoints): ids ascending, and per point in id order the eigenvalues of
 // Normals' covariance at salientRadius (ascending, zero where Normals answers "degenerate") and the saliency (the

@@ -174,6 +174,11 @@ PCGX_API pcgx_status pcgx_debug_walk_stats(const pcgx_kdtree *t, const float *d_
 PCGX_API pcgx_status pcgx_debug_grid_stats(const pcgx_kdtree *t, const float *d_q, int64_t nq, float max_range,
                                            int64_t out[14]);
 
+/* Test aid: where the grid's cells lie: geom = {lo.x, lo.y, lo.z, h, 1 / h}, dims = {nx, ny, nz}.  A point's cell along
+ * an axis is (int)clamp((v - lo) * (1 / h), 0, n - 1), evaluated in float32; a grid row is the cells of one (y, z).
+ * PCGX_E_INVALID for a tree without a grid. */
+PCGX_API pcgx_status pcgx_debug_grid_geometry(const pcgx_kdtree *t, float geom[5], int32_t dims[3]);
+
 /* Test aid: the points' certificates (csrc/knn_grid.hip, grid_cert_kernel), by point id, n floats into host memory.
  * A query whose DistSq to point i is below cert[i] has i as its one nearest base point; 0: no certificate (a point
  * with a twin).  PCGX_E_INVALID when the tree has none (no grid, labelled points). */
@@ -1524,6 +1529,59 @@ PCGX_API pcgx_status pcgx_kdtree_ground_dev(const pcgx_kdtree *t, const float *o
  * that takes its plain loop (above it: doubling in LDS): the boundaries the tests put nx, ny and half across. */
 PCGX_API int32_t pcgx_ground_tile(void);
 PCGX_API int32_t pcgx_ground_loop_max(void);
+
+/* ------------------------------------------- boundary points (extension: no reference parity)
+ * NOT in the reference.  A scan is a surface with edges: the rim where the sensor's view ends, shadows, holes.  A point
+ * sits on such an edge when its neighbours, seen in its tangent plane, leave a wide angular gap -- PCL's
+ * BoundaryEstimation, Open3D's compute_boundary_points.  Over the tree's own points only (the q == NULL convention of
+ * _fpfh and _local_maxima), every array in id order, deleted ids included.  This comment is the contract,
+ * tests/boundary_oracle.py restates it.
+ * Arguments: normals[3 Len()] in id order (what pcgx_kdtree_normals(q == NULL) writes), min_gap in sectors (1..64),
+ *   min_neighbors.
+ * Neighbourhood: N(i) = exactly the set pcgx_kdtree_range_count counts on that handle (float32 DistSq < radius^2, the
+ *   bound strict; grid, forced walk, after DeletePoint).  A deleted point is nobody's neighbour.  count = |N(i)|, a tree
+ *   point counting itself.
+ * Evaluated: point i is evaluated iff i is in N(i) (so a deleted id or a NaN coordinate never is), and its normal's
+ *   three components are finite and not all zero, and count >= max(min_neighbors, 1).  Otherwise mask = 0, gap = -1 and
+ *   the point is no boundary point.  counts[i] is |N(i)| where i is in N(i) and the normal is usable (so also where only
+ *   min_neighbors failed), else 0: nothing is enumerated for a normal that gives no frame.
+ * Frame, float64 from the float32 normal n widened, not normalised, no square root anywhere: e = the unit vector of the
+ *   axis where |n| is smallest (a tie: the lowest axis); u = n x e; v = n x u; each component a difference of two
+ *   products in the cross product's written order.  Normals are expected to be of unit length, which is what the library
+ *   writes: a normal of length L stretches v by L beside u and skews the sectors accordingly.
+ * Direction of a neighbour p seen from q = point i, all float64, fixed order, nothing fused: d = p - q;
+ *   a = (d.x u.x + d.y u.y) + d.z u.z; b likewise with v.  Both are finite, the members of N(i) being finite.
+ *   a == 0 and b == 0: the neighbour has no sector and sets no bit (the point itself, a coincident point, a point on the
+ *   normal's line).
+ * Sector, 64 of 5.625 degrees, each owning its lower border: the quarter turn Q and the rotated (x, y), x > 0, y >= 0:
+ *   Q0: a > 0, b >= 0 -> (a, b);  Q1: a <= 0, b > 0 -> (b, -a);  Q2: a < 0, b <= 0 -> (-a, -b);  Q3: a >= 0, b < 0 ->
+ *   (-b, a).  s = #{k in 1..15 : y >= x T[k]}, each product rounded once, T[k] the float64 nearest tan(k pi / 32), T[8]
+ *   = 1 exactly (csrc/boundary_terms.h writes them out).  sector = 16 Q + s.
+ * Mask and gap: mask = OR of 1 << sector over N(i).  gap = the longest cyclic run of zero bits of mask: 0..63 for a
+ *   non-zero mask, 64 for an evaluated point whose mask is 0.  Point i is a boundary point iff it is evaluated and
+ *   gap >= min_gap.
+ * What the gap means: for a true angular opening g between neighbouring directions and w = 5.625 degrees,
+ *   g / w - 2 < gap < g / w.  So a point flagged at min_gap has an opening wider than min_gap w, and every opening of at
+ *   least (min_gap + 2) w is flagged: with min_gap = 16 (PCL's pi / 2) nothing below 90 degrees and everything from
+ *   101.25 degrees.  Not PCL's or Open3D's bits: they sort angles from atan2 and compare with a float threshold.
+ * Outputs: ids[Len()] holds the boundary points in ascending id, then -1 in every remaining slot
+ *   (pcgx_kdtree_local_maxima's convention), *n_ids their number; gaps[Len()] int32, masks[Len()] uint64 and
+ *   counts[Len()] int32 may each be NULL.
+ * PCGX_E_INVALID: a NULL tree; a radius that is not finite and > 0; min_gap outside 1..64; NULL normals, ids or n_ids
+ *   with Len() > 0.  Len() == 0 is PCGX_OK and writes only *n_ids = 0.  The same input gives the same bits on every call
+ *   (OR and integer + over the set: the visit's order does not enter).  Always computed on the device
+ *   (csrc/boundary.hip): pcgx_kdtree_normals' enumeration once.  Temporaries: Len() bytes of flags and
+ *   4 ceil(Len() / 2048) bytes of tile counts. */
+PCGX_API pcgx_status pcgx_kdtree_boundary(const pcgx_kdtree *t, float radius, const float *normals /* [3 Len()] */,
+                                          int32_t min_gap, int32_t min_neighbors, int64_t *ids /* [Len()] */,
+                                          int64_t *n_ids, int32_t *gaps /* [Len()], may be NULL */,
+                                          uint64_t *masks /* [Len()], may be NULL */,
+                                          int32_t *counts /* [Len()], may be NULL */);
+/* Same, every array device resident (ids and the count are int32 there), enqueued on `stream` (NULL: the library's);
+ * returns without waiting.  d_normals can be what pcgx_kdtree_normals_dev wrote on the same stream. */
+PCGX_API pcgx_status pcgx_kdtree_boundary_dev(const pcgx_kdtree *t, float radius, const float *d_normals, int32_t min_gap,
+                                              int32_t min_neighbors, int32_t *d_ids /* [Len()] */, int32_t *d_n_ids,
+                                              int32_t *d_gaps, uint64_t *d_masks, int32_t *d_counts, void *stream);
 
 /* ------------------------------------------- score poses (extension: no reference parity)
  * NOT in the reference.  pcgx_pose_from_correspondences picks its pose by the inliers among the CORRESPONDENCES; on a

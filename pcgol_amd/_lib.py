@@ -163,6 +163,7 @@ SIGNATURES = {
     "pcgx_debug_icp_grid_stats": (_i32, [_vp, _vp, C.POINTER(_i64)]),
     "pcgx_debug_grid_stats": (_i32, [_vp, _vp, _i64, C.c_float, C.POINTER(_i64)]),
     "pcgx_debug_grid_cert": (_i32, [_vp, _vp, _i64]),
+    "pcgx_debug_grid_geometry": (_i32, [_vp, _vp, _vp]),
     "pcgx_kdtree_dump": (_i32, [_vp, _vp, _i64, C.POINTER(_i64)]),
     "pcgx_kdtree_delete_points": (_i32, [_vp, _vp, _i64]),
     "pcgx_kdtree_live_count": (_i32, [_vp, C.POINTER(_i64)]),
@@ -296,6 +297,8 @@ SIGNATURES = {
     "pcgx_kdtree_ground_dev": (_i32, [_vp, _vp, _vp, _f32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp]),
     "pcgx_ground_tile": (_i32, []),
     "pcgx_ground_loop_max": (_i32, []),
+    "pcgx_kdtree_boundary": (_i32, [_vp, _f32, _vp, _i32, _i32, _vp, C.POINTER(_i64), _vp, _vp, _vp]),
+    "pcgx_kdtree_boundary_dev": (_i32, [_vp, _f32, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
     "pcgx_kdtree_score_poses": (_i32, [_vp, _vp, _i64, _vp, _i64, _f32, _vp, _vp, C.POINTER(_i64), _vp]),
     "pcgx_kdtree_score_poses_dev": (_i32, [_vp, _vp, _i64, _vp, _i64, _f32, _vp, _vp, _vp, _vp]),
     "pcgx_score_tile": (_i32, []),

@@ -97,6 +97,20 @@ __global__ __launch_bounds__(256) void keypoints_tail_kernel(const int32_t *__re
   if (j < n && j >= (int64_t)*n_ids) ids[j] = -1;
 }
 
+// One flag byte per id -> the flagged ids in ascending order, -1 in every remaining slot, their number in *d_n_ids.
+// tile_count: ceil(n / kRunTile) words of the caller's.  boundary.hip compacts its flags through this too.
+pcgx_status flags_to_ids_enqueue(const uint8_t *d_flag, int64_t n, uint32_t *tile_count, int32_t *d_ids, int32_t *d_n_ids,
+                                 hipStream_t st) {
+  const int ntiles = (int)((n + kRunTile - 1) / kRunTile);
+  hipLaunchKernelGGL(keypoints_count_kernel, dim3(ntiles), dim3(256), 0, st, d_flag, n, tile_count);
+  hipLaunchKernelGGL(keypoints_scan_kernel, dim3(1), dim3(1024), 0, st, tile_count, ntiles, (uint32_t *)d_n_ids);
+  hipLaunchKernelGGL(keypoints_write_kernel, dim3(ntiles), dim3(256), 0, st, d_flag, n, (const uint32_t *)tile_count, d_ids);
+  hipLaunchKernelGGL(keypoints_tail_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const int32_t *)d_n_ids, n,
+                     d_ids);
+  PCGX_HIP_TRY(hipGetLastError());
+  return PCGX_OK;
+}
+
 template <int kSrc>
 void maxima_launch(const pcgx_kdtree *t, const TreeView &tv, const XTreeView &xv, const QuerySource &Q, float bound,
                    const float *d_score, uint8_t *d_flag, size_t stack_bytes, hipStream_t st) {
@@ -125,14 +139,7 @@ pcgx_status maxima_enqueue(const pcgx_kdtree *t, float radius, const float *d_sc
   if (src == kRangeXWalk) maxima_launch<kRangeXWalk>(t, tv, xv, Q, bound, d_score, d_flag, xwalk_stack_bytes(xv, kKeyBlock), st);
   else if (src == kRangeGrid) maxima_launch<kRangeGrid>(t, tv, xv, Q, bound, d_score, d_flag, 0, st);
   else maxima_launch<kRangeWalk>(t, tv, xv, Q, bound, d_score, d_flag, walk_stack_bytes(tv, kKeyBlock), st);
-  hipLaunchKernelGGL(keypoints_count_kernel, dim3(ntiles), dim3(256), 0, st, (const uint8_t *)d_flag, n, tile_count);
-  hipLaunchKernelGGL(keypoints_scan_kernel, dim3(1), dim3(1024), 0, st, tile_count, ntiles, (uint32_t *)d_n_ids);
-  hipLaunchKernelGGL(keypoints_write_kernel, dim3(ntiles), dim3(256), 0, st, (const uint8_t *)d_flag, n,
-                     (const uint32_t *)tile_count, d_ids);
-  hipLaunchKernelGGL(keypoints_tail_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, (const int32_t *)d_n_ids, n,
-                     d_ids);
-  PCGX_HIP_TRY(hipGetLastError());
-  return PCGX_OK;
+  return flags_to_ids_enqueue(d_flag, n, tile_count, d_ids, d_n_ids, st);
 }
 
 }  // namespace pcgx

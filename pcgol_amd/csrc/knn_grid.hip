@@ -708,3 +708,17 @@ extern "C" pcgx_status pcgx_debug_grid_stats(const pcgx_kdtree *t, const float *
   out[4] = (int64_t)(((uint64_t)c[21] << 32) | c[20]);  // lane-slots the scan loops ran (64 per round of 4 records, idle lanes included)
   return PCGX_OK;
 }
+
+// Test aid: where the grid's cells lie, for a test that has to know which points share a grid row.  geom = {lo.x, lo.y,
+// lo.z, h, inv_h}, dims = {nx, ny, nz}; a point's cell along an axis is (int)clamp((v - lo) * inv_h, 0, n - 1) in
+// float32 (grid_cell, knn_grid.h).
+extern "C" pcgx_status pcgx_debug_grid_geometry(const pcgx_kdtree *t, float geom[5], int32_t dims[3]) {
+  PCGX_API_LOCK();
+  if (!t || !geom || !dims) return pcgx::fail(PCGX_E_INVALID, "pcgx_debug_grid_geometry: bad argument");
+  if (!pcgx::grid_enabled(t)) return pcgx::fail(PCGX_E_INVALID, "pcgx_debug_grid_geometry: the tree has no grid");
+  for (int k = 0; k < 3; k++) geom[k] = t->grid.lo[k];
+  geom[3] = t->grid.h;
+  geom[4] = t->grid.inv_h;
+  dims[0] = t->grid.nx, dims[1] = t->grid.ny, dims[2] = t->grid.nz;
+  return PCGX_OK;
+}

@@ -1,6 +1,6 @@
 // radius_visit.h -- how a kernel consumes a radius neighbourhood: one visitor over the three enumerations of
-// range_enum.h, one query per lane.  normals.hip, mls.hip, keypoints.hip and fpfh.hip enumerate through it; range.hip
-// (counts, offsets, fills) and knearest.hip (a bound that shrinks) drive RowScan and the walks themselves.
+// range_enum.h, one query per lane.  normals.hip, mls.hip, keypoints.hip, fpfh.hip and boundary.hip enumerate through
+// it; range.hip (counts, offsets, fills) and knearest.hip (a bound that shrinks) drive RowScan and the walks themselves.
 //
 // The contract, stated here and nowhere else:
 //   * The set is every record p with ref_dist_sq(p, q) < bound, the bound STRICT, exactly what pcgx_kdtree_range_count

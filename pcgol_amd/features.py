@@ -1,6 +1,8 @@
 """Matching of FPFH descriptors (extension: no reference counterpart; include/pcgx.h, "FPFH matching"): for every row
 of one descriptor array the nearest and second nearest row of another, brute force on the GPU, and the correspondence
-list feature-based coarse alignment starts from.  Descriptors are (n, 33) float32, what KDTree.FPFH returns first."""
+list feature-based coarse alignment starts from.  Descriptors are (n, 33) float32, what KDTree.FPFH returns first.
+Below them, boundary points in PCL's wording (BoundaryEstimation over KDTree.Boundary; include/pcgx.h, "boundary
+points")."""
 import numpy as np
 
 from . import _lib as L
@@ -66,3 +68,70 @@ def CorrespondencesDev(d_a, na, d_b, nb, d_src_ids, d_dst_ids, d_n_pairs, MaxRat
         L.ptr(int(d_a)) if d_a else None, int(na), L.ptr(int(d_b)) if d_b else None, int(nb), float(r * r),
         1 if Mutual else 0, L.ptr(int(d_src_ids)), L.ptr(int(d_dst_ids)), L.ptr(int(d_n_pairs)),
         L.ptr(stream) if stream else None))
+
+
+# ------------------------------------------------------------------------------------------------ boundary points
+# (extension: no reference counterpart; include/pcgx.h, "boundary points")
+
+BOUNDARY_SECTORS = 64
+
+
+def boundary_min_gap(angle):
+    """The MinGap (sectors of 2 pi / 64 = 5.625 degrees) of an angle in radians: ceil(angle / (2 pi / 64)), clamped to
+    1..64.  The gap of a point is a count of empty sectors, not an angle: a true angular opening g between neighbouring
+    directions gives g / w - 2 < gap < g / w with w one sector.  So a point flagged at MinGap has an opening wider than
+    MinGap w, and every opening of at least (MinGap + 2) w is flagged; in between it depends on where the sector borders
+    fall.  boundary_min_gap(pi / 2) = 16: nothing below 90 degrees is flagged and everything from 101.25 degrees is."""
+    sectors = int(np.ceil(float(angle) / (2.0 * np.pi / BOUNDARY_SECTORS)))
+    return min(max(sectors, 1), BOUNDARY_SECTORS)
+
+
+class BoundaryEstimation:
+    """KDTree.Boundary in PCL's wording (pcl::BoundaryEstimation): the points of `tree` whose neighbours within the
+    search radius leave an angular gap wider than the threshold in the tangent plane of the input normals."""
+
+    def __init__(self, tree):
+        self._tree = tree
+        self._radius = None
+        self._normals = None
+        self._min_gap = boundary_min_gap(np.pi / 2.0)  # PCL's default angle threshold
+        self._min_neighbors = 1
+
+    def SetRadiusSearch(self, radius):
+        self._radius = float(radius)
+
+    def SetInputNormals(self, normals):
+        self._normals = L.f32c(normals).reshape(-1, 3)
+
+    def SetAngleThreshold(self, angle):
+        """radians; applied in whole sectors (boundary_min_gap)"""
+        self._min_gap = boundary_min_gap(angle)
+
+    def SetMinNeighbors(self, min_neighbors):
+        self._min_neighbors = int(min_neighbors)
+
+    def Compute(self):
+        """-> (ids int64 ascending, gaps int32 (n,), masks uint64 (n,), counts int32 (n,)), as KDTree.Boundary"""
+        if self._radius is None or self._normals is None:
+            raise ValueError("SetRadiusSearch and SetInputNormals come first")
+        return self._tree.Boundary(self._radius, self._normals, self._min_gap, self._min_neighbors)
+
+    def Loops(self, group_radius, MinSize=1):
+        """The connected outlines among the boundary points: the outer rim and every hole as one group each ->
+        (labels int64 (n,), sizes int64 (C,), ids int64 (sum(sizes),)) in the tree's ids, the largest group first:
+        labels is -1 off the boundary and for a group below MinSize, ids holds group 0's members ascending, then group
+        1's, ...  A host-level convenience, not a kernel: it reads the boundary ids and their number back, builds a
+        second KDTree over those points and takes its Clusters(group_radius).  The points of a loop are not ordered
+        along the outline."""
+        from . import kdtree
+        ids = self.Compute()[0]
+        n = self._tree.Len()
+        labels = np.full(n, -1, np.int64)
+        if len(ids) == 0:
+            return labels, np.zeros(0, np.int64), np.zeros(0, np.int64)
+        pts = np.empty((len(ids), 3), np.float32)
+        L.check(L.lib().pcgx_kdtree_points(self._tree._h, L.ptr(ids), len(ids), L.ptr(pts)))
+        sub_labels, sizes, sub_ids = kdtree.New(pts).Clusters(float(group_radius), MinSize=MinSize)
+        kept = sub_labels >= 0
+        labels[ids[kept]] = sub_labels[kept]
+        return labels, sizes, ids[sub_ids]  # (ids ascends, so a group's members stay ascending)

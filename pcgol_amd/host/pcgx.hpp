@@ -268,6 +268,30 @@ class KDTree {  // pc/storage/kdtree/kdtree.go:14-23
     r.ids.resize((size_t)m);
     return r;
   }
+  // Boundary points (extension: no reference parity; include/pcgx.h, pcgx_kdtree_boundary): the points whose radius
+  // neighbours leave an angular gap of at least minGap sectors of 5.625 degrees in the tangent plane of `normals` (one
+  // per point in id order).  ids ascending; gaps: the longest cyclic run of empty sectors, 64 for an empty mask, -1 where
+  // the point is not evaluated; masks: bit s set where a neighbour falls in sector s; counts: the neighbourhood's size.
+  struct BoundaryResult {
+    std::vector<int64_t> ids;
+    std::vector<int32_t> gaps, counts;
+    std::vector<uint64_t> masks;
+  };
+  BoundaryResult Boundary(float radius, const std::vector<Vec3> &normals, int32_t minGap = 16,
+                          int32_t minNeighbors = 1) const {
+    const int64_t n = Len();
+    if ((int64_t)normals.size() != n) throw Error(PCGX_E_INVALID, "one normal per point of the tree is required");
+    BoundaryResult r;
+    r.ids.resize((size_t)n);
+    r.gaps.resize((size_t)n);
+    r.masks.resize((size_t)n);
+    r.counts.resize((size_t)n);
+    int64_t m = 0;
+    check(pcgx_kdtree_boundary(h_.get(), radius, n ? normals[0].data() : nullptr, minGap, minNeighbors, r.ids.data(), &m,
+                               r.gaps.data(), r.masks.data(), r.counts.data()));
+    r.ids.resize((size_t)m);
+    return r;
+  }
   // Cluster extraction (extension: no reference parity; include/pcgx.h, pcgx_kdtree_clusters): the connected
   // components of the radius graph over the tree's own points, kept when max(minSize, 1) <= size (<= maxSize unless 0),
   // largest first, equal sizes by smallest id.  normals (empty: none): an edge also needs |n_i . n_j| >= minCos

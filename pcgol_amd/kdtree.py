@@ -1,7 +1,7 @@
 """pc/storage/kdtree mirror: KDTree on the GPU behind the storage.Search shape
 (pc/storage/search.go:13-17): Vec3At / Len / Nearest, plus batched NearestBatch, and extensions with no
 reference counterpart: surface normals (Normals), moving-least-squares smoothing (MLS), FPFH descriptors
-(FPFH, FPFHAt), keypoints (LocalMaxima, ISSKeypoints), cluster extraction (Clusters), density clusters (DBSCAN), plane segmentation (Planes), cylinder and sphere segmentation (Shapes), ground segmentation (Ground), per-group
+(FPFH, FPFHAt), keypoints (LocalMaxima, ISSKeypoints), cluster extraction (Clusters), density clusters (DBSCAN), plane segmentation (Planes), cylinder and sphere segmentation (Shapes), ground segmentation (Ground), boundary points (Boundary), per-group
 geometry (GroupStats), k nearest neighbours (KNearest) and their covariances (Covariances)."""
 import collections
 import ctypes as C
@@ -367,6 +367,38 @@ class KDTree:
             self._h, float(SalientRadius), float(NonMaxRadius), float(Gamma21), float(Gamma32), int(MinNeighbors),
             L.ptr(int(d_eigenvalues)) if d_eigenvalues else None, L.ptr(int(d_saliency)) if d_saliency else None,
             L.ptr(int(d_ids)), L.ptr(int(d_n_ids)), L.ptr(stream) if stream else None))
+
+    # -- extension (no reference parity): boundary points, where a scanned surface ends
+    def Boundary(self, radius, Normals, MinGap=16, MinNeighbors=1):
+        """The points whose radius neighbours (DistSq < radius^2, Range's set) leave an angular gap of at least MinGap
+        sectors of 5.625 degrees in the tangent plane of Normals (n,3) float32 in id order -> (ids int64 ascending, gaps
+        int32 (n,), masks uint64 (n,), counts int32 (n,)).  masks: bit s set where a neighbour's direction falls in
+        sector s; gaps: the longest cyclic run of zero bits, 64 for an empty mask, -1 where the point is not evaluated
+        (deleted, a NaN coordinate, a non-finite or zero normal, fewer than max(MinNeighbors, 1) neighbours).  A true
+        opening of g sectors gives g - 2 < gap < g (include/pcgx.h, pcgx_kdtree_boundary)."""
+        n = self.Len()
+        nrm = L.f32c(Normals).reshape(-1, 3)
+        if len(nrm) != n:
+            raise ValueError("one normal per point of the tree is required")
+        ids = np.empty(n, np.int64)
+        gaps = np.empty(n, np.int32)
+        masks = np.empty(n, np.uint64)
+        counts = np.empty(n, np.int32)
+        cnt = C.c_int64()
+        L.check(L.lib().pcgx_kdtree_boundary(self._h, float(radius), L.ptr(nrm), int(MinGap), int(MinNeighbors), L.ptr(ids),
+                                             C.byref(cnt), L.ptr(gaps), L.ptr(masks), L.ptr(counts)))
+        return ids[:cnt.value], gaps, masks, counts
+
+    def BoundaryDev(self, radius, d_normals, d_ids, d_n_ids, d_gaps=0, d_masks=0, d_counts=0, MinGap=16, MinNeighbors=1,
+                    stream=0):
+        """Device-resident Boundary: raw device addresses (e.g. torch .data_ptr()); d_normals float32 [3 Len()] (what
+        NormalsDev wrote on the same stream), d_ids int32 [Len()] (the boundary points ascending, then -1), d_n_ids one
+        int32, d_gaps int32 [Len()], d_masks uint64 [Len()], d_counts int32 [Len()] (each optional).  Enqueued on
+        `stream`, returns without waiting."""
+        opt = lambda a: L.ptr(int(a)) if a else None  # noqa: E731
+        L.check(L.lib().pcgx_kdtree_boundary_dev(
+            self._h, float(radius), L.ptr(int(d_normals)), int(MinGap), int(MinNeighbors), L.ptr(int(d_ids)),
+            L.ptr(int(d_n_ids)), opt(d_gaps), opt(d_masks), opt(d_counts), L.ptr(stream) if stream else None))
 
     # -- extension (no reference parity): clusters, the connected components of the radius graph
     def Clusters(self, radius, Normals=None, MinCos=0.0, Oriented=False, Curvature=None, MaxCurvature=0.0, MinSize=1,
