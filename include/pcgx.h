@@ -79,12 +79,13 @@ PCGX_API const char *pcgx_version(void);
 /* The layout version of this header's structs and fixed-size output arrays (pcgx_icp_params gained sums_mode in 3;
  * pcgx_debug_icp_strict_stats writes 64 words since 3; 4: device slots, pcgx_icp_fit_multi, pcgx_debug_voxel_stats;
  * 5: pcgx_debug_shard_stats, pcgx_prof_read_max, words 48 .. 63 of pcgx_debug_icp_strict_stats re-assigned;
- * 6: pcgx_debug_ring_kinds, pcgx_debug_host_walks, pcgx_debug_icp_one_launch).
+ * 6: pcgx_debug_ring_kinds, pcgx_debug_host_walks, pcgx_debug_icp_one_launch;
+ * 7: pcgx_debug_grid_runner, pcgx_debug_icp_runner_pairs).
  * A binding built against another version of the header must not call into the library: the mirrors (go/pcgx,
  * host/pcgx.hpp, pcgol_amd/_lib.py) compare PCGX_ABI_VERSION with pcgx_abi_version() when they load it.
  * pcgx_icp_params_init zeroes a parameter block of THIS version (all defaults); sizeof_params is the caller's
  * sizeof(pcgx_icp_params): a mismatch is PCGX_E_INVALID instead of a read past a shorter struct. */
-#define PCGX_ABI_VERSION 6
+#define PCGX_ABI_VERSION 7
 PCGX_API int32_t pcgx_abi_version(void);
 /* Block until all work enqueued on `stream` (NULL = library stream) is done. */
 PCGX_API pcgx_status pcgx_sync(void *stream);
@@ -183,6 +184,11 @@ PCGX_API pcgx_status pcgx_debug_grid_geometry(const pcgx_kdtree *t, float geom[5
  * A query whose DistSq to point i is below cert[i] has i as its one nearest base point; 0: no certificate (a point
  * with a twin).  PCGX_E_INVALID when the tree has none (no grid, labelled points). */
 PCGX_API pcgx_status pcgx_debug_grid_cert(const pcgx_kdtree *t, float *cert, int64_t n);
+/* ... and their runner-up records, made beside the certificates: runner[4 i ..] = {the nearest other point n1 of point
+ * i, cert2}, runner_id[i] = n1's id.  A query whose DistSq to point i is below cert2 has i or n1 as its nearest base
+ * point, whichever computes nearer; cert2 = 0: no record.  *below: ICP pairs carry the record where cert[i] is below it
+ * (PCGX_GRID_RUNNER_BELOW, in cell edges; +inf: every pair).  +20 bytes of device memory per base point. */
+PCGX_API pcgx_status pcgx_debug_grid_runner(const pcgx_kdtree *t, float *runner, uint32_t *runner_id, float *below, int64_t n);
 
 /* Measurement aid: what the grid pass of the session's NEXT iteration would read, without changing
  * the session: out = {targets, targets left to the walk, point records read, cell-bound words read,
@@ -200,6 +206,17 @@ PCGX_API pcgx_status pcgx_debug_icp_grid_stats(pcgx_icp_session *s, void *stream
  * chunks), [62]: walkers that gave up that wait and walked the earlier chunks alone, [63]: workgroups of the summary
  * kernel that gave up its exchange (both 0 in a healthy run: the tests require it). */
 PCGX_API pcgx_status pcgx_debug_icp_strict_stats(pcgx_icp_session *s, void *stream, int64_t out[64]);
+/* Words [47] and [59] of the above belong to the certified steps (the summary kernel tests every pair against its
+ * partner's certificate): [47] low word = certified steps, high word = those enqueued again; [59] = targets searched
+ * inside them.
+ * Test / measurement aid for level 2 of those certificates (PCGX_ICP_CERT2): a strict session's pairs in the caller's
+ * target order, {partner, its certificate (-1: no pair)}, and the runner words beside them (4 nt floats, 4 nt floats, nt
+ * words into host memory; all three NULL: none), and counts (may be NULL) = since the last call {targets that failed
+ * their certificate and kept their partner on its runner-up's record, targets moved to the runner-up, all that failed
+ * their certificate while level 2 was on} -- the third less the first two is what [59] counted in those steps.
+ * PCGX_E_INVALID for a session that keeps no runner words. */
+PCGX_API pcgx_status pcgx_debug_icp_runner_pairs(pcgx_icp_session *s, void *stream, float *match_caller, float *runner_caller,
+                                                 uint32_t *runner_id_caller, int64_t nt, int64_t counts[3]);
 
 /* The strict-sum pipeline in plain host loops (no GPU): *out = the sequential float32 sum
  * 0 + t0 + t1 + ... computed the way the strict kernels compute it; stats as in csrc/strict_sum.h

@@ -135,7 +135,7 @@ class IcpStat(C.Structure):
 
 # name -> (restype, argtypes); the complete export list of include/pcgx.h
 _vp, _i64, _i32, _u32, _f32, _sz = C.c_void_p, C.c_int64, C.c_int32, C.c_uint32, C.c_float, C.c_size_t
-ABI_VERSION = 6   # include/pcgx.h PCGX_ABI_VERSION
+ABI_VERSION = 7   # include/pcgx.h PCGX_ABI_VERSION
 
 SIGNATURES = {
     "pcgx_init": (_i32, [_i32]),
@@ -214,6 +214,8 @@ SIGNATURES = {
     "pcgx_icp_session_step_sharded": (_i32, [_vp, _vp, _vp]),
     "pcgx_icp_fit_sharded": (_i32, [_vp, _vp, _i64, C.POINTER(IcpParams), _vp, _vp, C.POINTER(IcpStat)]),
     "pcgx_debug_icp_strict_stats": (_i32, [_vp, _vp, _vp]),
+    "pcgx_debug_icp_runner_pairs": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _vp]),
+    "pcgx_debug_grid_runner": (_i32, [_vp, _vp, _vp, _vp, _i64]),
     "pcgx_debug_strict_sum_host": (_i32, [_vp, _i64, _i32, _vp, _vp]),
     "pcgx_debug_strict_sum_dev": (_i32, [_vp, _i64, _vp, _vp]),
     "pcgx_icp_session_result": (_i32, [_vp, _vp, _vp, C.POINTER(IcpStat), C.POINTER(_i32)]),

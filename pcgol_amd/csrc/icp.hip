@@ -159,7 +159,8 @@ __global__ __launch_bounds__(kIcpBlock) void icp_corr_kernel(
     const float4 *__restrict__ normals, uint32_t *__restrict__ walk_list, uint32_t *__restrict__ walk_count,
     int32_t n_grid_rows, const uint32_t *__restrict__ orig_of = nullptr, float4 *__restrict__ match_caller = nullptr,
     StrictWork strict_w = StrictWork(), int32_t tile_sums = 0, float *__restrict__ match_cert = nullptr,
-    const float *__restrict__ cert_by_id = nullptr) {
+    const float *__restrict__ cert_by_id = nullptr, RunnerView runner_grid = RunnerView(),
+    float4 *__restrict__ runner_caller = nullptr, uint32_t *__restrict__ runner_id_caller = nullptr) {
   static_assert(!(kGrid && kMinDist), "the grid answers exact-mode queries only");
   extern __shared__ uint32_t s_stack[];
   __shared__ uint32_t s_next_chunk;
@@ -257,9 +258,12 @@ __global__ __launch_bounds__(kIcpBlock) void icp_corr_kernel(
   auto emit = [&](int64_t i, const float4 &bp, float best_d) {
     const float4 rec = make_float4(bp.x, bp.y, bp.z, __float_as_int(bp.w) >= 0 ? best_d : -1.0f);
     match[i] = rec;
-    if (match_caller)  // strict sums: see icp_grid_kernel (w: the partner's certificate)
-      match_caller[orig_of[i]] = make_float4(rec.x, rec.y, rec.z,
-                                             rec.w >= 0.0f ? (cert_by_id ? cert_by_id[__float_as_uint(bp.w)] : 0.0f) : -1.0f);
+    if (match_caller) {  // strict sums: see icp_grid_kernel (w: the partner's certificate, and its runner words beside it)
+      const uint32_t c = orig_of[i];
+      const float cert = rec.w >= 0.0f ? (cert_by_id ? cert_by_id[__float_as_uint(bp.w)] : 0.0f) : -1.0f;
+      match_caller[c] = make_float4(rec.x, rec.y, rec.z, cert);
+      if (rec.w >= 0.0f) runner_words_store(runner_grid, runner_caller, runner_id_caller, c, cert, cert_by_id ? __float_as_int(bp.w) : -1);
+    }
     if (kPlane) match_id[i] = __float_as_uint(bp.w);
     // (the walked partner's certificate, for the next iteration's grid pass: icp_grid_kernel)
     if (match_cert) match_cert[i] = (cert_by_id && __float_as_int(bp.w) >= 0) ? cert_by_id[__float_as_uint(bp.w)] : 0.0f;
@@ -326,7 +330,9 @@ __global__ __launch_bounds__(kIcpGridBlock) void icp_grid_kernel(
     uint32_t *__restrict__ walk_list, uint32_t *__restrict__ walk_count, uint32_t n_corr_blocks,
     double *__restrict__ block_partials, unsigned long long *__restrict__ trace = nullptr,
     const uint32_t *__restrict__ orig_of = nullptr, float4 *__restrict__ match_caller = nullptr,
-    float *__restrict__ match_cert = nullptr, int caller_has_pairs = 0, int walk_follows = 1, int test_force_walk = 0) {
+    float *__restrict__ match_cert = nullptr, int caller_has_pairs = 0, int walk_follows = 1, int test_force_walk = 0,
+    float4 *__restrict__ runner_caller = nullptr, uint32_t *__restrict__ runner_id_caller = nullptr,
+    RunnerView runner_view = RunnerView()) {
   constexpr int NS = kPlane ? (int)P_COUNT : (int)S_COUNT;
   __shared__ float s_terms[NS][kIcpGridBlock + 16];  // + 16: the kSub-lane groups of one wave land on different banks
   // ("done" is looked at behind the target's loads, which it would only hold up: a workgroup of this kernel is five
@@ -414,7 +420,9 @@ __global__ __launch_bounds__(kIcpGridBlock) void icp_grid_kernel(
       // (w: a pair without a certificate, until the walk writes it with its certificate)
       if (!kSums && match_caller) {
         const bool seen = __float_as_int(best.w) >= 0;
-        match_caller[orig_of[i]] = make_float4(best.x, best.y, best.z, seen ? 0.0f : -1.0f);
+        const uint32_t c = orig_of[i];
+        match_caller[c] = make_float4(best.x, best.y, best.z, seen ? 0.0f : -1.0f);
+        if (seen) runner_words_store(runner_view, runner_caller, runner_id_caller, c, 0.0f, -1);
       }
     } else {
       const bool found = __float_as_int(best.w) >= 0;
@@ -428,8 +436,12 @@ __global__ __launch_bounds__(kIcpGridBlock) void icp_grid_kernel(
       // kernel tests the next pair against: strict.hip, CertifiedTerms; the terms' reader forms the distance from the
       // points, strict_terms.h, pair_terms, and looks at w >= 0 only)
       if (!kSums && match_caller && !(kept && caller_has_pairs)) {
-        const float c = kept ? pm_cert : ((use_cert && v == GRID_FOUND && found) ? grid.cert[__float_as_uint(best.w)] : 0.0f);
-        match_caller[orig_of[i]] = make_float4(bp.x, bp.y, bp.z, found ? c : -1.0f);  // (a kept pair is there already)
+        const bool fresh = !kept && use_cert && v == GRID_FOUND && found;  // (a new partner with a certificate)
+        const float c = kept ? pm_cert : (fresh ? grid.cert[__float_as_uint(best.w)] : 0.0f);
+        const uint32_t ci = orig_of[i];
+        match_caller[ci] = make_float4(bp.x, bp.y, bp.z, found ? c : -1.0f);  // (a kept pair is there already)
+        // (the partner's runner words beside it; a pair kept here has lost its id: it stands without a record)
+        if (found) runner_words_store(runner_view, runner_caller, runner_id_caller, ci, c, fresh ? __float_as_int(best.w) : -1);
       }
       if (kPlane && !kept) match_id[i] = __float_as_uint(best.w);
       if (found && kSums) {  // correspondence.go:27-29
@@ -747,6 +759,7 @@ struct pcgx_icp_session {
   uint32_t *d_pos_of = nullptr;  // [nt] position of the caller's target i in the session's order
   uint32_t *d_orig_of = nullptr;      // strict sums: [nt] the caller's index of the target at a position
   float4 *d_match_caller = nullptr;   // strict sums: match[] in the caller's target order
+  float4 *d_runner_caller = nullptr;  // ... and the partners' runner words beside it (level 2 of the certificates: RunnerWords)
   bool caller_order_fresh = false;    // the last step left every pair in d_match_caller as well (decide_step; small_steps: not)
   int strict = 0;                // sequential float32 sums: 1 = in parallel (strict.hip), 2 = one wave (icp_strict_sums_kernel)
   bool strict_explicit = false;  // asked for by name (set_strict, PCGX_SUMS_REFERENCE_CHAIN, the environment): a sharded step refuses
@@ -1247,6 +1260,14 @@ static int icp_knob(const char *name, int def, int lo, int hi) {
   return def;
 }
 
+// Level 2 of the certificates (PCGX_ICP_CERT2; strict.hip, certified_level2): the pairs carry their partners' runner-up
+// records and a pair that fails its certificate is kept or flipped on them.  1, the default (0: off -- no runner words,
+// the summary kernel without the test): 1.45 us of the C4 step, DESIGN 3.1.
+static bool cert2_knob() {
+  static const bool on = icp_knob("PCGX_ICP_CERT2", 1, 0, 1) != 0;
+  return on;
+}
+
 // The knobs of a step (icp_step_plan.h), read from the environment once per process, at its first step.
 static const StepKnobs &step_knobs() {
   static const StepKnobs knobs = [] {
@@ -1297,6 +1318,17 @@ static pcgx_status decide_step(pcgx_icp_session *s, hipStream_t st, bool may_spe
       } else {
         hipLaunchKernelGGL(invert_positions_kernel, dim3((unsigned)((s->nt + 255) / 256)), dim3(256), 0, st,
                            (const uint32_t *)s->d_pos_of, s->nt, s->d_orig_of);
+        // the pairs' runner words, from the same step on as the pairs themselves (not required: level 2 is then off)
+        if (cert2_knob() && grid_enabled(s->base) && s->base->runner_view.runner != nullptr) {
+          e = session_alloc(s, &s->d_runner_caller, RunnerWords::bytes(s->nt));
+          // (no record anywhere, cert2 = 0, until the pairs' writers say otherwise)
+          if (e == hipSuccess) e = hipMemsetAsync(s->d_runner_caller, 0, RunnerWords::bytes(s->nt), st);
+          if (e != hipSuccess) {
+            (void)hipGetLastError();
+            s->owned.give_up(s->d_runner_caller);
+            s->d_runner_caller = nullptr;
+          }
+        }
       }
     }
     PCGX_TRY(ensure_strict_buf(s, st));
@@ -1356,6 +1388,9 @@ static pcgx_status enqueue_corr(pcgx_icp_session *s, hipStream_t st, const StepP
   const uint32_t *orig_of = p.write_caller ? s->d_orig_of : nullptr;
   float4 *match_caller = p.write_caller ? s->d_match_caller : nullptr;
   float *cert = p.cert ? s->d_match_cert : nullptr;
+  // (the runner words go with the certificates: without them no step is a certified one, and nothing reads the words)
+  float4 *runner_caller = p.write_caller && p.cert ? s->d_runner_caller : nullptr;
+  uint32_t *runner_id_caller = runner_caller ? RunnerWords{runner_caller, s->nt}.ids() : nullptr;
   const bool grid = p.corr != kCorrWalk;
   if (grid) {
     ProfScope prof_grid(PCGX_PROF_ICP_GRID, st);
@@ -1365,7 +1400,7 @@ static pcgx_status enqueue_corr(pcgx_icp_session *s, hipStream_t st, const StepP
                          y, z, s->nt, s->d_state, s->kp, s->d_match, s->d_match_id, (const float4 *)s->d_normals,
                          s->d_first_leaf, s->d_walk_list, s->d_walk_count, (uint32_t)p.n_corr, s->d_partials,
                          (unsigned long long *)nullptr, orig_of, match_caller, cert, p.grid_has_caller_pairs ? 1 : 0,
-                         p.no_walk ? 0 : 1, strict_grid ? k.test_force_walk : 0);
+                         p.no_walk ? 0 : 1, strict_grid ? k.test_force_walk : 0, runner_caller, runner_id_caller, s->base->runner_view);
     };
     if (s->gicp) launch(icp_grid_kernel<true, false, false>, kIcpGridBlock);  // (pairs and ids only)
     else if (s->plane) launch(icp_grid_kernel<true>, kIcpGridBlock);
@@ -1385,7 +1420,7 @@ static pcgx_status enqueue_corr(pcgx_icp_session *s, hipStream_t st, const StepP
     hipLaunchKernelGGL(kernel, dim3(p.n_corr), dim3(kIcpBlock), lds, st, tv, x, y, z, s->nt, s->d_state, s->kp, s->d_match,
                        s->d_first_leaf, s->d_partials, s->d_match_id, (const float4 *)s->d_normals, s->d_walk_list,
                        s->d_walk_count, (int32_t)((s->nt + kIcpGridBlock - 1) / kIcpGridBlock), orig_of, match_caller, strict_w,
-                       (int32_t)(p.tile_sums ? 1 : 0), cert, s->base->grid.cert);
+                       (int32_t)(p.tile_sums ? 1 : 0), cert, s->base->grid.cert, s->base->runner_view, runner_caller, runner_id_caller);
   };
   // (a strict session's kernels form no float64 sums: kSums false)
   if (s->gicp) {
@@ -1431,6 +1466,10 @@ static pcgx_status enqueue_sums(pcgx_icp_session *s, hipStream_t st, const StepP
       C.match = s->d_match;
       C.match_cert = s->d_match_cert;
       C.pos_of = s->d_pos_of;
+      // level 2 (cert2_knob): pairs that fail their certificate are kept or flipped on the runner-up's
+      static const bool cert2_on = cert2_knob();
+      C.runner = s->base->runner_view;
+      C.runner_caller = cert2_on ? s->d_runner_caller : nullptr;
       C.test_force_walk = step_knobs().test_fused_search;
       C.test_force_grid_walk = step_knobs().test_fused_grid_walk;
     }
@@ -1509,6 +1548,35 @@ extern "C" pcgx_status pcgx_debug_icp_strict_stats(pcgx_icp_session *s, void *st
   unsigned long long h[64];
   PCGX_TRY(strict_read_debug(s->strict_buf, h, pick_stream(stream)));
   for (int k = 0; k < 64; k++) out[k] = (int64_t)h[k];
+  return PCGX_OK;
+}
+
+// Test / measurement aid: the pairs in the caller's order with their runner words, and level 2's counts since the last
+// call (see include/pcgx.h).
+extern "C" pcgx_status pcgx_debug_icp_runner_pairs(pcgx_icp_session *s, void *stream, float *match_caller, float *runner_caller,
+                                                   uint32_t *runner_id_caller, int64_t nt, int64_t counts[3]) {
+  PCGX_API_LOCK();
+  if (!s || !match_caller != !runner_caller || !match_caller != !runner_id_caller || (match_caller && nt != s->nt) || (!match_caller && !counts))
+    return fail(PCGX_E_INVALID, "pcgx_debug_icp_runner_pairs: bad argument");
+  if (!s->d_match_caller || !s->d_runner_caller)
+    return fail(PCGX_E_INVALID, "pcgx_debug_icp_runner_pairs: the session keeps no runner words");
+  hipStream_t st = pick_stream(stream);
+  PCGX_TRY(settle(s, st));
+  if (counts) {
+    const RunnerWords rw{s->d_runner_caller, s->nt};
+    std::vector<unsigned long long> h((size_t)(4 * RunnerWords::tiles(s->nt)));  // (per tile: RunnerWords)
+    PCGX_HIP_TRY(hipMemcpyAsync(h.data(), rw.counts(), h.size() * sizeof h[0], hipMemcpyDeviceToHost, st));
+    PCGX_HIP_TRY(hipMemsetAsync(rw.counts(), 0, h.size() * sizeof h[0], st));
+    PCGX_HIP_TRY(hipStreamSynchronize(st));
+    for (int k = 0; k < 3; k++) counts[k] = 0;
+    for (size_t t = 0; t < h.size(); t += 4)
+      for (int k = 0; k < 3; k++) counts[k] += (int64_t)h[t + k];
+  }
+  if (!match_caller) return PCGX_OK;
+  PCGX_HIP_TRY(hipMemcpyAsync(match_caller, s->d_match_caller, (size_t)nt * sizeof(float4), hipMemcpyDeviceToHost, st));
+  PCGX_HIP_TRY(hipMemcpyAsync(runner_caller, s->d_runner_caller, (size_t)nt * sizeof(float4), hipMemcpyDeviceToHost, st));
+  PCGX_HIP_TRY(hipMemcpyAsync(runner_id_caller, RunnerWords{s->d_runner_caller, s->nt}.ids(), (size_t)nt * sizeof(uint32_t), hipMemcpyDeviceToHost, st));
+  PCGX_HIP_TRY(hipStreamSynchronize(st));
   return PCGX_OK;
 }
 

@@ -64,14 +64,22 @@ __global__ __launch_bounds__(256) void grid_start_kernel(const uint32_t *__restr
 // where that is smaller (a point outside those cells is a cell's edge away).  |q - p| < 0.49 L then, every other point
 // is more than 1.04 times as far, its computed DistSq more than 1.07 times the one of p: strictly larger, no tie.  A
 // point with a twin (rho = 0) has cert 0: never certified.  The ICP loop keeps a pair on this alone (icp.hip).
-__global__ __launch_bounds__(256) void grid_cert_kernel(GridView g, int64_t n, float *__restrict__ cert) {
+// The runner-up record (RunnerView::runner, runner_id; nullptr: not made): n1 = the other point with the smallest
+// computed DistSq (of exact ties the first one met), and cert2 = 0.24 L2^2 with L2^2 made like L^2 from the
+// SECOND-smallest computed DistSq over the other points (a tie for the smallest is the second-smallest as well: cert2 =
+// cert then).  Every point but p and n1 is at least L2 away: the argument above, verbatim, says that a query whose
+// computed DistSq to p is below cert2 has p or n1 as its nearest -- no third point can win or tie.  A point with no
+// other point in its 27 cells has no record (cert2 = 0).
+__global__ __launch_bounds__(256) void grid_cert_kernel(GridView g, int64_t n, float *__restrict__ cert,
+                                                        float4 *__restrict__ runner, uint32_t *__restrict__ runner_id) {
   const int64_t f = (int64_t)blockIdx.x * 256 + threadIdx.x;
   if (f >= n) return;
   const float4 p = g.pts[f];
   const int cx = grid_cell(p.x, g.lo[0], g.inv_h, g.nx), cy = grid_cell(p.y, g.lo[1], g.inv_h, g.ny),
             cz = grid_cell(p.z, g.lo[2], g.inv_h, g.nz);
   const int x0 = max(cx - 1, 0), x1 = min(cx + 1, g.nx - 1);
-  float dmin = __builtin_inff();
+  float dmin = __builtin_inff(), dmin2 = __builtin_inff();
+  uint32_t k1 = 0xffffffffu;  // n1's position
   for (int z = max(cz - 1, 0); z <= min(cz + 1, g.nz - 1); z++)
     for (int y = max(cy - 1, 0); y <= min(cy + 1, g.ny - 1); y++) {
       const uint32_t row = (uint32_t)((z * g.ny + y) * g.nx);
@@ -81,7 +89,14 @@ __global__ __launch_bounds__(256) void grid_cert_kernel(GridView g, int64_t n, f
         const float4 o = g.pts[k];
         const float dx = o.x - p.x, dy = o.y - p.y, dz = o.z - p.z;
         const float d = (dx * dx + dy * dy) + dz * dz;
-        dmin = d < dmin ? d : dmin;  // (NaN never: the grid holds finite points only)
+        // (NaN never: the grid holds finite points only)
+        if (d < dmin) {
+          dmin2 = dmin;
+          dmin = d;
+          k1 = k;
+        } else if (d < dmin2) {
+          dmin2 = d;
+        }
       }
     }
   // (a cell's edge in coordinates: the cell numbers are rounded products of up to max(nx, ny, nz), their rounding is
@@ -91,6 +106,12 @@ __global__ __launch_bounds__(256) void grid_cert_kernel(GridView g, int64_t n, f
   float l2 = fminf(dmin - 2.0e-6f * dmin, edge * edge);
   if (!(l2 > 0.0f) || !(slack > 0.5f)) l2 = 0.0f;
   cert[__float_as_int(p.w)] = 0.24f * l2;  // by the point's id (ids are 0 .. n - 1: grid_build makes no certificates for labelled trees)
+  if (runner == nullptr) return;  // uniform
+  float l22 = fminf(dmin2 - 2.0e-6f * dmin2, edge * edge);
+  if (!(l22 > 0.0f) || !(slack > 0.5f) || k1 == 0xffffffffu) l22 = 0.0f;
+  const float4 o = g.pts[k1 == 0xffffffffu ? (uint32_t)f : k1];
+  runner[__float_as_int(p.w)] = make_float4(o.x, o.y, o.z, 0.24f * l22);
+  runner_id[__float_as_int(p.w)] = __float_as_uint(o.w);
 }
 
 // One query per lane.  Certified answers are written; the rest is appended to walk_list (query
@@ -429,15 +450,34 @@ void grid_free(pcgx_kdtree *t) {
   dev_cache_free(t->d_gpts);
   dev_cache_free(t->d_gstart);
   dev_cache_free(t->d_gcert);
+  dev_cache_free(t->d_grunner);
+  dev_cache_free(t->d_grunner_id);
   t->d_gpts = nullptr;
   t->d_gstart = nullptr;
   t->d_gcert = nullptr;
+  t->d_grunner = nullptr;
+  t->d_grunner_id = nullptr;
+  t->runner_view = {nullptr, nullptr, 0.0f};
   t->grid_ok = false;
 }
 
 static int grid_mode() {  // PCGX_GRID=0: tree walk only; =2: grid even for crowded cells (tests)
   const char *e = getenv("PCGX_GRID");
   return e ? atoi(e) : 1;
+}
+
+// RunnerView::below: a pair carries its partner's runner-up record where the partner's certificate is below
+// 0.24 (f h)^2, h the cell's edge.  PCGX_GRID_RUNNER_BELOW: f (inf: every pair, 0: none).  Default f = 0.22: at C4
+// (h = 114 mm) partners whose nearest other point is within 25 mm, 3 % of the base points, and every pair that fails
+// its certificate from a Fit's third Evaluate on but ten (tools/cert2_probe.py).
+static float runner_below(float h) {
+  float f = 0.22f;
+  if (const char *e = getenv("PCGX_GRID_RUNNER_BELOW")) {
+    const float v = (float)atof(e);
+    if (v >= 0.0f) f = v;  // (NaN: the default)
+  }
+  const float r = f * h;
+  return 0.24f * r * r;  // (f = inf: +inf)
 }
 
 bool grid_enabled(const pcgx_kdtree *t) { return t->grid_ok && grid_mode() != 0; }
@@ -558,10 +598,21 @@ pcgx_status grid_build(pcgx_kdtree *t, const float *d_xyz, const int32_t *d_labe
   hipLaunchKernelGGL(grid_gather_kernel, dim3(nb), dim3(256), 0, st, d_xyz, (const uint32_t *)vals[res], d_labels, n,
                      t->d_gpts);
   // the points' certificates (not required: without them every pair is searched for)
+  // ... and their runner-up records (not required either: level 2 of the certificates is then off)
   g.cert = nullptr;
+  t->runner_view = {nullptr, nullptr, 0.0f};
   if (d_labels == nullptr && dev_cache_alloc((void **)&t->d_gcert, (size_t)n * sizeof(float)) == hipSuccess) {
-    hipLaunchKernelGGL(grid_cert_kernel, dim3(nb), dim3(256), 0, st, g, n, t->d_gcert);
+    if (dev_cache_alloc((void **)&t->d_grunner, (size_t)n * sizeof(float4)) != hipSuccess ||
+        dev_cache_alloc((void **)&t->d_grunner_id, (size_t)n * sizeof(uint32_t)) != hipSuccess) {
+      (void)hipGetLastError();
+      dev_cache_free(t->d_grunner);
+      dev_cache_free(t->d_grunner_id);
+      t->d_grunner = nullptr;
+      t->d_grunner_id = nullptr;
+    }
+    hipLaunchKernelGGL(grid_cert_kernel, dim3(nb), dim3(256), 0, st, g, n, t->d_gcert, t->d_grunner, t->d_grunner_id);
     g.cert = t->d_gcert;
+    if (t->d_grunner) t->runner_view = {t->d_grunner, t->d_grunner_id, runner_below(g.h)};
   } else {
     (void)hipGetLastError();
     t->d_gcert = nullptr;
@@ -575,9 +626,14 @@ pcgx_status grid_build(pcgx_kdtree *t, const float *d_xyz, const int32_t *d_labe
     dev_cache_free(t->d_gpts);
     dev_cache_free(t->d_gstart);
     dev_cache_free(t->d_gcert);
+    dev_cache_free(t->d_grunner);
+    dev_cache_free(t->d_grunner_id);
     t->d_gpts = nullptr;
     t->d_gstart = nullptr;
     t->d_gcert = nullptr;
+    t->d_grunner = nullptr;
+    t->d_grunner_id = nullptr;
+    t->runner_view = {nullptr, nullptr, 0.0f};
   }
   return PCGX_OK;
 }
@@ -649,6 +705,17 @@ pcgx_status grid_launch_nearest_partitioned(const pcgx_kdtree *t, const float *d
 }
 
 }  // namespace pcgx
+
+extern "C" pcgx_status pcgx_debug_grid_runner(const pcgx_kdtree *t, float *runner, uint32_t *runner_id, float *below, int64_t n) {
+  PCGX_API_LOCK();
+  if (!t || !runner || !runner_id || !below || n != t->n) return pcgx::fail(PCGX_E_INVALID, "pcgx_debug_grid_runner: bad argument");
+  if (!pcgx::grid_enabled(t) || !t->d_grunner) return pcgx::fail(PCGX_E_INVALID, "pcgx_debug_grid_runner: the tree has no runner-up records");
+  PCGX_TRY(pcgx::ensure_init());
+  PCGX_HIP_TRY(hipMemcpy(runner, t->d_grunner, (size_t)n * sizeof(float4), hipMemcpyDeviceToHost));
+  PCGX_HIP_TRY(hipMemcpy(runner_id, t->d_grunner_id, (size_t)n * sizeof(uint32_t), hipMemcpyDeviceToHost));
+  *below = t->runner_view.below;
+  return PCGX_OK;
+}
 
 extern "C" pcgx_status pcgx_debug_grid_cert(const pcgx_kdtree *t, float *cert, int64_t n) {
   PCGX_API_LOCK();

@@ -223,6 +223,16 @@ struct GridView {
   int32_t nx, ny, nz;
 };
 
+// The points' runner-up records (knn_grid.hip, grid_cert_kernel: made with the certificates, by point id; runner ==
+// nullptr: none): n1 = the point's nearest other point, cert2 = the certificate over everything BUT n1 -- a query whose
+// DistSq to the point is below cert2 has the point or n1 as its nearest, whichever computes nearer (level 2 of the ICP
+// loop's certificates: strict.hip).  Beside GridView and not in it: the searching kernels' arguments stay what they were.
+struct RunnerView {
+  const float4 *runner;       // [n] {n1.x, n1.y, n1.z, cert2}; cert2 = 0: no record
+  const uint32_t *runner_id;  // [n] n1's id
+  float below;                // pairs carry their partner's record where its `cert` is below this (+inf: every pair)
+};
+
 // XCD-contiguous placement of the tiles of a launch whose neighbouring tiles read neighbouring data:
 // workgroups are dealt round-robin to the 8 XCDs (blockIdx % 8), each with an L2 of its own, so
 // workgroup b takes tile (b % 8) * per + b / 8 and an XCD works through one contiguous eighth of the
@@ -527,7 +537,10 @@ struct pcgx_kdtree {
   float4 *d_gpts = nullptr;
   uint32_t *d_gstart = nullptr;
   float *d_gcert = nullptr;
+  float4 *d_grunner = nullptr;      // RunnerView::runner, runner_id (+20 bytes a point)
+  uint32_t *d_grunner_id = nullptr;
   pcgx::GridView grid;
+  pcgx::RunnerView runner_view = {nullptr, nullptr, 0.0f};
   bool grid_ok = false;
   double grid_crowding = 0.0;  // mean number of other points in a point's cell
   std::vector<uint8_t> deleted;    // [n] once the first point was deleted

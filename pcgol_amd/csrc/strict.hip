@@ -456,15 +456,79 @@ struct CertifiedStore {
   uint32_t pos;  // the target's session position
   int32_t q;     // its index in the tile, bit 16: the partner has a certificate to fetch; < 0: nothing held
 };
-__device__ __forceinline__ void certified_store_flush(const CertifiedTerms &C, int64_t tile, CertifiedStore &D) {
+template <bool kLevel2>
+__device__ __forceinline__ void certified_store_flush(const CertifiedTerms &C, int64_t nt, int64_t tile, CertifiedStore &D) {
   if (D.q < 0) return;
   const bool found = __float_as_int(D.best.w) >= 0;
-  const float cert = (D.q & 0x10000) ? C.grid.cert[__float_as_uint(D.best.w)] : 0.0f;
+  const bool has_cert = (D.q & 0x10000) != 0;
+  const float cert = has_cert ? C.grid.cert[__float_as_uint(D.best.w)] : 0.0f;
   const int64_t c = tile * kTile + (D.q & 0xffff);
   C.match[D.pos] = make_float4(D.best.x, D.best.y, D.best.z, found ? D.best_d : -1.0f);
   C.match_cert[D.pos] = cert;
   C.match_caller[c] = make_float4(D.best.x, D.best.y, D.best.z, found ? cert : -1.0f);
+  // (the new partner's runner words beside it: level 2 below)
+  if (kLevel2 && found) runner_words_store(C.runner, C.runner_caller, RunnerWords{C.runner_caller, nt}.ids(), c, cert, has_cert ? __float_as_int(D.best.w) : -1);
   D.q = -1;
+}
+
+// Level 2 of the certificates (C.runner_caller != nullptr), in the owner lane and in front of the searches.
+// A pair that failed its certificate carries the runner-up record of last iteration's partner p: n1 = p's nearest other
+// point, cert2 = the certificate over every point BUT n1.  Where the DistSq dm to p is below cert2, the nearest point is
+// p or n1, whichever computes strictly nearer -- p: the pair stands (nothing to store, as for a level-1 keep); n1: the
+// pair flips to {n1, dn}, its terms are formed at once, and its records are written behind the summaries
+// (certified_flip_flush) from nothing but the slot's bit in `flips`.  A tie, a NaN, no record (cert2 = 0), dm not
+// below cert2: searched as before.  `lvl2`: the slot failed level 1 and has a record to look at.  The four records of a
+// lane are one round trip, taken only by waves with such a slot; they live from the load to the decision, and the
+// searches' registers (certified_wave_search, at the wave's limit) are what they were.
+// Returns the wave's keeps << 10 | flips << 20 (counted with the searched items, once per workgroup: RunnerWords::counts).
+__device__ __forceinline__ int certified_level2(const CertifiedTerms &C, int64_t i0, bool (&fail)[4], const bool (&lvl2)[4],
+                                                const float (&mx)[4], const float (&my)[4], const float (&mz)[4],
+                                                const float (&ub)[4], float4 (&bp)[4], int &flips) {
+  if (__ballot(lvl2[0] || lvl2[1] || lvl2[2] || lvl2[3]) == 0ull) return 0;  // uniform
+  float4 r[4];
+#pragma unroll
+  for (int c = 0; c < 4; c++) r[c] = lvl2[c] ? C.runner_caller[i0 + c] : make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+  int n_keep = 0, n_flip = 0;  // uniform
+#pragma unroll
+  for (int c = 0; c < 4; c++) {
+    const float dx = r[c].x - mx[c], dy = r[c].y - my[c], dz = r[c].z - mz[c];
+    const float dn = (dx * dx + dy * dy) + dz * dz;  // (the scan's expression, as the bound is)
+    const float dm = ub[c];
+    const bool in2 = lvl2[c] && r[c].w > 0.0f && dm < r[c].w && dm < C.max_dist_sq;
+    const bool keep = in2 && dm < dn, flip = in2 && dn < dm;
+    if (keep) bp[c].w = dm;  // (a pair again; the terms' reader looks at w >= 0 only)
+    if (flip) {
+      bp[c] = make_float4(r[c].x, r[c].y, r[c].z, dn);
+      flips |= 1 << c;
+    }
+    if (keep || flip) fail[c] = false;
+    n_keep += __popcll(__ballot(keep));
+    n_flip += __popcll(__ballot(flip));
+  }
+  return (n_keep << 10) | (n_flip << 20);
+}
+
+// The records of a flipped pair, behind phase 2 and off the exchange's path: the ones a search that found n1 leaves.
+// n1 and its id are still in the slot's runner words; the DistSq is formed again, from the same floats.
+__device__ __forceinline__ void certified_flip_flush(const CertifiedTerms &C, const IcpState *state, const float *xyz, int64_t nt, int64_t i0, int flips) {
+#pragma unroll 1
+  for (int c = 0; c < 4; c++) {
+    if (!((flips >> c) & 1)) continue;
+    const int64_t cg = i0 + c;
+    const float4 r = C.runner_caller[cg];
+    uint32_t *ids = RunnerWords{C.runner_caller, nt}.ids();
+    const uint32_t id = ids[cg];
+    const uint32_t pos = C.pos_of[cg];
+    float x, y, z;
+    mat4_transform(state->trans, xyz[3 * cg], xyz[3 * cg + 1], xyz[3 * cg + 2], x, y, z);  // (a flip: never the first Evaluate)
+    const float dx = r.x - x, dy = r.y - y, dz = r.z - z;
+    const float dn = (dx * dx + dy * dy) + dz * dz;
+    const float cert = C.grid.cert[id];
+    C.match[pos] = make_float4(r.x, r.y, r.z, dn);
+    C.match_cert[pos] = cert;
+    C.match_caller[cg] = make_float4(r.x, r.y, r.z, cert);
+    runner_words_store(C.runner, C.runner_caller, ids, cg, cert, (int32_t)id);
+  }
 }
 
 // kCertify's searches (strict_sum_kernel, phase 1): the targets whose certificate did not hold, wave by wave and out
@@ -480,6 +544,7 @@ __device__ __forceinline__ void certified_store_flush(const CertifiedTerms &C, i
 // launch in which every wave had something to search).
 // While a round's searches run, the lanes' own quads (pairs, targets) wait in `park`: the thread's nine slots of the
 // staged tile, which nobody has written yet -- next to grid_nearest's registers they do not fit the 128 of a wave.
+template <bool kLevel2>
 __device__ __forceinline__ int certified_wave_search(const CertifiedTerms &C, const IcpState *state, const StrictWork &W, int64_t tile,
                                                       int lane, int wave, const bool (&fail)[4], float (&mx)[4], float (&my)[4],
                                                       float (&mz)[4], const float (&ub)[4], float4 (&bp)[4], float4 *park,
@@ -497,7 +562,7 @@ __device__ __forceinline__ int certified_wave_search(const CertifiedTerms &C, co
   if (n == 0) return 0;
 #pragma unroll 1
   for (int r0 = 0; r0 < n; r0 += kLanes) {  // uniform
-    certified_store_flush(C, tile, D);  // (the round before this one: a wave with more than 64 items)
+    certified_store_flush<kLevel2>(C, W.nt, tile, D);  // (the round before this one: a wave with more than 64 items)
     const bool on = r0 + lane < n;
     const int k = on ? r0 + lane : r0;  // (a lane without an item goes through item r0's shuffles)
     const int c = (k >= base[1] ? 1 : 0) + (k >= base[2] ? 1 : 0) + (k >= base[3] ? 1 : 0);
@@ -570,7 +635,9 @@ __device__ __forceinline__ int certified_wave_search(const CertifiedTerms &C, co
 // before the terms are formed, while the other waves form and stage theirs; the new pairs are written in both orders at
 // the kernel's end.  A search the grid cannot certify (GRID_WALK) sets `done` 2, as the grid pass without the walk
 // does: the host enqueues the step again (settle()).
-template <bool kExchange, bool kSharded = false, bool kCertify = false>
+// kLevel2 (with kCertify; PCGX_ICP_CERT2): the pairs carry their partners' runner-up records, certified_level2 stands in
+// front of the searches.  An instantiation of its own: without it the kernel's code is what it was.
+template <bool kExchange, bool kSharded = false, bool kCertify = false, bool kLevel2 = false>
 __global__ __launch_bounds__(kSumBlock) __attribute__((amdgpu_waves_per_eu(4, 4))) void strict_sum_kernel(
     const float4 *__restrict__ match, const uint32_t *__restrict__ pos_of, const IcpState *__restrict__ state, StrictWork W,
     CertifiedTerms C = CertifiedTerms()) {
@@ -583,6 +650,7 @@ __global__ __launch_bounds__(kSumBlock) __attribute__((amdgpu_waves_per_eu(4, 4)
   __shared__ double s_tot[16];
   static_assert(!kSharded || kExchange, "the ring form rides on the exchange");
   static_assert(!kCertify || (kExchange && !kSharded), "the certified terms: one GPU, with the exchange");
+  static_assert(!kLevel2 || kCertify, "level 2 is the certified terms'");
   const int done = state->done;  // (looked at behind phase 1, whose loads it would only hold up: nothing is written before)
   const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
   const int64_t tile = blockIdx.x;
@@ -591,6 +659,9 @@ __global__ __launch_bounds__(kSumBlock) __attribute__((amdgpu_waves_per_eu(4, 4)
   long long t_x0 = 0;
   CertifiedStore held;  // kCertify: what this lane's search found, written out behind phase 2
   held.q = -1;
+  // kCertify: the slots of this thread's quad that level 2 flipped (certified_flip_flush, behind phase 2): a byte of LDS
+  // and not a register through the searches, which have none to spare
+  __shared__ unsigned char s_flips[kLevel2 ? kSumBlock : 1];
   // the float64 prefix of this wave's row (strict_tilesum_kernel's sums): its loads fly while phase 1 runs
   double P0 = (!kExchange && wave < NR) ? tile_prefix(W.tile_sum, W.ntiles, wave, tile, lane) : 0.0;
   // ---- phase 1: the tile's terms, every thread one quad
@@ -604,7 +675,7 @@ __global__ __launch_bounds__(kSumBlock) __attribute__((amdgpu_waves_per_eu(4, 4)
     float t[4][kStrictRows];
     int np = 0;
     if (kCertify) {
-      bool fail[4];
+      bool fail[4], lvl2[4];
       float ub[4];
 #pragma unroll
       for (int c = 0; c < 4; c++) {
@@ -618,13 +689,25 @@ __global__ __launch_bounds__(kSumBlock) __attribute__((amdgpu_waves_per_eu(4, 4)
         if ((C.test_force_walk && (i0 + c) % C.test_force_walk == 0) || (C.test_force_grid_walk && (i0 + c) % C.test_force_grid_walk == 0))
           kept = false;  // (tests: searched below, and with the second knob, handed back as GRID_WALK)
         fail[c] = !kept && i0 + c < W.nt;
+        // (level 2: the pair has runner words where its certificate is below the threshold; not a forced search)
+        lvl2[c] = kLevel2 && fail[c] && S.project && bp[c].w >= 0.0f && bp[c].w < C.runner.below &&
+                  !((C.test_force_walk && (i0 + c) % C.test_force_walk == 0) || (C.test_force_grid_walk && (i0 + c) % C.test_force_grid_walk == 0));
         ub[c] = (S.project && bp[c].w >= 0.0f && dm == dm) ? dm : __builtin_inff();  // (the search's bound)
         if (fail[c]) bp[c].w = -1.0f;  // (no pair unless the search below finds one)
         tx[c] = x; ty[c] = y; tz[c] = z;  // (moved: what the search and the terms start from)
       }
       int ns = 0;
-      if (!done) ns = certified_wave_search(C, state, W, tile, lane, wave, fail, tx, ty, tz, ub, bp, &s_terms[0][tile_quad(l, v)], held);  // (done: uniform)
-      if (lane == 0) s_ns[wave] = ns;
+      if (kLevel2 && !done) {  // uniform
+        int flips = 0;
+        const int n2 = certified_level2(C, i0, fail, lvl2, tx, ty, tz, ub, bp, flips);
+        s_flips[threadIdx.x] = (unsigned char)flips;
+        if (lane == 0) s_ns[wave] = n2;
+      }
+      if (!done) ns = certified_wave_search<kLevel2>(C, state, W, tile, lane, wave, fail, tx, ty, tz, ub, bp, &s_terms[0][tile_quad(l, v)], held);  // (done: uniform)
+      if (lane == 0) {
+        if (kLevel2) s_ns[wave] += ns;  // (beside the level-2 counts)
+        else s_ns[wave] = ns;
+      }
       TermSrc S0 = S;
       S0.project = false;  // (the targets are moved already)
 #pragma unroll
@@ -901,13 +984,29 @@ __global__ __launch_bounds__(kSumBlock) __attribute__((amdgpu_waves_per_eu(4, 4)
     for (int v = 0; v < kLeaf / 4; v++) dst[v * kLanes + lane_here] = s_terms[row][v * kLanes + lane_here];
   }
   if (kCertify) {
-    certified_store_flush(C, tile, held);
+    certified_store_flush<kLevel2>(C, W.nt, tile, held);
+    if (kLevel2) {
+      const int flips = s_flips[threadIdx.x];
+      if (flips) certified_flip_flush(C, state, W.xyz_caller, W.nt, tile * kTile + (int64_t)(threadIdx.x >> 3) * kLeaf + 4 * (threadIdx.x & 7), flips);
+    }
     // (the counters behind everything else: wave 0's look at its own stores in the exchange would wait for them too)
     if (threadIdx.x == 0) {
       if (tile == 0) atomicAdd(&W.dbg[47], 1ull);  // (fused steps; replayed ones in the high word: certified_wave_search)
-      int ns = 0;
-      for (int w = 0; w < kSumWaves; w++) ns += s_ns[w];
+      int ns = 0, n_keep = 0, n_flip = 0;  // (level 2, a wave's word: items searched, keeps << 10, flips << 20)
+      for (int w = 0; w < kSumWaves; w++) {
+        ns += kLevel2 ? s_ns[w] & 0x3ff : s_ns[w];
+        if (kLevel2) n_keep += (s_ns[w] >> 10) & 0x3ff;
+        if (kLevel2) n_flip += s_ns[w] >> 20;
+      }
       if (ns > 0) atomicAdd(&W.dbg[59], (unsigned long long)ns);
+      if (kLevel2 && ns + n_keep + n_flip > 0) {  // (level 2 on; W.dbg has no word to spare)
+        static_assert(kTile == 2048, "RunnerWords::tiles");
+        unsigned long long *counts = RunnerWords{C.runner_caller, W.nt}.counts() + 4 * tile;  // (this workgroup's alone)
+        const unsigned long long c0 = counts[0], c1 = counts[1], c2 = counts[2];
+        counts[0] = c0 + (unsigned long long)n_keep;
+        counts[1] = c1 + (unsigned long long)n_flip;
+        counts[2] = c2 + (unsigned long long)(ns + n_keep + n_flip);
+      }
     }
   }
   if (threadIdx.x == 0 && (W.selfcheck & 2)) {  // measurement aid (PCGX_STRICT_TRACE), plain stores only
@@ -2843,6 +2942,8 @@ static pcgx_status enqueue_stages(unsigned stages, const StrictLaunches &L, cons
       hipLaunchKernelGGL(strict_sum_kernel<true>, grid, block, 0, a.st, a.match, a.pos_of, state, W);
     else if (L.summary == kSumRing)
       hipLaunchKernelGGL((strict_sum_kernel<true, true>), grid, block, 0, a.st, a.match, a.pos_of, state, W);
+    else if (L.summary == kSumCertified && a.certify->runner_caller != nullptr)  // (level 2)
+      hipLaunchKernelGGL((strict_sum_kernel<true, false, true, true>), grid, block, 0, a.st, a.match, a.pos_of, state, W, *a.certify);
     else if (L.summary == kSumCertified)
       hipLaunchKernelGGL((strict_sum_kernel<true, false, true>), grid, block, 0, a.st, a.match, a.pos_of, state, W, *a.certify);
     else

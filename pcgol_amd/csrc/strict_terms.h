@@ -160,6 +160,25 @@ struct CertifiedTerms {
   const uint32_t *pos_of;    // [nt] caller's index -> session position
   int32_t test_force_walk;   // tests: every k-th target (caller index) is searched although its certificate holds
   int32_t test_force_grid_walk;  // tests: ... and its search ends in GRID_WALK (the step is replayed with the walk)
+  // level 2 (runner_caller == nullptr: off; behind everything else: the kernel without it reads the arguments it did):
+  // the runner-up record of every pair's partner (RunnerView), for the pairs whose certificate is below runner.below --
+  // written by whoever writes match_caller (runner_words_store)
+  // (one block and one pointer -- the summary kernel has no scalar register to spare: RunnerWords)
+  RunnerView runner;
+  float4 *runner_caller;       // [nt] caller order: {n1 of the partner, cert2}; cert2 = 0: no record
+};
+
+// The pairs' runner words, one block: [nt] float4 records, behind them [nt] n1 ids (caller order, as the records), behind
+// those four 64-bit words per tile of 2048 targets (measurement aid: the tile's targets level 2 kept, flipped, and all
+// that failed level 1 while it was on, added up over the steps by the tile's own workgroup with plain loads and stores --
+// atomics of every workgroup on one word are served one after the other, at the launch's end)
+struct RunnerWords {
+  float4 *rec;
+  int64_t nt;
+  __host__ __device__ uint32_t *ids() const { return reinterpret_cast<uint32_t *>(rec + nt); }
+  __host__ __device__ unsigned long long *counts() const { return reinterpret_cast<unsigned long long *>(rec + nt) + (nt + 1) / 2; }
+  static int64_t tiles(int64_t nt) { return (nt + 2047) / 2048; }
+  static size_t bytes(int64_t nt) { return (size_t)nt * sizeof(float4) + (size_t)((nt + 1) / 2 + 4 * tiles(nt)) * sizeof(unsigned long long); }
 };
 
 // ---- the ring (a target spread over ranks, strict_enqueue_ring) -------------------------------------------------
@@ -192,6 +211,20 @@ constexpr long long kRingGuessTicksApart = 20000000;   // 200 ms
 constexpr long long kRingWalkTicks = 1000000000;  // 10 s: waits for the state a walk starts from (there is no going on without it)
 
 #if defined(__HIPCC__)
+// The invariant of level 2: whoever writes match_caller[c] = {partner, cert} with cert >= 0 calls this behind it.  id:
+// the partner's, < 0 where the writer does not know it or the partner has no certificate -- the pair then stands
+// without a record (cert2 = 0) until it is next searched.  Pairs at or above the threshold are not written and not read.
+__device__ __forceinline__ void runner_words_store(const RunnerView &g, float4 *runner_caller, uint32_t *runner_id_caller,
+                                                   int64_t c, float cert, int32_t id) {
+  if (runner_caller == nullptr || !(cert < g.below)) return;
+  if (id >= 0 && g.runner != nullptr) {
+    runner_caller[c] = g.runner[id];
+    runner_id_caller[c] = g.runner_id[id];
+  } else {
+    runner_caller[c] = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
+  }
+}
+
 __device__ __forceinline__ void ring_put(unsigned long long *w, uint32_t payload, uint32_t epoch) {
   __hip_atomic_store(w, (unsigned long long)epoch << 32 | payload, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
 }
