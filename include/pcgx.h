@@ -733,7 +733,10 @@ PCGX_API pcgx_status pcgx_pcd_marshal(const pcgx_pcd_header *h, const void *data
  * A plane session is a pcgx_icp_session whose exchange vector has 30 doubles:
  *   {sum r^2, sum J r [6], upper triangle of sum J J^T row-major [21], sum w, pair count}.
  * partials / update / step / result / reset / set_pose / free are the session calls above;
- * params->weight is unused, params->threshold / max_iteration / min_pairs / max_dist as above. */
+ * params->weight is unused, params->threshold / max_iteration / min_pairs / max_dist as above.
+ * params->min_dist_sq has no meaning here either: a plane session always searches exactly (MinDistSq = 0), and
+ * pcgx_icp_plane_session_create answers a min_dist_sq > 0 with PCGX_E_INVALID instead of ignoring it silently
+ * (so does pcgx_icp_plane_fit): pass 0 whatever MinDistSq the tree handle was made with. */
 PCGX_API pcgx_status pcgx_icp_plane_session_create(const pcgx_kdtree *base, const float *base_normals,
                                                    const float *target, int64_t nt, int32_t on_device,
                                                    const pcgx_icp_params *params, float damping,
