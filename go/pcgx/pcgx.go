@@ -519,6 +519,93 @@ func (k *KDTree) Boundary(radius float32, normals []mat.Vec3, minGap, minNeighbo
 	return res, nil
 }
 
+// RayHits is what (*KDTree).RayCast returns, per ray: the first point's id (-1: none), Along = (p - o) . d and
+// OffSq = |(p - o) x d|^2 in float64 (0 for a miss).
+type RayHits struct {
+	IDs   []int64
+	Along []float64
+	OffSq []float64
+}
+
+// rayArgs checks one direction (and one sMin, sMax where given) per origin and returns the C pointers (nil: absent).
+func rayArgs(origins, directions []mat.Vec3, sMin, sMax []float32) (o, d, lo, hi *C.float, err error) {
+	nr := len(origins)
+	if len(directions) != nr || (sMin != nil && len(sMin) != nr) || (sMax != nil && len(sMax) != nr) {
+		return nil, nil, nil, nil, errors.New("pcgx: one direction (and one sMin, sMax where given) per origin is required")
+	}
+	if nr > 0 {
+		o, d = (*C.float)(unsafe.Pointer(&origins[0])), (*C.float)(unsafe.Pointer(&directions[0]))
+		if sMin != nil {
+			lo = (*C.float)(unsafe.Pointer(&sMin[0]))
+		}
+		if sMax != nil {
+			hi = (*C.float)(unsafe.Pointer(&sMax[0]))
+		}
+	}
+	return o, d, lo, hi, nil
+}
+
+// RayCast returns, for each ray origins[j] + s directions[j] with s in [sMin[j], sMax[j]] (nil: 0 and +inf), the first
+// of the tree's points within radius of the ray's line: the member with the smallest Along, a tie going to the smallest
+// id.  Directions are not normalised: s = Along / |d|^2 (extension: no reference parity; include/pcgx.h,
+// pcgx_kdtree_raycast).
+func (k *KDTree) RayCast(origins, directions []mat.Vec3, radius float32, sMin, sMax []float32) (*RayHits, error) {
+	runtime.LockOSThread() // the error text is thread-local on the C side: call and pcgx_last_error on one OS thread
+	defer runtime.UnlockOSThread()
+	defer runtime.KeepAlive(k) // the finalizer must not free the handle while a call is in flight
+	o, d, lo, hi, err := rayArgs(origins, directions, sMin, sMax)
+	if err != nil {
+		return nil, err
+	}
+	nr := len(origins)
+	res := &RayHits{IDs: make([]int64, nr), Along: make([]float64, nr), OffSq: make([]float64, nr)}
+	if nr == 0 {
+		return res, nil
+	}
+	rc := C.pcgx_kdtree_raycast(k.t.h, o, d, lo, hi, C.int64_t(nr), C.float(radius), (*C.int64_t)(unsafe.Pointer(&res.IDs[0])),
+		(*C.double)(unsafe.Pointer(&res.Along[0])), (*C.double)(unsafe.Pointer(&res.OffSq[0])))
+	runtime.KeepAlive(origins)
+	runtime.KeepAlive(directions)
+	runtime.KeepAlive(sMin)
+	runtime.KeepAlive(sMax)
+	runtime.KeepAlive(res)
+	if err := status(rc); err != nil {
+		return nil, err
+	}
+	return res, nil
+}
+
+// RayPierce returns, per point in id order, how many of the rays it lies in the tube of (RayCast's member test; a
+// deleted point counts 0): what free-space carving asks of a map (extension: no reference parity; include/pcgx.h,
+// pcgx_kdtree_ray_pierce).
+func (k *KDTree) RayPierce(origins, directions []mat.Vec3, radius float32, sMin, sMax []float32) ([]int32, error) {
+	runtime.LockOSThread() // the error text is thread-local on the C side: call and pcgx_last_error on one OS thread
+	defer runtime.UnlockOSThread()
+	defer runtime.KeepAlive(k) // the finalizer must not free the handle while a call is in flight
+	o, d, lo, hi, err := rayArgs(origins, directions, sMin, sMax)
+	if err != nil {
+		return nil, err
+	}
+	var ln C.int64_t
+	if err := status(C.pcgx_kdtree_len(k.t.h, &ln)); err != nil {
+		return nil, err
+	}
+	counts := make([]int32, int(ln))
+	if len(counts) == 0 || len(origins) == 0 {
+		return counts, nil
+	}
+	rc := C.pcgx_kdtree_ray_pierce(k.t.h, o, d, lo, hi, C.int64_t(len(origins)), C.float(radius),
+		(*C.int32_t)(unsafe.Pointer(&counts[0])))
+	runtime.KeepAlive(origins)
+	runtime.KeepAlive(directions)
+	runtime.KeepAlive(sMin)
+	runtime.KeepAlive(sMax)
+	if err := status(rc); err != nil {
+		return nil, err
+	}
+	return counts, nil
+}
+
 // ISSKeypoints returns the ISS keypoints of the tree's points (Zhong 2009, Open3D's form; extension: no reference
 // parity; include/pcgx.h, pcgx_kdtree_iss_keypoints): ids ascending, and per point in id order the eigenvalues of
 // Normals' covariance at salientRadius (ascending, zero where Normals answers "degenerate") and the saliency (the

@@ -1603,6 +1603,60 @@ PCGX_API pcgx_status pcgx_kdtree_boundary_dev(const pcgx_kdtree *t, float radius
                                               int32_t min_neighbors, int32_t *d_ids /* [Len()] */, int32_t *d_n_ids,
                                               int32_t *d_gaps, uint64_t *d_masks, int32_t *d_counts, void *stream);
 
+/* ------------------------------------------- ray queries (extension: no reference parity)
+ * NOT in the reference.  Every other query is about a point and its surroundings; these are about a line: which map
+ * points later beams passed through (free-space carving), which points are seen from a viewpoint, the point under a
+ * cursor, a range image of a map.  One primitive: for a batch of rays, the tree's points inside a thin tube around
+ * each, and of that set the first point along the ray or a count of how often each point was pierced.  This comment is
+ * the contract, tests/rays_oracle.py restates it.
+ * A ray: an origin o, a direction d (NOT normalised: any finite non-zero vector) and a parameter range [s_min, s_max];
+ *   its point at s is o + s d.  For a beam that ended at e: d = e - o and s_max = 1 - margin.  origins and directions are
+ *   [3 nr] float32, s_min and s_max [nr] float32; s_min == NULL means 0, s_max == NULL means +inf.
+ * Member: all float64 from the float32 inputs widened, fixed order, each product rounded once, nothing fused, no square
+ *   root and no division.  For a live tree point p with three finite coordinates: w = p - o;
+ *   a = (w.x d.x + w.y d.y) + w.z d.z;  dd = (d.x d.x + d.y d.y) + d.z d.z;  c = w x d = (w.y d.z - w.z d.y,
+ *   w.z d.x - w.x d.z, w.x d.y - w.y d.x);  cc = (c.x c.x + c.y c.y) + c.z c.z;  rr = radius radius.
+ *   p is a member iff cc <= rr dd and s_min dd <= a <= s_max dd: the tube's surface and both ends belong to it.
+ *   A deleted point is no ray's member.  A ray has no members if o or d has a non-finite component, if dd == 0, if s_min
+ *   or s_max is NaN, or if s_min > s_max.  A negative s_min is allowed, and so are -inf and +inf.
+ * First hit (pcgx_kdtree_raycast): per ray the member with the smallest a, a tie going to the smallest id.  ids[nr]
+ *   (-1: none), along[nr] = a, off_sq[nr] = cc, both float64, written as 0 for a miss, each may be NULL.  The caller
+ *   derives s = a / dd and the metric offset sqrt(cc / dd).
+ * Pierced counts (pcgx_kdtree_ray_pierce): counts[Len()] in id order; every (ray, member) pair adds 1 to counts[id].
+ *   The host form returns this call's counts; the _dev form ADDS into the caller's int32 array, so successive scans
+ *   accumulate on one stream with nothing read back.
+ * A minimum under a total order and an integer sum over a set: the same bits on every call, on every kind of handle
+ *   (grid, PCGX_RANGE_WALK=1, after DeletePoint) and however the work is split.
+ * PCGX_E_INVALID: a NULL tree; a radius that is not finite and > 0; nr < 0 (or above 2^31 - 16); NULL origins,
+ *   directions or ids / counts with nr > 0 (counts: and Len() > 0); a tree whose finite points span 2^62 or more along
+ *   an axis (float32 squared distances overflow there: csrc/ray_terms.h).  nr == 0 or Len() == 0 is PCGX_OK; with an
+ *   empty tree every ray is a miss.
+ * Always computed on the device (csrc/rays.hip): a wave per ray; the ray's range, clipped to the box of the tree's
+ *   finite points, is cut into slabs of about 2 radius (no shorter than a grid cell, at most 4096 per ray: longer slabs
+ *   beyond, never a shorter ray), each one ball query of pcgx_kdtree_range_count's enumeration whose candidates the
+ *   float64 member test filters.  csrc/ray_terms.h proves the balls cover the members.  No temporaries.  A tree with a
+ *   NaN or infinite coordinate among its points has no such enumeration to rely on (the reference's build has no
+ *   consistent order for a NaN): there a wave tests its ray against every point, from a copy of the handle's points
+ *   uploaded in the call (12 Len() bytes, Len() more after DeletePoint). */
+PCGX_API pcgx_status pcgx_kdtree_raycast(const pcgx_kdtree *t, const float *origins /* [3 nr] */,
+                                         const float *directions /* [3 nr] */, const float *s_min /* [nr] or NULL */,
+                                         const float *s_max /* [nr] or NULL */, int64_t nr, float radius,
+                                         int64_t *ids /* [nr] */, double *along /* [nr], may be NULL */,
+                                         double *off_sq /* [nr], may be NULL */);
+/* Same, every array device resident (ids are int32 there), enqueued on `stream` (NULL: the library's); returns without
+ * waiting. */
+PCGX_API pcgx_status pcgx_kdtree_raycast_dev(const pcgx_kdtree *t, const float *d_origins, const float *d_directions,
+                                             const float *d_s_min, const float *d_s_max, int64_t nr, float radius,
+                                             int32_t *d_ids, double *d_along, double *d_off_sq, void *stream);
+PCGX_API pcgx_status pcgx_kdtree_ray_pierce(const pcgx_kdtree *t, const float *origins /* [3 nr] */,
+                                            const float *directions /* [3 nr] */, const float *s_min /* [nr] or NULL */,
+                                            const float *s_max /* [nr] or NULL */, int64_t nr, float radius,
+                                            int32_t *counts /* [Len()] */);
+/* Same on the device, ADDING into d_counts int32 [Len()] (the caller zeroes it before the first scan). */
+PCGX_API pcgx_status pcgx_kdtree_ray_pierce_dev(const pcgx_kdtree *t, const float *d_origins, const float *d_directions,
+                                                const float *d_s_min, const float *d_s_max, int64_t nr, float radius,
+                                                int32_t *d_counts, void *stream);
+
 /* ------------------------------------------- score poses (extension: no reference parity)
  * NOT in the reference.  pcgx_pose_from_correspondences picks its pose by the inliers among the CORRESPONDENCES; on a
  * scene with repeated structure a wrong pose can collect more of them than the right one.  This call counts, for each of

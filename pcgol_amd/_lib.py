@@ -301,6 +301,10 @@ SIGNATURES = {
     "pcgx_ground_loop_max": (_i32, []),
     "pcgx_kdtree_boundary": (_i32, [_vp, _f32, _vp, _i32, _i32, _vp, C.POINTER(_i64), _vp, _vp, _vp]),
     "pcgx_kdtree_boundary_dev": (_i32, [_vp, _f32, _vp, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "pcgx_kdtree_raycast": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _f32, _vp, _vp, _vp]),
+    "pcgx_kdtree_raycast_dev": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _f32, _vp, _vp, _vp, _vp]),
+    "pcgx_kdtree_ray_pierce": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _f32, _vp]),
+    "pcgx_kdtree_ray_pierce_dev": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _f32, _vp, _vp]),
     "pcgx_kdtree_score_poses": (_i32, [_vp, _vp, _i64, _vp, _i64, _f32, _vp, _vp, C.POINTER(_i64), _vp]),
     "pcgx_kdtree_score_poses_dev": (_i32, [_vp, _vp, _i64, _vp, _i64, _f32, _vp, _vp, _vp, _vp]),
     "pcgx_score_tile": (_i32, []),

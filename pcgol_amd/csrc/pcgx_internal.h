@@ -510,6 +510,9 @@ struct pcgx_kdtree {
   int32_t dir_bits = 0;
   float dir_lo[3] = {0, 0, 0}, dir_scale[3] = {0, 0, 0};
   float bbox_lo[3] = {0, 0, 0}, bbox_hi[3] = {0, 0, 0};  // of the base cloud
+  float ray_lo[3] = {0, 0, 0}, ray_hi[3] = {0, 0, 0};    // of the base cloud's FINITE points (rays.hip, made on first use,
+  int ray_box_state = 0;                                 // guarded by mu): 0 not made, 1 made, 2 no finite point
+  bool ray_all_finite = true;                            // ... and whether every point is finite (else rays scan all points)
   bool has_nan = false;            // a NaN coordinate among the points (host build; no one-launch Fit: icp_small.hip)
   bool many_ties = false;          // along some axis most coordinates come several times (a scan of a plane, a lattice): the
                                    // reference's plane test (kdtree.go:111-115) rules out little there -- icp_small.hip

@@ -292,6 +292,36 @@ class KDTree {  // pc/storage/kdtree/kdtree.go:14-23
     r.ids.resize((size_t)m);
     return r;
   }
+  // Ray queries (extension: no reference parity; include/pcgx.h, pcgx_kdtree_raycast / _ray_pierce): ray j is
+  // origins[j] + s directions[j], s in [sMin[j], sMax[j]] (an empty vector: 0 and +inf); directions are not normalised.
+  // RayCast: per ray the first of the tree's points within `radius` of the ray's line -- ids (-1: none), along =
+  // (p - o) . d and offSq = |(p - o) x d|^2 in float64 (0 for a miss), a tie in along going to the smallest id.
+  // RayPierce: per point in id order, how many rays it lies in the tube of.
+  struct RayHits {
+    std::vector<int64_t> ids;
+    std::vector<double> along, offSq;
+  };
+  RayHits RayCast(const std::vector<Vec3> &origins, const std::vector<Vec3> &directions, float radius,
+                  const std::vector<float> &sMin = {}, const std::vector<float> &sMax = {}) const {
+    const size_t nr = RayCount(origins, directions, sMin, sMax);
+    RayHits r;
+    r.ids.resize(nr);
+    r.along.resize(nr);
+    r.offSq.resize(nr);
+    check(pcgx_kdtree_raycast(h_.get(), nr ? origins[0].data() : nullptr, nr ? directions[0].data() : nullptr,
+                              sMin.empty() ? nullptr : sMin.data(), sMax.empty() ? nullptr : sMax.data(), (int64_t)nr, radius,
+                              r.ids.data(), r.along.data(), r.offSq.data()));
+    return r;
+  }
+  std::vector<int32_t> RayPierce(const std::vector<Vec3> &origins, const std::vector<Vec3> &directions, float radius,
+                                 const std::vector<float> &sMin = {}, const std::vector<float> &sMax = {}) const {
+    const size_t nr = RayCount(origins, directions, sMin, sMax);
+    std::vector<int32_t> counts((size_t)Len(), 0);
+    check(pcgx_kdtree_ray_pierce(h_.get(), nr ? origins[0].data() : nullptr, nr ? directions[0].data() : nullptr,
+                                 sMin.empty() ? nullptr : sMin.data(), sMax.empty() ? nullptr : sMax.data(), (int64_t)nr,
+                                 radius, counts.data()));
+    return counts;
+  }
   // Cluster extraction (extension: no reference parity; include/pcgx.h, pcgx_kdtree_clusters): the connected
   // components of the radius graph over the tree's own points, kept when max(minSize, 1) <= size (<= maxSize unless 0),
   // largest first, equal sizes by smallest id.  normals (empty: none): an edge also needs |n_i . n_j| >= minCos
@@ -572,6 +602,13 @@ class KDTree {  // pc/storage/kdtree/kdtree.go:14-23
 
  private:
   KDTree(const KDTree &) = default;
+  static size_t RayCount(const std::vector<Vec3> &origins, const std::vector<Vec3> &directions,
+                         const std::vector<float> &sMin, const std::vector<float> &sMax) {
+    const size_t nr = origins.size();
+    if (directions.size() != nr || (!sMin.empty() && sMin.size() != nr) || (!sMax.empty() && sMax.size() != nr))
+      throw Error(PCGX_E_INVALID, "one direction (and one sMin, sMax where given) per origin is required");
+    return nr;
+  }
   std::shared_ptr<pcgx_kdtree> h_;
 };
 

@@ -1,7 +1,7 @@
 """pc/storage/kdtree mirror: KDTree on the GPU behind the storage.Search shape
 (pc/storage/search.go:13-17): Vec3At / Len / Nearest, plus batched NearestBatch, and extensions with no
 reference counterpart: surface normals (Normals), moving-least-squares smoothing (MLS), FPFH descriptors
-(FPFH, FPFHAt), keypoints (LocalMaxima, ISSKeypoints), cluster extraction (Clusters), density clusters (DBSCAN), plane segmentation (Planes), cylinder and sphere segmentation (Shapes), ground segmentation (Ground), boundary points (Boundary), per-group
+(FPFH, FPFHAt), keypoints (LocalMaxima, ISSKeypoints), cluster extraction (Clusters), density clusters (DBSCAN), plane segmentation (Planes), cylinder and sphere segmentation (Shapes), ground segmentation (Ground), boundary points (Boundary), ray queries (RayCast, RayPierce), per-group
 geometry (GroupStats), k nearest neighbours (KNearest) and their covariances (Covariances)."""
 import collections
 import ctypes as C
@@ -399,6 +399,60 @@ class KDTree:
         L.check(L.lib().pcgx_kdtree_boundary_dev(
             self._h, float(radius), L.ptr(int(d_normals)), int(MinGap), int(MinNeighbors), L.ptr(int(d_ids)),
             L.ptr(int(d_n_ids)), opt(d_gaps), opt(d_masks), opt(d_counts), L.ptr(stream) if stream else None))
+
+    # -- extension (no reference parity): ray queries, the points inside a thin tube around each ray
+    @staticmethod
+    def _rays(origins, directions, s_min, s_max):
+        o = L.f32c(origins).reshape(-1, 3)
+        d = L.f32c(directions).reshape(-1, 3)
+        if len(o) != len(d):
+            raise ValueError("one direction per origin is required")
+        lo = None if s_min is None else np.ascontiguousarray(np.broadcast_to(np.asarray(s_min, np.float32), (len(o),)))
+        hi = None if s_max is None else np.ascontiguousarray(np.broadcast_to(np.asarray(s_max, np.float32), (len(o),)))
+        return o, d, lo, hi
+
+    def RayCast(self, origins, directions, radius, s_min=None, s_max=None):
+        """The first point along each ray o + s d, s in [s_min, s_max] (None: 0 and +inf; scalars or (nr,) arrays), among
+        the tree's points within `radius` of the ray's line -> (ids int64 (nr,), -1 for a miss, along float64 (nr,),
+        off_sq float64 (nr,)).  d is not normalised; along = (p - o) . d and off_sq = |(p - o) x d|^2 in float64, 0 for a
+        miss, so s = along / |d|^2 and the metric offset is sqrt(off_sq / |d|^2); a tie in along goes to the smallest id
+        (include/pcgx.h, pcgx_kdtree_raycast)."""
+        o, d, lo, hi = self._rays(origins, directions, s_min, s_max)
+        nr = len(o)
+        ids = np.empty(nr, np.int64)
+        along = np.empty(nr, np.float64)
+        off = np.empty(nr, np.float64)
+        L.check(L.lib().pcgx_kdtree_raycast(self._h, L.ptr(o), L.ptr(d), L.ptr(lo), L.ptr(hi), nr, float(radius),
+                                            L.ptr(ids), L.ptr(along), L.ptr(off)))
+        return ids, along, off
+
+    def RayCastDev(self, d_origins, d_directions, nr, radius, d_ids, d_along=0, d_off_sq=0, d_s_min=0, d_s_max=0,
+                   stream=0):
+        """Device-resident RayCast: raw device addresses (e.g. torch .data_ptr()); d_origins, d_directions float32
+        [3 nr], d_s_min, d_s_max float32 [nr] (0: 0 and +inf), d_ids int32 [nr], d_along, d_off_sq float64 [nr] (each
+        optional).  Enqueued on `stream`, returns without waiting."""
+        opt = lambda a: L.ptr(int(a)) if a else None  # noqa: E731
+        L.check(L.lib().pcgx_kdtree_raycast_dev(
+            self._h, opt(d_origins), opt(d_directions), opt(d_s_min), opt(d_s_max), int(nr), float(radius), opt(d_ids),
+            opt(d_along), opt(d_off_sq), L.ptr(stream) if stream else None))
+
+    def RayPierce(self, origins, directions, radius, s_min=None, s_max=None):
+        """How often each point was pierced: counts int32 (Len(),) in id order, one added for every (ray, point) pair
+        where the point lies within `radius` of the ray's line and s_min <= s <= s_max (RayCast's member test; a deleted
+        point counts 0; include/pcgx.h, pcgx_kdtree_ray_pierce)."""
+        o, d, lo, hi = self._rays(origins, directions, s_min, s_max)
+        counts = np.zeros(self.Len(), np.int32)
+        L.check(L.lib().pcgx_kdtree_ray_pierce(self._h, L.ptr(o), L.ptr(d), L.ptr(lo), L.ptr(hi), len(o), float(radius),
+                                               L.ptr(counts)))
+        return counts
+
+    def RayPierceDev(self, d_origins, d_directions, nr, radius, d_counts, d_s_min=0, d_s_max=0, stream=0):
+        """Device-resident RayPierce, ADDING into d_counts int32 [Len()]: zero it before the first scan, and successive
+        scans accumulate on one stream with nothing read back.  Enqueued on `stream`, returns without waiting."""
+        opt = lambda a: L.ptr(int(a)) if a else None  # noqa: E731
+        L.check(L.lib().pcgx_kdtree_ray_pierce_dev(
+            self._h, opt(d_origins), opt(d_directions), opt(d_s_min), opt(d_s_max), int(nr), float(radius),
+            opt(d_counts), L.ptr(stream) if stream else None))
 
     # -- extension (no reference parity): clusters, the connected components of the radius graph
     def Clusters(self, radius, Normals=None, MinCos=0.0, Oriented=False, Curvature=None, MaxCurvature=0.0, MinSize=1,
