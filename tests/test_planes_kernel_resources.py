@@ -7,12 +7,13 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 import kernel_resources as KR  # noqa: E402
 
-PLANES_KERNELS = ["planes_gather_kernel", "planes_empty_kernel", "planes_fit_kernel", "planes_count_kernelILb0EE",
-                  "planes_count_kernelILb1EE", "planes_select_kernel", "planes_tile_count_kernelILi0EE",
-                  "planes_tile_count_kernelILi1EE", "planes_tile_count_kernelILi2EE", "planes_scan_kernelILi0EE",
-                  "planes_scan_kernelILi1EE", "planes_scan_kernelILi2EE", "planes_scatter_kernelILi0EE",
-                  "planes_scatter_kernelILi1EE", "planes_scatter_kernelILi2EE", "planes_refit_kernel",
-                  "planes_round_end_kernel"]
+M = "INS_10PlaneModelE"  # the round machinery's kernels (csrc/consensus_peel.h) as instantiated on planes.hip's model
+PLANES_KERNELS = ["peel_gather_kernel", "peel_empty_kernelILi4EE", "planes_fit_kernel", "planes_count_kernelILb0EE",
+                  "planes_count_kernelILb1EE", "peel_select_kernel" + M + "EE", "peel_tile_count_kernel" + M + "Li0EE",
+                  "peel_tile_count_kernel" + M + "Li1EE", "peel_tile_count_kernel" + M + "Li2EE",
+                  "peel_scan_kernel" + M + "Li0EE", "peel_scan_kernel" + M + "Li1EE", "peel_scan_kernel" + M + "Li2EE",
+                  "peel_scatter_kernel" + M + "Li0EE", "peel_scatter_kernel" + M + "Li1EE",
+                  "peel_scatter_kernel" + M + "Li2EE", "planes_refit_kernel", "peel_round_end_kernel" + M + "EE"]
 
 
 def test_planes_kernels_use_no_scratch():

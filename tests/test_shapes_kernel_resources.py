@@ -8,13 +8,16 @@ ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "tools"))
 import kernel_resources as KR  # noqa: E402
 
-SHAPES_KERNELS = ["shapes_gather_kernel", "shapes_empty_kernel", "shapes_partner_kernelILi0EE", "shapes_partner_kernelILi1EE",
+M = "INS_10ShapeModelE"  # the round machinery's kernels (csrc/consensus_peel.h) as instantiated on shapes.hip's model
+SHAPES_KERNELS = ["peel_gather_kernel", "peel_empty_kernelILi8EE", "shapes_partner_kernelILi0EE", "shapes_partner_kernelILi1EE",
                   "shapes_partner_kernelILi2EE", "shapes_fit_kernel", "shapes_count_kernelILi0ELb0EE",
                   "shapes_count_kernelILi0ELb1EE", "shapes_count_kernelILi1ELb0EE", "shapes_count_kernelILi1ELb1EE",
-                  "shapes_select_kernel", "shapes_tile_count_kernelILi0EE", "shapes_tile_count_kernelILi1EE",
-                  "shapes_tile_count_kernelILi2EE", "shapes_scan_kernelILi0EE", "shapes_scan_kernelILi1EE",
-                  "shapes_scan_kernelILi2EE", "shapes_scatter_kernelILi0EE", "shapes_scatter_kernelILi1EE",
-                  "shapes_scatter_kernelILi2EE", "shapes_sums_kernel", "shapes_refit_kernel", "shapes_round_end_kernel"]
+                  "peel_select_kernel" + M + "EE", "peel_tile_count_kernel" + M + "Li0EE",
+                  "peel_tile_count_kernel" + M + "Li1EE", "peel_tile_count_kernel" + M + "Li2EE",
+                  "peel_scan_kernel" + M + "Li0EE", "peel_scan_kernel" + M + "Li1EE", "peel_scan_kernel" + M + "Li2EE",
+                  "peel_scatter_kernel" + M + "Li0EE", "peel_scatter_kernel" + M + "Li1EE",
+                  "peel_scatter_kernel" + M + "Li2EE", "shapes_sums_kernel", "shapes_refit_kernel",
+                  "peel_round_end_kernel" + M + "EE"]
 
 
 def test_shapes_kernels_use_no_scratch():

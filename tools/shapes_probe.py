@@ -125,7 +125,7 @@ def trace_summary(d):
     by = {}
     for r in rows:
         name = r["Kernel_Name"].split("(")[0]
-        if "shapes_" not in name and "planes_" not in name and "gs_" not in name:
+        if not any(k in name for k in ("shapes_", "planes_", "peel_", "gs_")):  # (peel_: consensus_peel.h's rounds)
             continue
         by.setdefault(name, []).append((int(r["End_Timestamp"]) - int(r["Start_Timestamp"])) / 1e3)
     out = {"how": "rocprofv3 --kernel-trace --stats --output-format csv -- python tools/shapes_probe.py --reps 3 --only NAME "
