@@ -10,14 +10,13 @@
 //               {nx, ny, nz, usable} record, BESIDE the grid's cell-ordered points (by id for a handle without a grid).
 //               The inner loops below read positions, not ids (what reads by id cost) -- and nothing at
 //               all in the Euclidean form on a grid, whose points are all finite and so all usable.
-//   components  the shape of region growing's grid path (segment.hip, with its measured reasons): in cell order every
-//               usable point hooks itself under the smallest qualifying position below its own, pointer jumping, a union
-//               pass over what is still apart, jumping again.  Every edge from its higher end.  A handle without a grid
-//               (PCGX_RANGE_WALK=1, after DeletePoint: the rebuilt tree of resolve_tree) takes the walk's form of the same
-//               union, positions = ids.  No wave-shared fat-row path, as in region growing: a row of thousands of
-//               coincident points is one lane's loop for each of them.
+//   components  the radius graph's passes (radius_graph.h, with their measured reasons) under ClusterEdge: in cell order
+//               every usable point hooks itself under the smallest qualifying position below its own, pointer jumping, a
+//               union pass over what is still apart, jumping again.  Every edge from its higher end.  A handle without a
+//               grid (PCGX_RANGE_WALK=1, after DeletePoint: the rebuilt tree of resolve_tree) takes the walk's form of
+//               the same union, positions = ids.
 //   sizes and   per root the number of usable points under it and their smallest id, one atomic per distinct root of a
-//   names       wave (rg_min_id_kernel's way); then every point's name (the smallest id), size and sort key.
+//   names       wave (wave_root_flush); then every point's name (the smallest id), size and sort key.
 //   ranking     one stable radix sort of the keys with iota values puts the C seeds first, by decreasing size and
 //               ascending id: a seed's position is its cluster's number.  The count is where the seeds end.
 //   grouping    labels = rank[name]; a second stable sort of the labels with iota values gives the member lists.
@@ -33,8 +32,7 @@
 #include "cluster_terms.h"
 #include "dbscan.h"
 #include "knn_grid.h"
-#include "range_walk.h"
-#include "uf.h"
+#include "radius_graph.h"
 
 namespace pcgx {
 
@@ -90,12 +88,8 @@ __global__ __launch_bounds__(256) void cl_stage_grid_kernel(GridView g, int64_t 
 __global__ __launch_bounds__(256) void cl_stage_tree_kernel(TreeView tv, float bound, const float *__restrict__ normals,
                                                             const float *__restrict__ curvature, float max_curvature,
                                                             uint8_t *__restrict__ usable, float4 *__restrict__ nrm) {
-  const uint32_t b = blockIdx.x * 256u + threadIdx.x + 1u;
-  if (b >= (1u << tv.depth)) return;
-  const int depth = 31 - __clz((int)b);
-  const uint32_t sz = node_size(b, depth, (uint32_t)tv.n + 1u);
-  if (sz == 0u || sz > (uint32_t)tv.n) return;  // slot without a node
-  const float4 nd = node_at(tv.nodes, b);
+  float4 nd;
+  if (!tree_slot_node(tv, blockIdx.x * 256u + threadIdx.x + 1u, &nd)) return;
   const uint32_t id = __float_as_uint(nd.w);
   cl_stage(nd.x, nd.y, nd.z, id, (int64_t)id, bound, normals, curvature, max_curvature, usable, nrm);
 }
@@ -105,122 +99,41 @@ __global__ __launch_bounds__(256) void cl_stage_tree_kernel(TreeView tv, float b
 // nor curvature every point is usable), its usable flag, or its {nx, ny, nz, usable} record.
 enum ClusterRead { kCutNone = 0, kCutFlags = 1, kCutNormals = 2 };
 
-// Does the staged record at position f join a usable point with the normal `mine`?
+// The edge of the radius graph's passes (radius_graph.h): both ends usable, and with normals the cut.  flags: the byte at
+// every position that says whether the point there takes part (density clustering passes its core flags).
 template <int kCut>
-__device__ __forceinline__ bool cl_joins(const uint8_t *__restrict__ usable, const float4 *__restrict__ nrm, const uint32_t f,
-                                         const float4 &mine, const ClusterCut &cut) {
-  if constexpr (kCut == kCutNormals) {
-    const float4 s = nrm[f];
-    return s.w != 0.0f && cluster_normals_agree(mine.x, mine.y, mine.z, s.x, s.y, s.z, cut.min_cos, cut.oriented);
-  } else if constexpr (kCut == kCutFlags) {
-    return usable[f] != 0;
-  } else {
-    return true;
+struct ClusterEdge {
+  static constexpr bool kWalks = kCut != kCutNone;
+  const uint8_t *__restrict__ flags;
+  const float4 *__restrict__ nrm;
+  ClusterCut cut;
+  __device__ __forceinline__ bool live(const uint32_t pos, uint32_t) const { return kCut == kCutNone || flags[pos] != 0; }
+  __device__ __forceinline__ float4 mine(const uint32_t pos, uint32_t) const {
+    if constexpr (kCut == kCutNormals) return nrm[pos];
+    return make_float4(0.0f, 0.0f, 0.0f, 0.0f);
   }
-}
-
-// Region growing's grid passes (rg_grid_kernel, segment.hip) with the staged records in place of the property by id:
-// kHookMin: parent[f0] = the smallest qualifying position below f0 (a store to the lane's own word); else the unions of
-// what is still apart.  An unusable point enumerates nothing and stays its own root.
-template <bool kHookMin, int kCut>
-__global__ __launch_bounds__(256) void cl_grid_kernel(GridView g, int64_t n, float bound, const uint8_t *__restrict__ usable,
-                                                      const float4 *__restrict__ nrm, ClusterCut cut,
-                                                      uint32_t *__restrict__ parent) {
-  const int64_t f0 = (int64_t)blockIdx.x * 256 + threadIdx.x;
-  if (f0 >= n) return;
-  if (kCut != kCutNone && !usable[f0]) return;  // (parent[f0] == f0 from cl_init_kernel)
-  const float4 me = g.pts[f0];
-  float4 mine = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-  if constexpr (kCut == kCutNormals) mine = nrm[f0];
-  uint32_t best = (uint32_t)f0;
-  uint32_t my_root = kHookMin ? (uint32_t)f0 : uf_find(parent, (uint32_t)f0);
-  const GridBox box = grid_cover(g, me.x, me.y, me.z, bound);
-  for (int z = box.z0; z <= box.z1; z++) {
-    for (int y = box.y0; y <= box.y1; y++) {
-      const uint32_t row = ((uint32_t)z * (uint32_t)g.ny + (uint32_t)y) * (uint32_t)g.nx;
-      uint32_t f = g.start[row + (uint32_t)box.x0];
-      uint32_t e = g.start[row + (uint32_t)box.x1 + 1u];
-      e = e < (uint32_t)f0 ? e : (uint32_t)f0;  // each edge from its higher end
-      for (; f < e; f++) {
-        const float4 p = g.pts[f];
-        const float d = ref_dist_sq(p.x, p.y, p.z, me.x, me.y, me.z);
-        if (!(d < bound) || !cl_joins<kCut>(usable, nrm, f, mine, cut)) continue;
-        if (kHookMin) {
-          best = f < best ? f : best;
-        } else {
-          const uint32_t rj = uf_find(parent, f);
-          if (rj != my_root) {
-            uf_union(parent, my_root, rj);
-            my_root = uf_find(parent, my_root);
-          }
-        }
-      }
+  // Does the staged record at position f join a usable point with the normal `mine`?
+  __device__ __forceinline__ bool joins(const uint32_t f, uint32_t, const float4 &mine) const {
+    if constexpr (kCut == kCutNormals) {
+      const float4 s = nrm[f];
+      return s.w != 0.0f && cluster_normals_agree(mine.x, mine.y, mine.z, s.x, s.y, s.z, cut.min_cos, cut.oriented);
+    } else if constexpr (kCut == kCutFlags) {
+      return flags[f] != 0;
+    } else {
+      return true;
     }
   }
-  if (kHookMin) parent[f0] = best;
-}
-
-// The walk's form (rg_union_kernel, segment.hip): one lane per tree node, positions are ids, the larger id unions.
-template <int kCut>
-__global__ __launch_bounds__(kRangeWalkBlock) void cl_walk_kernel(TreeView tv, float bound, const uint8_t *__restrict__ usable,
-                                                                  const float4 *__restrict__ nrm, ClusterCut cut,
-                                                                  uint32_t *__restrict__ parent) {
-  extern __shared__ uint32_t s_stack[];
-  const uint32_t b = blockIdx.x * kRangeWalkBlock + threadIdx.x + 1u;
-  if (b >= (1u << tv.depth)) return;
-  const int depth = 31 - __clz((int)b);
-  const uint32_t sz = node_size(b, depth, (uint32_t)tv.n + 1u);
-  if (sz == 0u || sz > (uint32_t)tv.n) return;  // slot without a node
-  const float4 nd = node_at(tv.nodes, b);
-  const int32_t id = __float_as_int(nd.w);
-  if (!usable[id]) return;
-  float4 mine = make_float4(0.0f, 0.0f, 0.0f, 0.0f);
-  if constexpr (kCut == kCutNormals) mine = nrm[id];
-  uint32_t my_root = (uint32_t)id;
-  range_walk(tv, s_stack + threadIdx.x, kRangeWalkBlock, nd.x, nd.y, nd.z, bound, [&](int32_t j, float) {
-    if (j < id && cl_joins<kCut>(usable, nrm, (uint32_t)j, mine, cut)) {
-      const uint32_t rj = uf_find(parent, (uint32_t)j);
-      if (rj != my_root) {
-        uf_union(parent, my_root, rj);
-        my_root = uf_find(parent, my_root);
-      }
-    }
-  });
-}
+};
 
 // ------------------------------------------------------------------ sizes and names
 // count[root] = usable points under it, min_id[root] = their smallest id.  The lanes of a wave are neighbours in space
-// and mostly of one component: one atomic pair per distinct root of the wave (rg_min_id_kernel: 150k same-address
-// atomics are served one after the other, 2 ms).  pts: the grid's records (positions -> ids), nullptr: positions are ids.
+// and mostly of one component: one atomic pair per distinct root of the wave (wave_root_flush, radius_graph.h, with the
+// measured reason).  pts: the grid's records (positions -> ids), nullptr: positions are ids.
 // Even so a cloud that is one component sends every wave's atomics to one word (218 us at 1M points), so the waves of a
 // workgroup first put the first root each of them meets -- in cell order nearly always the only one -- into LDS, and the
 // first wave merges those entries by the same method: a sixteenth of the atomics.  A wave's further roots go straight
 // to memory.
 constexpr int kStatsBlock = 1024, kStatsWaves = kStatsBlock / 64;
-
-// one (root, count, smallest id) per lane -> memory, one atomic pair per distinct root of the wave; all 64 lanes call it
-__device__ __forceinline__ void cl_stats_flush(const bool valid, const uint32_t root, const uint32_t cnt, const uint32_t id,
-                                               const int lane, unsigned long long todo, uint32_t *__restrict__ count,
-                                               uint32_t *__restrict__ min_id) {
-  while (todo) {  // uniform
-    const int leader = __ffsll((long long)todo) - 1;
-    const uint32_t r = (uint32_t)__builtin_amdgcn_readlane((int)root, leader);
-    const bool mine = valid && root == r;
-    const unsigned long long same = __ballot(mine);
-    uint32_t m = mine ? id : 0xffffffffu, c = mine ? cnt : 0u;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-      const uint32_t v = (uint32_t)__shfl_xor((int)m, o);
-      m = v < m ? v : m;
-      c += (uint32_t)__shfl_xor((int)c, o);
-    }
-    if (lane == leader) {
-      atomicAdd(count + r, c);
-      if (m < __atomic_load_n(min_id + r, __ATOMIC_RELAXED)) atomicMin(min_id + r, m);
-    }
-    todo &= ~same;
-  }
-}
 
 __global__ __launch_bounds__(kStatsBlock) void cl_root_stats_kernel(const float4 *__restrict__ pts, int64_t n,
                                                                     const uint32_t *__restrict__ parent,
@@ -253,12 +166,12 @@ __global__ __launch_bounds__(kStatsBlock) void cl_root_stats_kernel(const float4
     s_cnt[wave] = c0;
     s_min[wave] = m0;
   }
-  cl_stats_flush(valid, root, 1u, id, lane, todo, count, min_id);  // the wave's other roots
+  wave_root_flush<true>(valid, root, 1u, id, lane, todo, count, min_id);  // the wave's other roots
   __syncthreads();
   if (wave == 0) {
     const bool v = lane < kStatsWaves && s_cnt[lane < kStatsWaves ? lane : 0] != 0u;
     const uint32_t rr = v ? s_root[lane] : 0xffffffffu, cc = v ? s_cnt[lane] : 0u, mm = v ? s_min[lane] : 0xffffffffu;
-    cl_stats_flush(v, rr, cc, mm, lane, __ballot(v), count, min_id);
+    wave_root_flush<true>(v, rr, cc, mm, lane, __ballot(v), count, min_id);
   }
 }
 
@@ -356,56 +269,30 @@ pcgx_status clusters_enqueue(const pcgx_kdtree *a, int64_t n, float radius, cons
   hipLaunchKernelGGL(cl_init_kernel, dim3(nb), dim3(256), 0, st, parent, count, min_id, n);
   const bool on_grid = a && a->grid_ok && a->n == n && !range_walk_forced();  // (as region growing takes its source)
   const float4 *pts = on_grid ? a->grid.pts : nullptr;
-  if (on_grid) {
-    const GridView &g = a->grid;
-    if (dense)
-      dbscan_flags_launch(a, true, n, bound, density->min_pts, density->count_all, core, st);
-    else
-      hipLaunchKernelGGL(cl_stage_grid_kernel, dim3(nb), dim3(256), 0, st, g, n, bound, d_normals, d_curvature,
-                         max_curvature, usable, nrm);
-    const int read = d_normals ? kCutNormals : (d_curvature || dense ? kCutFlags : kCutNone);
-    const uint8_t *joins = dense ? core : usable;  // the byte cl_joins reads of a neighbour
-#define PCGX_CL_GRID(HOOK)                                                                                             \
-  do {                                                                                                                 \
-    if (read == kCutNormals)                                                                                           \
-      hipLaunchKernelGGL((cl_grid_kernel<HOOK, kCutNormals>), dim3(nb), dim3(256), 0, st, g, n, bound,                 \
-                         joins, (const float4 *)nrm, cut, parent);                                                     \
-    else if (read == kCutFlags)                                                                                        \
-      hipLaunchKernelGGL((cl_grid_kernel<HOOK, kCutFlags>), dim3(nb), dim3(256), 0, st, g, n, bound,                   \
-                         joins, (const float4 *)nrm, cut, parent);                                                     \
-    else                                                                                                               \
-      hipLaunchKernelGGL((cl_grid_kernel<HOOK, kCutNone>), dim3(nb), dim3(256), 0, st, g, n, bound,                    \
-                         joins, (const float4 *)nrm, cut, parent);                                                     \
-  } while (0)
-    PCGX_CL_GRID(true);
-    hipLaunchKernelGGL(uf_jump_kernel, dim3(nb), dim3(256), 0, st, parent, n);
-    PCGX_CL_GRID(false);
-#undef PCGX_CL_GRID
-    if (dense) dbscan_border_launch(a, true, n, bound, core, usable, parent, st);
-    hipLaunchKernelGGL(uf_jump_kernel, dim3(nb), dim3(256), 0, st, parent, n);
-  } else {
+  if (!on_grid) {
     PCGX_HIP_TRY(hipMemsetAsync(usable, 0, (size_t)n, st));
     if (dense) PCGX_HIP_TRY(hipMemsetAsync(core, 0, (size_t)n, st));
-    if (a) {
+  }
+  if (a) {
+    if (dense) {
+      dbscan_flags_launch(a, on_grid, n, bound, density->min_pts, density->count_all, core, st);
+    } else if (on_grid) {
+      hipLaunchKernelGGL(cl_stage_grid_kernel, dim3(nb), dim3(256), 0, st, a->grid, n, bound, d_normals, d_curvature,
+                         max_curvature, usable, nrm);
+    } else {
       const TreeView tv = a->view();
-      const uint32_t slots = 1u << tv.depth;
-      if (dense)
-        dbscan_flags_launch(a, false, n, bound, density->min_pts, density->count_all, core, st);
-      else
-        hipLaunchKernelGGL(cl_stage_tree_kernel, dim3((slots + 255u) / 256u), dim3(256), 0, st, tv, bound, d_normals,
-                           d_curvature, max_curvature, usable, nrm);
-      const uint8_t *joins = dense ? core : usable;
-      const dim3 wgrid((slots + kRangeWalkBlock - 1) / kRangeWalkBlock), wblock(kRangeWalkBlock);
-      const size_t lds = walk_stack_bytes(tv, kRangeWalkBlock);
-      if (d_normals)
-        hipLaunchKernelGGL(cl_walk_kernel<kCutNormals>, wgrid, wblock, lds, st, tv, bound, (const uint8_t *)usable,
-                           (const float4 *)nrm, cut, parent);
-      else
-        hipLaunchKernelGGL(cl_walk_kernel<kCutFlags>, wgrid, wblock, lds, st, tv, bound, joins, (const float4 *)nrm, cut,
-                           parent);
-      if (dense) dbscan_border_launch(a, false, n, bound, core, usable, parent, st);
-      hipLaunchKernelGGL(uf_jump_kernel, dim3(nb), dim3(256), 0, st, parent, n);
+      hipLaunchKernelGGL(cl_stage_tree_kernel, dim3(((1u << tv.depth) + 255u) / 256u), dim3(256), 0, st, tv, bound,
+                         d_normals, d_curvature, max_curvature, usable, nrm);
     }
+    const uint8_t *flags = dense ? core : usable;  // the byte the edge test reads of a point
+    if (d_normals)
+      PCGX_TRY(rgraph_components_enqueue(a, on_grid, n, bound, ClusterEdge<kCutNormals>{flags, nrm, cut}, parent, st));
+    else if (d_curvature || dense || !on_grid)
+      PCGX_TRY(rgraph_components_enqueue(a, on_grid, n, bound, ClusterEdge<kCutFlags>{flags, nrm, cut}, parent, st));
+    else
+      PCGX_TRY(rgraph_components_enqueue(a, on_grid, n, bound, ClusterEdge<kCutNone>{flags, nrm, cut}, parent, st));
+    if (dense) dbscan_border_launch(a, on_grid, n, bound, core, usable, parent, st);
+    hipLaunchKernelGGL(uf_jump_kernel, dim3(nb), dim3(256), 0, st, parent, n);
   }
   hipLaunchKernelGGL(cl_root_stats_kernel, dim3((unsigned)((n + kStatsBlock - 1) / kStatsBlock)), dim3(kStatsBlock), 0, st,
                      pts, n, (const uint32_t *)parent,

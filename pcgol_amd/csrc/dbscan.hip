@@ -8,22 +8,22 @@
 // The two passes that are new, both one lane per point in the grid's cell order (the walk's form for a handle without a
 // grid: one lane per tree node, positions are ids):
 //   flag pass    counts the members of N(i) and writes the core flag as a byte beside the cell-ordered points, where
-//                cl_grid_kernel<., kCutFlags> reads a byte per candidate.  Only the flag leaves the pass, so with kStop
-//                a lane stops counting at min_pts (DESIGN.md 3.21 has both forms' times).
+//                rgraph_grid_kernel<., ClusterEdge<kCutFlags>> reads a byte per candidate.  Only the flag leaves the
+//                pass, so with kStop a lane stops counting at min_pts (DESIGN.md 3.21 has both forms' times).
 //   border pass  a usable lane that is not core enumerates its whole neighbourhood -- not only the positions below its
 //                own: its nearest core neighbour may lie on either side -- keeps the smallest (DistSq, id) among the core
 //                candidates (dbscan_terms.h) and stores that position into its own parent word.  A store to the lane's
 //                own word, as in the hook pass, and nobody hooks under a border point: it carries no edge.  The pointer
 //                jumping that follows takes it to its component's root.
-// No atomics at all here, no scratch; no wave-shared fat-row path, as in clusters: a row of thousands of coincident
-// points is one lane's loop for each of them (with kStop the flag pass leaves such a row after min_pts records).
+// No atomics at all here, no scratch; no wave-shared fat-row path, as in the radius graph's self scan
+// (radius_graph.h), which the border pass takes whole (with kStop the flag pass leaves a fat row after min_pts records).
 #include <math.h>
 #include <stdlib.h>
 
 #include "dbscan.h"
 #include "dbscan_terms.h"
 #include "knn_grid.h"
-#include "range_walk.h"
+#include "radius_graph.h"
 
 namespace pcgx {
 
@@ -41,9 +41,9 @@ __global__ __launch_bounds__(256) void db_flag_grid_kernel(GridView g, int64_t n
   if (!own) box.z1 = box.z0 - 1;  // an unusable point has nobody in reach
   for (int z = box.z0; more && z <= box.z1; z++) {
     for (int y = box.y0; more && y <= box.y1; y++) {
-      const uint32_t row = ((uint32_t)z * (uint32_t)g.ny + (uint32_t)y) * (uint32_t)g.nx;
-      uint32_t f = g.start[row + (uint32_t)box.x0];
-      const uint32_t e = g.start[row + (uint32_t)box.x1 + 1u];
+      const GridRow r = grid_row(g, z, y, box.x0, box.x1);
+      uint32_t f = r.f;
+      const uint32_t e = r.e;
       // with the stop: four records in flight (range_enum.h's RowScan) and the stop looked at once per four -- tested
       // per record it cost more where it never fires than it saved where it does.  Without it the plain loop below is
       // the whole scan: the compiler pipelines it better than the four written out (DESIGN.md 3.21 has the figures)
@@ -65,22 +65,12 @@ __global__ __launch_bounds__(256) void db_flag_grid_kernel(GridView g, int64_t n
   core[f0] = dbscan_core(own, cnt, min_pts) ? (uint8_t)1 : (uint8_t)0;
 }
 
-// The slot's node, if it has one.
-__device__ __forceinline__ bool db_node(const TreeView &tv, const uint32_t b, float4 *nd) {
-  if (b >= (1u << tv.depth)) return false;
-  const int depth = 31 - __clz((int)b);
-  const uint32_t sz = node_size(b, depth, (uint32_t)tv.n + 1u);
-  if (sz == 0u || sz > (uint32_t)tv.n) return false;
-  *nd = node_at(tv.nodes, b);
-  return true;
-}
-
 // The walk's form: the whole count (the walk has no way out before its end).
 __global__ __launch_bounds__(kRangeWalkBlock) void db_flag_walk_kernel(TreeView tv, float bound, int32_t min_pts,
                                                                        uint8_t *__restrict__ core) {
   extern __shared__ uint32_t s_stack[];
   float4 nd;
-  if (!db_node(tv, blockIdx.x * kRangeWalkBlock + threadIdx.x + 1u, &nd)) return;
+  if (!tree_slot_node(tv, blockIdx.x * kRangeWalkBlock + threadIdx.x + 1u, &nd)) return;
   const bool own = ref_dist_sq(nd.x, nd.y, nd.z, nd.x, nd.y, nd.z) < bound;
   if (!own) return;  // (core[] was zeroed)
   uint32_t cnt = 0u;
@@ -99,29 +89,20 @@ __global__ __launch_bounds__(256) void db_border_grid_kernel(GridView g, int64_t
     return;
   }
   const float4 me = g.pts[f0];
-  const bool own = ref_dist_sq(me.x, me.y, me.z, me.x, me.y, me.z) < bound;
   float best_d = __builtin_inff();
   uint32_t best_id = 0xffffffffu, best_f = (uint32_t)f0;
-  GridBox box = grid_cover(g, me.x, me.y, me.z, bound);
-  if (!own) box.z1 = box.z0 - 1;  // an unusable point is no border point
-  for (int z = box.z0; z <= box.z1; z++) {
-    for (int y = box.y0; y <= box.y1; y++) {
-      const uint32_t row = ((uint32_t)z * (uint32_t)g.ny + (uint32_t)y) * (uint32_t)g.nx;
-      uint32_t f = g.start[row + (uint32_t)box.x0];
-      const uint32_t e = g.start[row + (uint32_t)box.x1 + 1u];
-      for (; f < e; f++) {
-        const float4 p = g.pts[f];
-        const float d = ref_dist_sq(p.x, p.y, p.z, me.x, me.y, me.z);
-        if (!(d < bound) || !core[f]) continue;
-        const uint32_t id = __float_as_uint(p.w);
-        if (dbscan_beats(d, id, best_d, best_id)) {
-          best_d = d;
-          best_id = id;
-          best_f = f;
-        }
-      }
+  // (an unusable point is no border point: no distance from it compares below the bound)
+  grid_self_scan<false>(g, f0, me, bound, [&](const uint32_t f, const float4 &p, const float d) {
+    // a statement of its own: written as `core[f] && dbscan_beats(...)` the record's 16-byte load became a 12-byte one
+    // and a dependent read of the id per core candidate, 8 us of 655 where nearly every point is a border point
+    if (!core[f]) return;
+    const uint32_t id = __float_as_uint(p.w);
+    if (dbscan_beats(d, id, best_d, best_id)) {
+      best_d = d;
+      best_id = id;
+      best_f = f;
     }
-  }
+  });
   const bool border = best_f != (uint32_t)f0;
   kindp[f0] = border ? kDbBorder : kDbNoise;
   if (border) parent[f0] = best_f;
@@ -133,7 +114,7 @@ __global__ __launch_bounds__(kRangeWalkBlock) void db_border_walk_kernel(TreeVie
                                                                          uint32_t *__restrict__ parent) {
   extern __shared__ uint32_t s_stack[];
   float4 nd;
-  if (!db_node(tv, blockIdx.x * kRangeWalkBlock + threadIdx.x + 1u, &nd)) return;
+  if (!tree_slot_node(tv, blockIdx.x * kRangeWalkBlock + threadIdx.x + 1u, &nd)) return;
   const uint32_t id0 = __float_as_uint(nd.w);
   if (core[id0]) {
     kindp[id0] = kDbCore;

@@ -1,5 +1,5 @@
-// uf.h -- the lock-free union-find of the component kernels (segment.hip: flood fill and region growing; cluster.hip:
-// cluster extraction), one statement of it for both.
+// uf.h -- the lock-free union-find of the component kernels (segment.hip: flood fill; radius_graph.h: the radius graph's
+// components for region growing, clusters and DBSCAN), one statement of it for all.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -38,6 +38,16 @@ __device__ __forceinline__ void uf_union(uint32_t *__restrict__ parent, uint32_t
     a = uf_find(parent, old);
     b = uf_find(parent, b);
   }
+}
+
+// An edge from a point last seen under my_root to j: union if j's root differs; returns a root the point is under now.
+__device__ __forceinline__ uint32_t uf_link(uint32_t *__restrict__ parent, uint32_t my_root, const uint32_t j) {
+  const uint32_t rj = uf_find(parent, j);
+  if (rj != my_root) {
+    uf_union(parent, my_root, rj);
+    my_root = uf_find(parent, my_root);
+  }
+  return my_root;
 }
 
 // parent[i] := root of i (every chain descends: roots are their components' smallest members so far)

@@ -10,7 +10,8 @@ sys.path.insert(0, os.path.join(ROOT, "tools"))
 import kernel_resources as KR  # noqa: E402
 
 DBSCAN_KERNELS = ["db_flag_grid_kernelILb0EE", "db_flag_grid_kernelILb1EE", "db_flag_walk_kernel", "db_border_grid_kernel",
-                  "db_border_walk_kernel", "db_kind_kernel"]
+                  "db_border_walk_kernel", "db_kind_kernel",
+                  "uf_jump_kernel"]  # (csrc/radius_graph.h brings csrc/uf.h's per-file copy along; not launched here)
 ROR_KERNELS = ["ror_place_kernel", "ror_keep_count_kernel", "ror_keep_write_kernel"]
 
 

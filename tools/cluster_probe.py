@@ -20,8 +20,9 @@ Each repetition times every call in turn (host clock around the call and a devic
 tools/ndt_probe.py), after two warm-up rounds; the figures are medians over --reps rounds.
 
 The trace summary cuts the dispatch stream into calls (a call starts at uf_init_kernel or cl_init_kernel; (b) shows in
-its cl_grid_kernel's last template argument, (c) and (d) run the same kernels and go by their order in a round) and sums each call's kernels by stage, so the
-pointer-jumping kernel both source files launch under one name is counted for the call it ran in.
+the edge policy of its rgraph_grid_kernel, ClusterEdge<0>; (c) and (d) run the same kernels, ClusterEdge<2>, and go by
+their order in a round) and sums each call's kernels by stage, so the pointer-jumping kernel both source files launch
+under one name is counted for the call it ran in.
 """
 import argparse
 import csv
@@ -36,7 +37,7 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, ROOT)
 
-KERNELS = ("cl_", "rg_", "uf_", "rs_")
+KERNELS = ("cl_", "rg_", "rgraph_", "uf_", "rs_")
 CALLS = ("region_growing", "clusters_dev", "clusters_dev_normals", "clusters_dev_normals_every_edge")
 
 
@@ -112,7 +113,7 @@ def measure(reps):
 
 
 def stage_of(name, seen_rank, seen_label):
-    if "rg_grid_kernel" in name or "cl_grid_kernel" in name or "cl_walk_kernel" in name or "uf_jump_kernel" in name:
+    if "rgraph_grid_kernel" in name or "rgraph_walk_kernel" in name or "uf_jump_kernel" in name:
         return "components"
     if "cl_init_kernel" in name or "cl_stage_" in name:
         return "staging"
@@ -146,8 +147,8 @@ def trace_summary(d):
             calls.append(cur)
         if cur is None:
             continue  # (sorts of the tree builds before the first call)
-        if "cl_grid_kernel" in name:
-            if not name.rstrip().endswith("2>"):
+        if "rgraph_grid_kernel" in name and "ClusterEdge" in name:
+            if "ClusterEdge<2>" not in name:
                 cur["kind"] = CALLS[1]
             elif cur["kind"] is None:  # (c) and (d) run the same kernels: (c) follows (b), (d) follows (c)
                 prev = [c["kind"] for c in calls[:-1] if c["kind"]]

@@ -113,7 +113,7 @@ def stage_of(name, seen_label):
         return "border_pass"
     if "db_kind_kernel" in name:
         return "kind"
-    if "cl_grid_kernel" in name or "cl_walk_kernel" in name or "uf_jump_kernel" in name:
+    if "rgraph_grid_kernel" in name or "rgraph_walk_kernel" in name or "uf_jump_kernel" in name:
         return "components"
     if "cl_init_kernel" in name or "cl_stage_" in name:
         return "staging"
@@ -133,7 +133,7 @@ def trace_summary(d):
     for f in glob.glob(os.path.join(d, "**", "*kernel_trace.csv"), recursive=True):
         with open(f) as fh:
             rows += list(csv.DictReader(fh))
-    rows = [r for r in rows if any(s in r.get("Kernel_Name", "") for s in ("cl_", "db_", "uf_", "rs_"))]
+    rows = [r for r in rows if any(s in r.get("Kernel_Name", "") for s in ("cl_", "db_", "rgraph_", "uf_", "rs_"))]
     rows.sort(key=lambda r: int(r["Start_Timestamp"]))
     calls, cur = [], None
     for r in rows:
