@@ -23,7 +23,8 @@ import (
 // nonMaxRadius, gamma21, gamma32, minNeighbors) (include/pcgx.h, "keypoints"), and cluster extraction,
 // Clusters(radius, pcgx.ClusterParams{...}) (include/pcgx.h, "clusters"), with the geometry of its groups,
 // GroupStats(ids, sizes) (include/pcgx.h, "group geometry"), and what they stand on, GroupHulls(ids, sizes)
-// (include/pcgx.h, "group footprints").
+// (include/pcgx.h, "group footprints"), and minimum-distance subsampling, Thin(radius, seed, score) (include/pcgx.h,
+// "minimum-distance subsampling").
 type KDTree = pcgx.KDTree
 
 // KDTreeOption is kdtree.KDTreeOption (kdtree.go:31).

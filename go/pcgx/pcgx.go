@@ -477,6 +477,44 @@ func (k *KDTree) LocalMaxima(radius float32, score []float32) ([]int64, error) {
 	return ids[:int(m)], nil
 }
 
+// Thin returns a maximal subset of the tree's own points no two of which are within radius of each other, ascending ids,
+// and per point in id order the kept point that stands for it (extension: no reference parity; include/pcgx.h,
+// pcgx_kdtree_thin).  The set is what greedy selection in priority order keeps: by hash(seed, id) where score is nil,
+// else the larger score first, ties to the smaller id.  owner: a kept point itself, a dropped point its kept neighbour
+// of the smallest (DistSq, id), -1 for a deleted id, a non-finite point or a NaN score.
+func (k *KDTree) Thin(radius float32, seed uint32, score []float32) (ids, owner []int64, err error) {
+	runtime.LockOSThread() // the error text is thread-local on the C side: call and pcgx_last_error on one OS thread
+	defer runtime.UnlockOSThread()
+	defer runtime.KeepAlive(k) // the finalizer must not free the handle while a call is in flight
+	var ln C.int64_t
+	if err := status(C.pcgx_kdtree_len(k.t.h, &ln)); err != nil {
+		return nil, nil, err
+	}
+	n := int(ln)
+	if score != nil && len(score) != n {
+		return nil, nil, errors.New("pcgx: one score per point of the tree is required")
+	}
+	ids = make([]int64, n)
+	owner = make([]int64, n)
+	if n == 0 {
+		return ids, owner, nil
+	}
+	var sp *C.float
+	if score != nil {
+		sp = (*C.float)(unsafe.Pointer(&score[0]))
+	}
+	var m C.int64_t
+	rc := C.pcgx_kdtree_thin(k.t.h, C.float(radius), C.uint32_t(seed), sp, (*C.int64_t)(unsafe.Pointer(&ids[0])), &m,
+		(*C.int64_t)(unsafe.Pointer(&owner[0])))
+	runtime.KeepAlive(score)
+	runtime.KeepAlive(ids)
+	runtime.KeepAlive(owner)
+	if err := status(rc); err != nil {
+		return nil, nil, err
+	}
+	return ids[:int(m)], owner, nil
+}
+
 // BoundaryPoints is what (*KDTree).Boundary returns: the boundary points' ids ascending, and per point in id order the
 // longest cyclic run of empty sectors (64 for an empty mask, -1 where the point is not evaluated), the mask of the
 // sectors a neighbour falls in, and the neighbourhood's size.

@@ -1882,6 +1882,62 @@ PCGX_API pcgx_status pcgx_ror_filter_dev(const void *d_data, int64_t n, int32_t 
                                          int32_t min_neighbors, int32_t negative, void *d_out, int64_t *out_n,
                                          void *stream);
 
+/* ------------------------------------------- minimum-distance subsampling (extension: no reference parity)
+ * NOT in the reference.  CloudCompare's "subsample by space", Poisson-disk sampling, greedy non-maximum suppression:
+ * a subset of the tree's ORIGINAL points no two of which are within `radius` of each other, maximal (every dropped
+ * point has a kept one within `radius`), and for every dropped point the kept point that stands for it.  Unlike the
+ * voxel filter the output points are input points, so ids, normals, labels and descriptors carry over; unlike
+ * pcgx_kdtree_local_maxima the selection is greedy and the spacing is guaranteed.  This comment is the contract,
+ * tests/thin_oracle.py restates it.
+ * Eligible points E: the live points (not deleted) whose x, y, z are finite and, in score mode, whose score is no NaN.
+ *   The others are never kept, suppress nobody and have owner -1.
+ * Neighbours: pcgx_kdtree_range_count's set on that handle, DistSq(p_i, p_j) < radius * radius, DistSq the reference's
+ *   float32 expression, the product float32, the bound STRICT: two kept points have DistSq >= the bound, and a point at
+ *   exactly DistSq == bound suppresses nothing.
+ * Priority, a total order on E.  score == NULL (hash mode): the smaller ((uint64)mix(seed, id) << 32) | id comes first,
+ *   mix the partner rule's of "shapes" (csrc/shape_terms.h: shape_mix).  Score mode: j comes before i iff
+ *   score[j] > score[i], or they are equal (-0 == +0) and j < i; scores <= 0 and +-inf are ordinary values here.
+ * Kept set K: what visiting E in priority order and keeping a point iff no kept point is its neighbour keeps -- the
+ *   lexicographically first maximal independent set of the radius graph on E.  Given the order it is unique, so the
+ *   result is a property of the point set: the same bits on every call, on every kind of handle (grid,
+ *   PCGX_RANGE_WALK=1, after DeletePoint) and whatever the schedule.
+ * Outputs: ids[Len()] = K ascending, -1 in every remaining slot; *n_ids = |K|; owner[Len()] (may be NULL) = the point
+ *   itself for a kept point, for a dropped point of E its kept neighbour with the smallest (DistSq, id) (the rule of
+ *   "density clusters" for a border point), -1 for every other point.
+ * Rounds (csrc/thin.hip).  One round decides every still undecided point i of E from the states AS THE PREVIOUS ROUND
+ *   LEFT THEM: a neighbour before i is KEPT -> i is DROPPED; else no neighbour before i is UNDECIDED -> i is KEPT; else
+ *   i stays.  Rounds to completion give K; the states after R rounds are a property of the set as well.  Hash mode needs
+ *   O(log n) rounds; a smooth score gives chains as long as the cloud is wide in radii.
+ * The host form always finishes: it enqueues batches of pcgx_thin_default_rounds() rounds and reads one count word per
+ *   batch until it is zero.
+ * PCGX_E_INVALID: a NULL tree; a radius that is not finite and > 0, or whose float32 square is not (a bound of 0 holds
+ *   nobody, not a point itself); NULL ids or n_ids with Len() > 0; more than 2^31 - 1 points; max_rounds < 0.
+ *   Len() == 0: *n_ids = 0, PCGX_OK. */
+PCGX_API pcgx_status pcgx_kdtree_thin(const pcgx_kdtree *t, float radius, uint32_t seed,
+                                      const float *score /* [Len()] or NULL */, int64_t *ids /* [Len()] */,
+                                      int64_t *n_ids, int64_t *owner /* [Len()], may be NULL */);
+/* Same, every array device resident (ids and owners are int32 there), enqueued on `stream` (NULL: the library's);
+ * returns without waiting and reads nothing back.  It enqueues max_rounds rounds (0: pcgx_thin_default_rounds()), each
+ * of which returns at once when nothing is undecided.  *d_n_left (may be NULL) receives the number of points still
+ * undecided.  0: the outputs are the contract's.  > 0: d_ids / d_n_ids hold the points decided KEPT so far -- a subset
+ * of K, pairwise at least `radius` apart, not yet maximal -- and d_owner is -2 in every slot. */
+PCGX_API pcgx_status pcgx_kdtree_thin_dev(const pcgx_kdtree *t, float radius, uint32_t seed,
+                                          const float *d_score /* [Len()] or NULL */, int32_t max_rounds,
+                                          int32_t *d_ids /* [Len()] */, int32_t *d_n_ids,
+                                          int32_t *d_owner /* [Len()], may be NULL */, int32_t *d_n_left, void *stream);
+PCGX_API int32_t pcgx_thin_default_rounds(void);
+/* The filter form over an AoS cloud (stride / xyz_off as pcgx_voxel_filter), in the shape of pcgx_ror_filter: F = the
+ * records whose x, y, z are all finite; a tree over F is built inside the call; the kept records are hash mode's K
+ * over that tree (ids: positions in F), byte for byte, in input order; *out_n of them (out_data must hold n*stride
+ * bytes).  PCGX_E_INVALID: a radius that is not finite and > 0; a stride / offset that does not hold an xyz triple ->
+ * PCGX_E_BAD_FIELD; n == 0 or F empty -> PCGX_E_NO_POINT. */
+PCGX_API pcgx_status pcgx_thin_filter(const void *data, int64_t n, int32_t stride, int32_t xyz_off, float radius,
+                                      uint32_t seed, void *out_data, int64_t *out_n);
+/* Device resident: d_data and d_out (>= n*stride bytes) are device buffers; out_n is host memory.  Returns when
+ * everything is done on `stream`. */
+PCGX_API pcgx_status pcgx_thin_filter_dev(const void *d_data, int64_t n, int32_t stride, int32_t xyz_off, float radius,
+                                          uint32_t seed, void *d_out, int64_t *out_n, void *stream);
+
 /* ------------------------------------------- Normal Distributions Transform (extension: no reference parity)
  * NOT in the reference: pcgol has nothing like it.  NDT registration (Biber and Strasser 2003; Magnusson 2009; PCL's
  * NormalDistributionsTransform) as a fourth Fit beside point-to-point, point-to-plane and Generalized ICP.  It needs

@@ -324,6 +324,11 @@ SIGNATURES = {
     "pcgx_sor_filter_dev": (_i32, [_vp, _i64, _i32, _i32, _i32, _f32, _i32, _vp, C.POINTER(_i64), _vp, _vp, _vp]),
     "pcgx_ror_filter": (_i32, [_vp, _i64, _i32, _i32, _f32, _i32, _i32, _vp, C.POINTER(_i64)]),
     "pcgx_ror_filter_dev": (_i32, [_vp, _i64, _i32, _i32, _f32, _i32, _i32, _vp, C.POINTER(_i64), _vp]),
+    "pcgx_kdtree_thin": (_i32, [_vp, _f32, _u32, _vp, _vp, C.POINTER(_i64), _vp]),
+    "pcgx_kdtree_thin_dev": (_i32, [_vp, _f32, _u32, _vp, _i32, _vp, _vp, _vp, _vp, _vp]),
+    "pcgx_thin_default_rounds": (_i32, []),
+    "pcgx_thin_filter": (_i32, [_vp, _i64, _i32, _i32, _f32, _u32, _vp, C.POINTER(_i64)]),
+    "pcgx_thin_filter_dev": (_i32, [_vp, _i64, _i32, _i32, _f32, _u32, _vp, C.POINTER(_i64), _vp]),
     "pcgx_ndt_map_create": (_i32, [_vp, _vp, _i64, _i32, _i32, _i32, _i32, _f32, C.POINTER(_vp)]),
     "pcgx_ndt_map_free": (_i32, [_vp]),
     "pcgx_ndt_map_counts": (_i32, [_vp, C.POINTER(_i64), C.POINTER(_i64)]),

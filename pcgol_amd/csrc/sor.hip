@@ -232,8 +232,10 @@ __global__ __launch_bounds__(256) void ror_keep_write_kernel(const uint8_t *__re
 
 // The whole filter on device records; temporaries from `ka` (begun by the caller), the tree's and the flag pass's from
 // the context's arena.  Returns with st drained.
-pcgx_status ror_run(const uint8_t *d_data, int64_t n, int32_t stride, int32_t off, float radius, int32_t min_neighbors,
-                    int32_t negative, uint8_t *d_out, int64_t *out_n, hipStream_t st, Arena &ka) {
+// flag_pass(tree, d_core): one byte per tree id, nonzero for the points step 5 is to take as 1 (the others as 2).
+template <class FlagPass>
+pcgx_status flag_filter_run(const char *fn, const uint8_t *d_data, int64_t n, int32_t stride, int32_t off, uint8_t want,
+                            FlagPass flag_pass, uint8_t *d_out, int64_t *out_n, hipStream_t st, Arena &ka) {
   const int ntiles = (int)((n + kRunTile - 1) / kRunTile);
   uint32_t *tile_count = nullptr, *d_total = nullptr;
   float *d_xyz = nullptr;
@@ -255,22 +257,20 @@ pcgx_status ror_run(const uint8_t *d_data, int64_t n, int32_t stride, int32_t of
   PCGX_HIP_TRY(hipMemcpyAsync(&m32, d_total, 4, hipMemcpyDeviceToHost, st));
   PCGX_HIP_TRY(hipStreamSynchronize(st));
   const int64_t m = m32;
-  if (m == 0) return fail(PCGX_E_NO_POINT, "pcgx_ror_filter: no finite point");
+  if (m == 0) return fail(PCGX_E_NO_POINT, "%s: no finite point", fn);
   // 2. the tree
   RawVector<float> h_xyz((size_t)m * 3);
   PCGX_TRY(staged_download(h_xyz.data(), d_xyz, (size_t)m * 12, st));
   pcgx_kdtree *raw = nullptr;
   PCGX_TRY(pcgx_kdtree_build(h_xyz.data(), m, 12, 0, &raw));
   std::unique_ptr<pcgx_kdtree, TreeFree> tree(raw);
-  // 3. the core flag per tree id
-  PCGX_TRY(ctx().arena.begin(st));
-  PCGX_TRY(dbscan_core_by_id_enqueue(tree.get(), radius, min_neighbors, d_core, st));
+  // 3. the flag per tree id
+  PCGX_TRY(flag_pass(tree.get(), d_core));
   // by input index
   PCGX_HIP_TRY(hipMemsetAsync(d_flag, 0, (size_t)n, st));
   hipLaunchKernelGGL(ror_place_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, st, (const uint8_t *)d_core,
                      (const int64_t *)d_orig, m, d_flag);
   // 5. the kept records
-  const uint8_t want = negative ? (uint8_t)2 : (uint8_t)1;
   hipLaunchKernelGGL(ror_keep_count_kernel, dim3(ntiles), dim3(256), 0, st, (const uint8_t *)d_flag, n, want, tile_count);
   hipLaunchKernelGGL(sor_scan_kernel, dim3(1), dim3(1024), 0, st, tile_count, ntiles, d_total + 1);
   hipLaunchKernelGGL(ror_keep_write_kernel, dim3(ntiles), dim3(256), 0, st, (const uint8_t *)d_flag, n, want,
@@ -283,6 +283,29 @@ pcgx_status ror_run(const uint8_t *d_data, int64_t n, int32_t stride, int32_t of
   return PCGX_OK;
 }
 
+pcgx_status ror_run(const uint8_t *d_data, int64_t n, int32_t stride, int32_t off, float radius, int32_t min_neighbors,
+                    int32_t negative, uint8_t *d_out, int64_t *out_n, hipStream_t st, Arena &ka) {
+  return flag_filter_run(
+      "pcgx_ror_filter", d_data, n, stride, off, negative ? (uint8_t)2 : (uint8_t)1,
+      [&](const pcgx_kdtree *tree, uint8_t *d_core) -> pcgx_status {
+        PCGX_TRY(ctx().arena.begin(st));
+        return dbscan_core_by_id_enqueue(tree, radius, min_neighbors, d_core, st);
+      },
+      d_out, out_n, st, ka);
+}
+
+// pcgx_thin_filter: the same pipeline once more, step 3 minimum-distance subsampling in hash mode (thin.hip): the kept
+// points are its kept set.
+pcgx_status thin_kept_by_id(const pcgx_kdtree *t, float radius, uint32_t seed, uint8_t *d_kept, hipStream_t st);
+
+pcgx_status thin_filter_run(const uint8_t *d_data, int64_t n, int32_t stride, int32_t off, float radius, uint32_t seed,
+                            uint8_t *d_out, int64_t *out_n, hipStream_t st, Arena &ka) {
+  return flag_filter_run(
+      "pcgx_thin_filter", d_data, n, stride, off, (uint8_t)1,
+      [&](const pcgx_kdtree *tree, uint8_t *d_kept) { return thin_kept_by_id(tree, radius, seed, d_kept, st); }, d_out,
+      out_n, st, ka);
+}
+
 pcgx_status ror_check(const char *fn, const void *data, int64_t n, int32_t stride, int32_t off, float radius,
                       int32_t min_neighbors, const void *out, const int64_t *out_n) {
   if (!out_n || n < 0 || (n > 0 && (!data || !out))) return fail(PCGX_E_INVALID, "%s: bad argument", fn);
@@ -291,6 +314,14 @@ pcgx_status ror_check(const char *fn, const void *data, int64_t n, int32_t strid
   if (stride < 12 || off < 0 || off + 12 > stride)
     return fail(PCGX_E_BAD_FIELD, "%s: stride %d / xyz offset %d do not hold an xyz triple", fn, (int)stride, (int)off);
   if (n == 0) return fail(PCGX_E_NO_POINT, "%s: empty cloud", fn);
+  return PCGX_OK;
+}
+
+pcgx_status thin_filter_check(const char *fn, const void *data, int64_t n, int32_t stride, int32_t off, float radius,
+                              const void *out, const int64_t *out_n) {
+  PCGX_TRY(ror_check(fn, data, n, stride, off, radius, 1, out, out_n));
+  if (!(radius * radius > 0.0f && radius * radius < __builtin_inff()))
+    return fail(PCGX_E_INVALID, "%s: the float32 square of the radius must be finite and > 0", fn);
   return PCGX_OK;
 }
 
@@ -364,6 +395,37 @@ extern "C" pcgx_status pcgx_sor_filter(const void *data, int64_t n, int32_t stri
   PCGX_TRY(sor_run(d_in, n, stride, xyz_off, mean_k, std_mul, negative, d_out, &kept, d_md, stats, st, ka));
   PCGX_TRY(staged_download(out_data, d_out, (size_t)kept * (size_t)stride, st));
   if (mean_dist) PCGX_TRY(staged_download(mean_dist, d_md, (size_t)n * 8, st));
+  *out_n = kept;
+  return PCGX_OK;
+}
+
+extern "C" pcgx_status pcgx_thin_filter_dev(const void *d_data, int64_t n, int32_t stride, int32_t xyz_off, float radius,
+                                            uint32_t seed, void *d_out, int64_t *out_n, void *stream) {
+  PCGX_API_LOCK();
+  PCGX_TRY(thin_filter_check("pcgx_thin_filter_dev", d_data, n, stride, xyz_off, radius, d_out, out_n));
+  PCGX_TRY(ensure_init());
+  hipStream_t st = pick_stream(stream);
+  Arena &ka = ctx().host_arena;
+  PCGX_TRY(ka.begin(st));
+  return thin_filter_run((const uint8_t *)d_data, n, stride, xyz_off, radius, seed, (uint8_t *)d_out, out_n, st, ka);
+}
+
+extern "C" pcgx_status pcgx_thin_filter(const void *data, int64_t n, int32_t stride, int32_t xyz_off, float radius,
+                                        uint32_t seed, void *out_data, int64_t *out_n) {
+  PCGX_API_CALL();
+  PCGX_TRY(thin_filter_check("pcgx_thin_filter", data, n, stride, xyz_off, radius, out_data, out_n));
+  PCGX_TRY(ensure_init());
+  hipStream_t st = ctx().stream;
+  Arena &ka = ctx().host_arena;
+  PCGX_TRY(ka.begin(st));
+  const size_t bytes = (size_t)n * (size_t)stride;
+  uint8_t *d_in = nullptr, *d_out = nullptr;
+  PCGX_TRY(ka.alloc_n(bytes, &d_in));
+  PCGX_TRY(ka.alloc_n(bytes, &d_out));
+  PCGX_TRY(staged_upload(d_in, data, bytes, st));
+  int64_t kept = 0;
+  PCGX_TRY(thin_filter_run(d_in, n, stride, xyz_off, radius, seed, d_out, &kept, st, ka));
+  if (kept > 0) PCGX_TRY(staged_download(out_data, d_out, (size_t)kept * (size_t)stride, st));
   *out_n = kept;
   return PCGX_OK;
 }

@@ -247,6 +247,26 @@ class KDTree {  // pc/storage/kdtree/kdtree.go:14-23
     ids.resize((size_t)m);
     return ids;
   }
+  // Minimum-distance subsampling (extension: no reference parity; include/pcgx.h, pcgx_kdtree_thin): a maximal subset of
+  // the tree's own points no two of which are within radius, the one greedy selection keeps -- by hash(seed, id) where
+  // `score` is empty, else the larger score first, ties to the smaller id.  ids: ascending; owner (id order, filled
+  // where withOwner): a kept point itself, a dropped point its kept neighbour of the smallest (DistSq, id), -1 for a
+  // point that takes no part.
+  struct ThinResult {
+    std::vector<int64_t> ids, owner;
+  };
+  ThinResult Thin(float radius, uint32_t seed = 0, const std::vector<float> &score = {}, bool withOwner = false) const {
+    const int64_t n = Len();
+    if (!score.empty() && (int64_t)score.size() != n) throw Error(PCGX_E_INVALID, "one score per point of the tree is required");
+    ThinResult r;
+    r.ids.resize((size_t)n);
+    if (withOwner) r.owner.resize((size_t)n);
+    int64_t m = 0;
+    check(pcgx_kdtree_thin(h_.get(), radius, seed, score.empty() ? nullptr : score.data(), r.ids.data(), &m,
+                           withOwner ? r.owner.data() : nullptr));
+    r.ids.resize((size_t)m);
+    return r;
+  }
   // ISS keypoints (extension: no reference parity; include/pcgx.h, pcgx_kdtree_iss_keypoints).  eigenvalues: of
   // Normals' covariance at salientRadius, ascending, {0, 0, 0} where Normals answers "degenerate"; saliency: the
   // smallest eigenvalue of a salient point, else 0; ids: LocalMaxima(nonMaxRadius, saliency).  All in id order.

@@ -368,6 +368,37 @@ class KDTree:
             L.ptr(int(d_eigenvalues)) if d_eigenvalues else None, L.ptr(int(d_saliency)) if d_saliency else None,
             L.ptr(int(d_ids)), L.ptr(int(d_n_ids)), L.ptr(stream) if stream else None))
 
+    # -- extension (no reference parity): minimum-distance subsampling, a maximal set of points at least radius apart
+    def Thin(self, radius, Seed=0, Score=None, Owner=False):
+        """A maximal subset of the tree's own points no two of which are within radius (DistSq < radius^2, Range's
+        set, strict) -> ids int64 ascending, or (ids, owner int64 (n,)) with Owner=True.  The set is what greedy
+        selection in priority order keeps: by hash(Seed, id) when Score is None, else the larger Score first, ties to
+        the smaller id (a NaN score, a deleted id or a non-finite point takes no part: owner -1).  owner: a kept point
+        itself, a dropped point its kept neighbour of the smallest (DistSq, id) (include/pcgx.h, pcgx_kdtree_thin)."""
+        n = self.Len()
+        score = None
+        if Score is not None:
+            score = L.f32c(Score).reshape(-1)
+            if len(score) != n:
+                raise ValueError("one score per point of the tree is required")
+        ids = np.empty(n, np.int64)
+        owner = np.empty(n, np.int64) if Owner else None
+        cnt = C.c_int64()
+        L.check(L.lib().pcgx_kdtree_thin(self._h, float(radius), int(Seed) & 0xffffffff, L.ptr(score), L.ptr(ids),
+                                         C.byref(cnt), L.ptr(owner)))
+        return (ids[:cnt.value], owner) if Owner else ids[:cnt.value]
+
+    def ThinDev(self, radius, d_ids, d_n_ids, d_n_left, d_owner=0, d_score=0, Seed=0, MaxRounds=0, stream=0):
+        """Device-resident Thin: raw device addresses (e.g. torch .data_ptr()); d_ids int32 [Len()] (the kept ids
+        ascending, then -1), d_n_ids and d_n_left one int32 each, d_owner int32 [Len()], d_score float32 [Len()].
+        MaxRounds rounds are enqueued (0: the library's default); *d_n_left > 0 afterwards means the kept set is not
+        maximal yet and d_owner is all -2.  Enqueued on `stream`, returns without waiting."""
+        L.check(L.lib().pcgx_kdtree_thin_dev(
+            self._h, float(radius), int(Seed) & 0xffffffff, L.ptr(int(d_score)) if d_score else None, int(MaxRounds),
+            L.ptr(int(d_ids)) if d_ids else None, L.ptr(int(d_n_ids)) if d_n_ids else None,
+            L.ptr(int(d_owner)) if d_owner else None, L.ptr(int(d_n_left)) if d_n_left else None,
+            L.ptr(stream) if stream else None))
+
     # -- extension (no reference parity): boundary points, where a scanned surface ends
     def Boundary(self, radius, Normals, MinGap=16, MinNeighbors=1):
         """The points whose radius neighbours (DistSq < radius^2, Range's set) leave an angular gap of at least MinGap
