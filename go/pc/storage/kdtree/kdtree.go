@@ -24,7 +24,8 @@ import (
 // Clusters(radius, pcgx.ClusterParams{...}) (include/pcgx.h, "clusters"), with the geometry of its groups,
 // GroupStats(ids, sizes) (include/pcgx.h, "group geometry"), and what they stand on, GroupHulls(ids, sizes)
 // (include/pcgx.h, "group footprints"), and minimum-distance subsampling, Thin(radius, seed, score) (include/pcgx.h,
-// "minimum-distance subsampling").
+// "minimum-distance subsampling"), and farthest-point sampling to a target count, FarthestPoints(count, start)
+// (include/pcgx.h, "farthest-point sampling").
 type KDTree = pcgx.KDTree
 
 // KDTreeOption is kdtree.KDTreeOption (kdtree.go:31).

@@ -515,6 +515,54 @@ func (k *KDTree) Thin(radius float32, seed uint32, score []float32) (ids, owner 
 	return ids[:int(m)], owner, nil
 }
 
+// FarthestResult is what (*KDTree).FarthestPoints returns: the picks in pick order, the d of each pick at the moment it
+// was picked (the first +Inf, then non-increasing), the d the next pick would have had (-1 when no point is left), and
+// per point in id order the id of the pick nearest to it (the earlier pick among equal distances, -1 for a deleted id or
+// a non-finite point).
+type FarthestResult struct {
+	IDs     []int64
+	DistSq  []float32
+	CoverSq float32
+	Owner   []int64
+}
+
+// FarthestPoints returns count of the tree's own points, each the one farthest from those picked before it (float32
+// DistSq to the nearest pick so far, ties to the smallest id), starting at start or, for -1, at the smallest eligible id
+// (extension: no reference parity; include/pcgx.h, pcgx_kdtree_fps).  There are min(count, eligible points) picks, and
+// they are the first picks of any larger count: one call orders a cloud so that every prefix is a sampling of its own.
+func (k *KDTree) FarthestPoints(count int, start int64) (*FarthestResult, error) {
+	runtime.LockOSThread() // the error text is thread-local on the C side: call and pcgx_last_error on one OS thread
+	defer runtime.UnlockOSThread()
+	defer runtime.KeepAlive(k) // the finalizer must not free the handle while a call is in flight
+	if count < 0 {
+		return nil, errors.New("pcgx: count must be >= 0")
+	}
+	var ln C.int64_t
+	if err := status(C.pcgx_kdtree_len(k.t.h, &ln)); err != nil {
+		return nil, err
+	}
+	n := int(ln)
+	res := &FarthestResult{IDs: make([]int64, count), DistSq: make([]float32, count), CoverSq: -1, Owner: make([]int64, n)}
+	var ip, op *C.int64_t
+	var dp *C.float
+	if count > 0 {
+		ip = (*C.int64_t)(unsafe.Pointer(&res.IDs[0]))
+		dp = (*C.float)(unsafe.Pointer(&res.DistSq[0]))
+	}
+	if n > 0 {
+		op = (*C.int64_t)(unsafe.Pointer(&res.Owner[0]))
+	}
+	var m C.int64_t
+	var cover C.float
+	rc := C.pcgx_kdtree_fps(k.t.h, C.int64_t(count), C.int64_t(start), ip, &m, dp, &cover, op)
+	runtime.KeepAlive(res)
+	if err := status(rc); err != nil {
+		return nil, err
+	}
+	res.IDs, res.DistSq, res.CoverSq = res.IDs[:int(m)], res.DistSq[:int(m)], float32(cover)
+	return res, nil
+}
+
 // BoundaryPoints is what (*KDTree).Boundary returns: the boundary points' ids ascending, and per point in id order the
 // longest cyclic run of empty sectors (64 for an empty mask, -1 where the point is not evaluated), the mask of the
 // sectors a neighbour falls in, and the neighbourhood's size.

@@ -1938,6 +1938,67 @@ PCGX_API pcgx_status pcgx_thin_filter(const void *data, int64_t n, int32_t strid
 PCGX_API pcgx_status pcgx_thin_filter_dev(const void *d_data, int64_t n, int32_t stride, int32_t xyz_off, float radius,
                                           uint32_t seed, void *d_out, int64_t *out_n, void *stream);
 
+/* ------------------------------------------- farthest-point sampling (extension: no reference parity)
+ * NOT in the reference.  PointNet++'s sampling layer, Open3D's farthest_point_down_sample: `count` of the tree's
+ * ORIGINAL points, each as far as possible from the ones picked before it, in pick order.  Where the voxel filter takes a
+ * leaf and pcgx_kdtree_thin a radius, this takes a target count.  This comment is the contract, tests/fps_oracle.py
+ * restates it.
+ * Eligible points E: the live points (not deleted) whose x, y, z are all finite.  Every other point is never picked
+ *   and has owner -1.
+ * Distance: DistSq, the reference's float32 expression (dx dx + dy dy) + dz dz of d = p - q, never contracted.  It is
+ *   symmetric in its two points bit for bit; on E it is never NaN, it is >= +0, and it may be +inf on overflow.
+ * Start: start >= 0 is the first pick and must lie in E; start = -1 means the smallest id in E.
+ * Pick j + 1: among the points of E not yet picked, the one with the largest d_j(p) = the minimum of
+ *   DistSq(p, pick_i) over the picks 1 .. j; ties go to the smallest id.  A picked point is never a candidate again;
+ *   coincident points have d = 0 and come last, in id order.
+ * Stop: after min(count, |E|) picks.
+ * Outputs: ids[count] = the picks in pick order, then -1; *n_ids = how many.  dist_sq[count] (may be NULL) = d of each
+ *   pick at the moment it was picked: the first +inf, the tail -1.0f; from the second entry on it does not increase.
+ *   *cover_sq (may be NULL) = the d the next pick would have had, the largest d among the unpicked points of E: every
+ *   point of E lies within it of a pick; -1.0f when none is left.  owner[Len()] (may be NULL) = for a point of E the
+ *   id of the pick nearest to it, among equal DistSq the EARLIER pick (an owner changes only when a later pick is
+ *   strictly nearer: not pcgx_kdtree_thin's (DistSq, id) rule); -1 for every other point.
+ * Prefix property: a maximum with a fixed tie rule does not depend on the schedule, so the result is a property of the
+ *   point set -- the same bits on every call and every kind of handle -- and ids and dist_sq for `count` are the first
+ *   `count` entries of those for any larger count, and cover_sq is that call's dist_sq[count] (-1.0f where that is
+ *   padding).  One call orders a cloud so that every prefix is a sampling of its own.
+ * How (csrc/fps.hip): the points in Morton order, in tiles that carry their box and their largest d; a pick skips every
+ *   tile whose box is at least that far away, which is exact in float32 (csrc/fps_terms.h states the lemma).  One
+ *   launch per pick: the cost is a chain of `count` launches, so for a count above a fraction of Len() a radius and
+ *   pcgx_kdtree_thin is the tool.
+ * PCGX_E_INVALID, with nothing written: a NULL tree; count < 0 (or above 2^31 - 1); NULL ids or n_ids with Len() > 0
+ *   and count > 0; start not in [-1, Len()); start not in E.
+ *   Len() == 0, count == 0, or an empty E with start = -1: *n_ids = 0, every output slot holds its padding value,
+ *   PCGX_OK. */
+PCGX_API pcgx_status pcgx_kdtree_fps(const pcgx_kdtree *t, int64_t count, int64_t start, int64_t *ids /* [count] */,
+                                     int64_t *n_ids, float *dist_sq /* [count], may be NULL */,
+                                     float *cover_sq /* may be NULL */, int64_t *owner /* [Len()], may be NULL */);
+/* Same, every array device resident (ids and owners are int32 there), enqueued on `stream` (NULL: the library's);
+ * returns without waiting and reads nothing back: `start` is checked against the handle's host copy. */
+PCGX_API pcgx_status pcgx_kdtree_fps_dev(const pcgx_kdtree *t, int64_t count, int64_t start,
+                                         int32_t *d_ids /* [count] */, int32_t *d_n_ids,
+                                         float *d_dist_sq /* [count], may be NULL */, float *d_cover_sq /* may be NULL */,
+                                         int32_t *d_owner /* [Len()], may be NULL */, void *stream);
+/* Measurement hook (tools/fps_probe.py).  d_touched == NULL: the call's preparation alone -- the ordered copy of the
+ * points, the tiles (rebuilt by every call, not kept on the handle) -- enqueued on `stream`, no output.  Else the steps
+ * run too and d_touched[j] (device, uint32 [min(count, Len())]) = the tiles step j touched. */
+PCGX_API pcgx_status pcgx_kdtree_fps_prep_dev(const pcgx_kdtree *t, int64_t count, uint32_t *d_touched, void *stream);
+/* How a call over n points is cut up (csrc/fps_plan.h), for tests that want sizes at the seams: out4 = {points per
+ * tile, tiles, tiles per workgroup of a pick launch, workgroups of a pick launch}; zeros for n == 0 or count == 0. */
+PCGX_API pcgx_status pcgx_fps_plan(int64_t n, int64_t count, int64_t out4[4]);
+/* The filter form over an AoS cloud (stride / xyz_off as pcgx_voxel_filter), in the shape of pcgx_thin_filter: F = the
+ * records whose x, y, z are all finite; a tree over F is built inside the call; the output records are the picks over
+ * that tree (start: -1, or a position in F), byte for byte, IN PICK ORDER -- not pcgx_thin_filter's input order: the
+ * prefix property is the point; *out_n = min(count, |F|) of them (out_data must hold n*stride bytes).
+ * PCGX_E_INVALID: count < 0, start not in [-1, |F|); a stride / offset that does not hold an xyz triple ->
+ * PCGX_E_BAD_FIELD; n == 0 or F empty -> PCGX_E_NO_POINT. */
+PCGX_API pcgx_status pcgx_fps_filter(const void *data, int64_t n, int32_t stride, int32_t xyz_off, int64_t count,
+                                     int64_t start, void *out_data, int64_t *out_n);
+/* Device resident: d_data and d_out (>= n*stride bytes) are device buffers; out_n is host memory.  Returns when
+ * everything is done on `stream`. */
+PCGX_API pcgx_status pcgx_fps_filter_dev(const void *d_data, int64_t n, int32_t stride, int32_t xyz_off, int64_t count,
+                                         int64_t start, void *d_out, int64_t *out_n, void *stream);
+
 /* ------------------------------------------- Normal Distributions Transform (extension: no reference parity)
  * NOT in the reference: pcgol has nothing like it.  NDT registration (Biber and Strasser 2003; Magnusson 2009; PCL's
  * NormalDistributionsTransform) as a fourth Fit beside point-to-point, point-to-plane and Generalized ICP.  It needs

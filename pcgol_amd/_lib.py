@@ -329,6 +329,12 @@ SIGNATURES = {
     "pcgx_thin_default_rounds": (_i32, []),
     "pcgx_thin_filter": (_i32, [_vp, _i64, _i32, _i32, _f32, _u32, _vp, C.POINTER(_i64)]),
     "pcgx_thin_filter_dev": (_i32, [_vp, _i64, _i32, _i32, _f32, _u32, _vp, C.POINTER(_i64), _vp]),
+    "pcgx_kdtree_fps": (_i32, [_vp, _i64, _i64, _vp, C.POINTER(_i64), _vp, _vp, _vp]),
+    "pcgx_kdtree_fps_dev": (_i32, [_vp, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "pcgx_kdtree_fps_prep_dev": (_i32, [_vp, _i64, _vp, _vp]),
+    "pcgx_fps_plan": (_i32, [_i64, _i64, _vp]),
+    "pcgx_fps_filter": (_i32, [_vp, _i64, _i32, _i32, _i64, _i64, _vp, C.POINTER(_i64)]),
+    "pcgx_fps_filter_dev": (_i32, [_vp, _i64, _i32, _i32, _i64, _i64, _vp, C.POINTER(_i64), _vp]),
     "pcgx_ndt_map_create": (_i32, [_vp, _vp, _i64, _i32, _i32, _i32, _i32, _f32, C.POINTER(_vp)]),
     "pcgx_ndt_map_free": (_i32, [_vp]),
     "pcgx_ndt_map_counts": (_i32, [_vp, C.POINTER(_i64), C.POINTER(_i64)]),

@@ -17,6 +17,18 @@
 
 namespace pcgx {
 
+// The reference's DistSq in float32 (mat/vec3.go:18-20,38-40): (dx * dx + dy * dy) + dz * dz with d = p - q, never
+// contracted (-ffp-contract=off on both sides)
+#if defined(__HIPCC__)
+__host__ __device__ inline __attribute__((always_inline))  // (hip_runtime.h's __forceinline__, spelt out)
+#else
+inline
+#endif
+float ref_dist_sq(const float px, const float py, const float pz, const float qx, const float qy, const float qz) {
+  const float dx = px - qx, dy = py - qy, dz = pz - qz;
+  return (dx * dx + dy * dy) + dz * dz;
+}
+
 struct Mat4 {
   float m[16];  // column-major: m[4*col + row]   (mat/mat4.go:8-10)
 };

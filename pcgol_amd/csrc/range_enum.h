@@ -14,13 +14,7 @@
 
 namespace pcgx {
 
-// The reference's DistSq in float32 (mat/vec3.go:18-20,38-40): (dx * dx + dy * dy) + dz * dz with d = p - q, never
-// contracted (-ffp-contract=off on both sides)
-__host__ __device__ __forceinline__ float ref_dist_sq(const float px, const float py, const float pz, const float qx,
-                                                      const float qy, const float qz) {
-  const float dx = px - qx, dy = py - qy, dz = pz - qz;
-  return (dx * dx + dy * dy) + dz * dz;
-}
+// (ref_dist_sq, the reference's float32 DistSq, is pcgx_math.h's: the host programs of the tests compile it too)
 
 // Where a handle's neighbourhoods come from.  (An int template argument of the kernels: normals_kernel<kSrc>,
 // range_kernel<kSrc, kFill>.)

@@ -267,6 +267,30 @@ class KDTree {  // pc/storage/kdtree/kdtree.go:14-23
     r.ids.resize((size_t)m);
     return r;
   }
+  // Farthest-point sampling (extension: no reference parity; include/pcgx.h, pcgx_kdtree_fps): `count` of the tree's own
+  // points in pick order, each the one farthest (float32 DistSq to the nearest pick so far, ties to the smallest id)
+  // from those before it; start: the first pick, -1 for the smallest eligible id.  ids and distSq have min(count,
+  // eligible points) entries and are a prefix of what a larger count gives; distSq[0] is +inf; coverSq: the d the next
+  // pick would have had, -1 when no point is left; owner (id order, filled where withOwner): the nearest pick's id, the
+  // earlier pick among equal distances, -1 for a deleted or non-finite point.
+  struct FarthestResult {
+    std::vector<int64_t> ids, owner;
+    std::vector<float> distSq;
+    float coverSq = -1.0f;
+  };
+  FarthestResult FarthestPoints(int64_t count, int64_t start = -1, bool withOwner = false) const {
+    if (count < 0) throw Error(PCGX_E_INVALID, "count must be >= 0");
+    FarthestResult r;
+    r.ids.resize((size_t)count);
+    r.distSq.resize((size_t)count);
+    if (withOwner) r.owner.resize((size_t)Len());
+    int64_t m = 0;
+    check(pcgx_kdtree_fps(h_.get(), count, start, r.ids.data(), &m, r.distSq.data(), &r.coverSq,
+                          withOwner ? r.owner.data() : nullptr));
+    r.ids.resize((size_t)m);
+    r.distSq.resize((size_t)m);
+    return r;
+  }
   // ISS keypoints (extension: no reference parity; include/pcgx.h, pcgx_kdtree_iss_keypoints).  eigenvalues: of
   // Normals' covariance at salientRadius, ascending, {0, 0, 0} where Normals answers "degenerate"; saliency: the
   // smallest eigenvalue of a salient point, else 0; ids: LocalMaxima(nonMaxRadius, saliency).  All in id order.

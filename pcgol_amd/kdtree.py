@@ -399,6 +399,36 @@ class KDTree:
             L.ptr(int(d_owner)) if d_owner else None, L.ptr(int(d_n_left)) if d_n_left else None,
             L.ptr(stream) if stream else None))
 
+    # -- extension (no reference parity): farthest-point sampling, a target count of well-spread points in pick order
+    def FarthestPoints(self, count, Start=-1, Owner=False):
+        """count of the tree's own points, each the one farthest (float32 DistSq to the nearest pick so far, ties to the
+        smallest id) from those picked before it -> (ids int64 in pick order, dist_sq float32, cover_sq float32), or
+        with Owner=True (..., owner int64 (n,)).  The first pick is Start, or the smallest eligible id (-1); deleted
+        and non-finite points are never picked.  ids and dist_sq have min(count, eligible points) entries and are a
+        prefix of what any larger count gives; dist_sq[0] is +inf; cover_sq is the d the next pick would have had
+        (every eligible point lies within it of a pick), -1 when no point is left.  owner: the nearest pick's id, the
+        earlier pick among equal distances, -1 for a point that is not eligible (include/pcgx.h, pcgx_kdtree_fps)."""
+        n, count = self.Len(), int(count)
+        ids = np.empty(max(count, 0), np.int64)
+        dist = np.empty(max(count, 0), np.float32)
+        cover = np.empty(1, np.float32)
+        owner = np.empty(n, np.int64) if Owner else None
+        cnt = C.c_int64()
+        L.check(L.lib().pcgx_kdtree_fps(self._h, count, int(Start), L.ptr(ids), C.byref(cnt), L.ptr(dist), L.ptr(cover),
+                                        L.ptr(owner)))
+        out = (ids[:cnt.value], dist[:cnt.value], cover[0])
+        return out + (owner,) if Owner else out
+
+    def FarthestPointsDev(self, count, d_ids, d_n_ids, d_dist_sq=0, d_cover_sq=0, d_owner=0, Start=-1, stream=0):
+        """Device-resident FarthestPoints: raw device addresses (e.g. torch .data_ptr()); d_ids int32 [count] (the picks
+        in order, then -1), d_n_ids one int32, d_dist_sq float32 [count] (then -1), d_cover_sq one float32, d_owner
+        int32 [Len()].  Enqueued on `stream`, returns without waiting, reads nothing back."""
+        L.check(L.lib().pcgx_kdtree_fps_dev(
+            self._h, int(count), int(Start), L.ptr(int(d_ids)) if d_ids else None,
+            L.ptr(int(d_n_ids)) if d_n_ids else None, L.ptr(int(d_dist_sq)) if d_dist_sq else None,
+            L.ptr(int(d_cover_sq)) if d_cover_sq else None, L.ptr(int(d_owner)) if d_owner else None,
+            L.ptr(stream) if stream else None))
+
     # -- extension (no reference parity): boundary points, where a scanned surface ends
     def Boundary(self, radius, Normals, MinGap=16, MinNeighbors=1):
         """The points whose radius neighbours (DistSq < radius^2, Range's set) leave an angular gap of at least MinGap

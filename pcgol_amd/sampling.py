@@ -1,4 +1,6 @@
-"""Minimum-distance subsampling (extension: no reference counterpart; CloudCompare's "subsample by space", Poisson-disk
+"""Samplers that keep ORIGINAL records: MinDistance (a radius) and FarthestPoint (a target count, below).
+
+Minimum-distance subsampling (extension: no reference counterpart; CloudCompare's "subsample by space", Poisson-disk
 sampling) behind the filter.Filter shape (pc/filter/filter.go:7-9), in the option style of pc/filter/voxelgrid:
 MinDistance(radius, WithSeed(7)).Filter(pp).
 
@@ -51,3 +53,46 @@ class MinDistance:
 
 def New(radius, *opts):
     return MinDistance(radius, *opts)
+
+
+def WithStart(index):
+    """The first pick: an index among the finite records (-1: the first finite record)."""
+    def opt(o):
+        o.Start = int(index)
+    return opt
+
+
+class FarthestPoint:
+    """Farthest-point sampling to a target count (extension: no reference counterpart; PointNet++'s sampling layer,
+    Open3D's farthest_point_down_sample): FarthestPoint(4096, WithStart(0)).Filter(pp).  The output records are ORIGINAL
+    records, byte for byte, IN PICK ORDER -- each the finite point farthest (float32 DistSq to the nearest pick so far,
+    ties to the earlier record) from those before it -- so the first K records of the output are the output for count K.
+    Non-finite points are dropped.  The contract is include/pcgx.h's pcgx_fps_filter; KDTree.FarthestPoints is the same
+    selection over a tree, with the distances and the owner of every point."""
+
+    def __init__(self, count, *opts):
+        self.Count = int(count)
+        self.Start = -1
+        for o in opts:
+            o(self)
+
+    def Filter(self, pp):
+        """Returns a new PointCloud (header cloned, Width = M, Height = 1)."""
+        if not isinstance(pp, PointCloud):
+            pp = PointCloud.from_xyz(pp)
+        stride, off = pp.Stride(), pp.xyz_offset()
+        n = pp.Points
+        out = np.empty(max(n, 1) * stride, np.uint8)
+        m = C.c_int64()
+        L.check(L.lib().pcgx_fps_filter(L.ptr(pp.Data), n, stride, off, self.Count, self.Start, L.ptr(out), C.byref(m)))
+        h = pp.PointCloudHeader.Clone()
+        h.Width, h.Height = m.value, 1
+        return PointCloud(h, m.value, out[: m.value * stride].copy())
+
+    def FilterDev(self, d_data, n, stride, off, d_out, stream=0):
+        """Device-resident variant (raw device addresses; d_out >= n * stride bytes).  Returns M when the work on
+        `stream` is done."""
+        m = C.c_int64()
+        L.check(L.lib().pcgx_fps_filter_dev(L.ptr(int(d_data)), int(n), int(stride), int(off), self.Count, self.Start,
+                                            L.ptr(int(d_out)), C.byref(m), L.ptr(stream) if stream else None))
+        return m.value
