@@ -25,7 +25,8 @@ import (
 // GroupStats(ids, sizes) (include/pcgx.h, "group geometry"), and what they stand on, GroupHulls(ids, sizes)
 // (include/pcgx.h, "group footprints"), and minimum-distance subsampling, Thin(radius, seed, score) (include/pcgx.h,
 // "minimum-distance subsampling"), and farthest-point sampling to a target count, FarthestPoints(count, start)
-// (include/pcgx.h, "farthest-point sampling").
+// (include/pcgx.h, "farthest-point sampling"), and consistent normal orientation, OrientNormals(radius, normals, mode,
+// ref) (include/pcgx.h, "consistent normal orientation").
 type KDTree = pcgx.KDTree
 
 // KDTreeOption is kdtree.KDTreeOption (kdtree.go:31).

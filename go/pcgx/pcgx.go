@@ -563,6 +563,64 @@ func (k *KDTree) FarthestPoints(count int, start int64) (*FarthestResult, error)
 	return res, nil
 }
 
+// OrientMode says how (*KDTree).OrientNormals fixes the overall sign of a component: OrientKeep leaves its smallest id
+// as given, OrientDirection makes its topmost point along ref look along ref (Hoppe's rule), OrientViewpoint makes the
+// majority of its normals look towards ref.
+type OrientMode int32
+
+const (
+	OrientKeep      OrientMode = 0
+	OrientDirection OrientMode = 1
+	OrientViewpoint OrientMode = 2
+)
+
+// OrientedNormals is what (*KDTree).OrientNormals returns, everything in id order: the normals (3 floats per point, the
+// given bits with the signs inverted where Flipped), the flags, the smallest id of each point's component (-1 for a
+// point that takes no part: a deleted id, a non-finite point, a zero or non-finite normal), and the component count.
+type OrientedNormals struct {
+	Normals    []float32
+	Flipped    []uint8
+	Component  []int64
+	Components int64
+}
+
+// OrientNormals gives neighbouring normals (DistSq < radius^2, Range's set) the same side: the sign is carried along the
+// minimum spanning forest of the radius graph, its edges ordered by |n_i . n_j| descending, then the smaller ids
+// (extension: no reference parity; include/pcgx.h, pcgx_kdtree_orient_normals).  normals: 3 floats per point in id order.
+func (k *KDTree) OrientNormals(radius float32, normals []float32, mode OrientMode, ref [3]float32) (*OrientedNormals, error) {
+	runtime.LockOSThread() // the error text is thread-local on the C side: call and pcgx_last_error on one OS thread
+	defer runtime.UnlockOSThread()
+	defer runtime.KeepAlive(k) // the finalizer must not free the handle while a call is in flight
+	var ln C.int64_t
+	if err := status(C.pcgx_kdtree_len(k.t.h, &ln)); err != nil {
+		return nil, err
+	}
+	n := int(ln)
+	if len(normals) != 3*n {
+		return nil, errors.New("pcgx: one normal per point of the tree is required")
+	}
+	res := &OrientedNormals{Normals: make([]float32, 3*n), Flipped: make([]uint8, n), Component: make([]int64, n)}
+	var np, op *C.float
+	var fp *C.uint8_t
+	var cp *C.int64_t
+	if n > 0 {
+		np = (*C.float)(unsafe.Pointer(&normals[0]))
+		op = (*C.float)(unsafe.Pointer(&res.Normals[0]))
+		fp = (*C.uint8_t)(unsafe.Pointer(&res.Flipped[0]))
+		cp = (*C.int64_t)(unsafe.Pointer(&res.Component[0]))
+	}
+	var nc, open C.int64_t
+	rc := C.pcgx_kdtree_orient_normals(k.t.h, C.float(radius), np, C.int32_t(mode), (*C.float)(unsafe.Pointer(&ref[0])), op,
+		fp, cp, &nc, &open)
+	runtime.KeepAlive(normals)
+	runtime.KeepAlive(res)
+	if err := status(rc); err != nil {
+		return nil, err
+	}
+	res.Components = int64(nc)
+	return res, nil
+}
+
 // BoundaryPoints is what (*KDTree).Boundary returns: the boundary points' ids ascending, and per point in id order the
 // longest cyclic run of empty sectors (64 for an empty mask, -1 where the point is not evaluated), the mask of the
 // sectors a neighbour falls in, and the neighbourhood's size.

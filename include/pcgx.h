@@ -1999,6 +1999,78 @@ PCGX_API pcgx_status pcgx_fps_filter(const void *data, int64_t n, int32_t stride
 PCGX_API pcgx_status pcgx_fps_filter_dev(const void *d_data, int64_t n, int32_t stride, int32_t xyz_off, int64_t count,
                                          int64_t start, void *d_out, int64_t *out_n, void *stream);
 
+/* ------------------------------------------- consistent normal orientation (extension: no reference parity)
+ * NOT in the reference.  Hoppe et al. 1992; Open3D's orient_normals_consistent_tangent_plane; CloudCompare's "orient
+ * normals with a minimum spanning tree".  pcgx_kdtree_normals turns every normal towards one viewpoint, which is right
+ * for one scan from one pose and wrong for a merged map, a downsampled cloud or a closed object.  This call gives
+ * neighbouring normals the same side instead: it propagates a sign along the minimum spanning forest of the radius graph,
+ * whose edges are cheapest where two normals are most nearly parallel.  Over the tree's own points only; every array is in
+ * id order over Len(), deleted ids included (the q == NULL convention).  This comment is the contract,
+ * tests/orient_oracle.py restates it, csrc/orient_terms.h holds its expressions.
+ * Neighbourhood N(i): the set pcgx_kdtree_range_count counts on that handle, float32 DistSq < radius * radius, STRICT.
+ * Usable point: "clusters"' rule with normals given: i is in N(i) (not deleted, x, y, z finite, a bound above 0), and
+ *   the three components of its normal are finite and not all zero.  Normals are taken as given, not normalised.
+ * Edge {i, j}, i != j: both usable and j in N(i) (DistSq is symmetric bit for bit).  Its agreement is
+ *   c = (nx_i nx_j + ny_i ny_j) + nz_i nz_j in float64 from the float32 components, the products exact, the two additions
+ *   rounded in this order, nothing contracted ("clusters"' expression); its sign is s = (c < 0).
+ * Edge order, strict and total: e comes before f iff |c_e| > |c_f|, or they are equal and min(i, j) is smaller, or those
+ *   are equal too and max(i, j) is smaller.  (Hoppe's weight 1 - |c|, the ties made explicit.)
+ * Forest after R rounds: F_0 has no edges.  In a round every component of F_R that has an edge leaving it takes the
+ *   first such edge in the edge order; all taken edges are added at once.  Under a strict order that makes no cycle, and
+ *   F_inf is the minimum spanning forest, which is unique.  The components with a leaving edge at least halve each round:
+ *   pcgx_orient_full_rounds(Len()) = max(1, ceil(log2 Len())) rounds always suffice.
+ * Parity pi_i: the XOR of s along the forest's path from i to the smallest member id of its component.
+ * Component sign sigma, by mode:
+ *   0  sigma = 0: the smallest-id member keeps its given sign.  ref is not read.
+ *   1  ref = a direction u.  The anchor is the member with the largest float32 h = (px ux + py uy) + pz uz, never
+ *      contracted, compared after h + 0 (so -0 ties with +0; a NaN from an overflow is ordered by its bits), ties to the
+ *      smallest id.  sigma = 1 iff the anchor's normal after pi, dotted with u the way c is formed, is < 0.  (Hoppe's
+ *      rule: the topmost point looks up.)
+ *   2  ref = a viewpoint v.  Member i votes "wrong" when t_i < 0 and "right" when t_i > 0, t_i = (n'x ex + n'y ey) +
+ *      n'z ez in float64, e = (double)v - (double)p_i, n' the normal after pi; t_i == 0 (or NaN) abstains.  sigma = 1 iff
+ *      wrong > right.
+ * Outputs: flipped[i] = pi_i ^ sigma, 0 for an unusable point.  normals_out[3 i ..] = the given normal with the sign bit
+ *   of all three components inverted where flipped[i], else the given bits (an unusable point's too); normals_out ==
+ *   normals is allowed.  component[i] (may be NULL) = the smallest member id of i's component, -1 for an unusable point.
+ *   *n_components = the components.  *n_open = the components that still had a leaving edge after the last round run: 0
+ *   means the result is final.  Either of normals_out and flipped may be NULL, not both.
+ * The host form always finishes.  The device form enqueues max_rounds rounds, 0 meaning pcgx_orient_full_rounds(Len());
+ *   a round reads the number of still-active points from a device word and costs almost nothing once it is zero; nothing
+ *   is read back.  With max_rounds = R too small every output is this contract applied to F_R, and *n_open > 0.
+ * The same input gives the same bits on every call and on every kind of handle (grid, PCGX_RANGE_WALK=1, after
+ *   DeletePoint): the forest is a property of the point set, not of a schedule.
+ * A handle that holds a NaN coordinate: its tree is out of order, N is whatever Range gives on it, and j in N(i) need not
+ *   mean i in N(j).  There "i in N(i)" is looked up, not assumed, and a component takes the first among the leaving edges
+ *   {i, j} one of ITS members i sees (j in N(i)) and the edges other components took into it in that round; with
+ *   symmetric neighbourhoods that is the rule above.  Still a property of the handle, the same bits on every call.
+ * PCGX_E_INVALID, nothing written: a NULL tree; a radius that is not finite and > 0; a mode outside 0..2; in mode 1 or 2
+ *   a NULL ref or one with a non-finite component; max_rounds < 0; NULL n_components or n_open; with Len() > 0, NULL
+ *   normals, or NULL normals_out and flipped.  Len() == 0: PCGX_OK, the two counts are written (0), nothing else.
+ * Always computed on the device (csrc/orient.hip).  Temporaries: 83 bytes per point. */
+PCGX_API pcgx_status pcgx_kdtree_orient_normals(const pcgx_kdtree *t, float radius, const float *normals /* [3 Len()] */,
+                                                int32_t mode, const float *ref /* [3]; mode 0: may be NULL */,
+                                                float *normals_out /* [3 Len()] */, uint8_t *flipped /* [Len()] */,
+                                                int64_t *component /* [Len()], may be NULL */, int64_t *n_components,
+                                                int64_t *n_open);
+/* Same, every array device resident (component and the counts are int32 there; ref stays host memory), enqueued on
+ * `stream` (NULL: the library's); returns without waiting, reads nothing back. */
+PCGX_API pcgx_status pcgx_kdtree_orient_normals_dev(const pcgx_kdtree *t, float radius, const float *d_normals, int32_t mode,
+                                                    const float *ref, int32_t max_rounds, float *d_normals_out,
+                                                    uint8_t *d_flipped, int32_t *d_component /* may be NULL */,
+                                                    int32_t *d_n_components, int32_t *d_n_open, void *stream);
+/* Rounds that finish a call over n points for certain: max(1, ceil(log2 n)); 0 for n <= 0. */
+PCGX_API int32_t pcgx_orient_full_rounds(int64_t n);
+/* Measurement hooks (tools/orient_probe.py).  The device form without `component`, and d_active (device, uint32
+ * [rounds + 1], may be NULL) = the points still in the active list before each enqueued round and after the last.
+ * pcgx_orient_active_list: 0 where the library was built with -DPCGX_ORIENT_ACTIVE_LIST=0 (every point stays in the list:
+ * the same results, for comparison), else 1. */
+PCGX_API pcgx_status pcgx_kdtree_orient_normals_probe_dev(const pcgx_kdtree *t, float radius, const float *d_normals,
+                                                          int32_t mode, const float *ref, int32_t max_rounds,
+                                                          float *d_normals_out, uint8_t *d_flipped,
+                                                          int32_t *d_n_components, int32_t *d_n_open, uint32_t *d_active,
+                                                          void *stream);
+PCGX_API int32_t pcgx_orient_active_list(void);
+
 /* ------------------------------------------- Normal Distributions Transform (extension: no reference parity)
  * NOT in the reference: pcgol has nothing like it.  NDT registration (Biber and Strasser 2003; Magnusson 2009; PCL's
  * NormalDistributionsTransform) as a fourth Fit beside point-to-point, point-to-plane and Generalized ICP.  It needs

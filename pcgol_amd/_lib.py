@@ -335,6 +335,11 @@ SIGNATURES = {
     "pcgx_fps_plan": (_i32, [_i64, _i64, _vp]),
     "pcgx_fps_filter": (_i32, [_vp, _i64, _i32, _i32, _i64, _i64, _vp, C.POINTER(_i64)]),
     "pcgx_fps_filter_dev": (_i32, [_vp, _i64, _i32, _i32, _i64, _i64, _vp, C.POINTER(_i64), _vp]),
+    "pcgx_kdtree_orient_normals": (_i32, [_vp, _f32, _vp, _i32, _vp, _vp, _vp, _vp, C.POINTER(_i64), C.POINTER(_i64)]),
+    "pcgx_kdtree_orient_normals_dev": (_i32, [_vp, _f32, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "pcgx_orient_full_rounds": (_i32, [_i64]),
+    "pcgx_kdtree_orient_normals_probe_dev": (_i32, [_vp, _f32, _vp, _i32, _vp, _i32, _vp, _vp, _vp, _vp, _vp, _vp]),
+    "pcgx_orient_active_list": (_i32, []),
     "pcgx_ndt_map_create": (_i32, [_vp, _vp, _i64, _i32, _i32, _i32, _i32, _f32, C.POINTER(_vp)]),
     "pcgx_ndt_map_free": (_i32, [_vp]),
     "pcgx_ndt_map_counts": (_i32, [_vp, C.POINTER(_i64), C.POINTER(_i64)]),

@@ -135,3 +135,43 @@ class BoundaryEstimation:
         kept = sub_labels >= 0
         labels[ids[kept]] = sub_labels[kept]
         return labels, sizes, ids[sub_ids]  # (ids ascends, so a group's members stay ascending)
+
+
+# ------------------------------------------------------------------------------------------ consistent orientation
+# (extension: no reference counterpart; include/pcgx.h, "consistent normal orientation")
+
+def WithDirection(u):
+    """NormalOrientation option: every component's topmost point along u looks along u (Hoppe's rule)"""
+    return ("direction", tuple(float(v) for v in np.asarray(u, np.float32).reshape(3)))
+
+
+def WithViewpoint(v):
+    """NormalOrientation option: the majority of every component's normals looks towards v"""
+    return ("viewpoint", tuple(float(w) for w in np.asarray(v, np.float32).reshape(3)))
+
+
+class NormalOrientation:
+    """KDTree.OrientNormals as an estimator beside BoundaryEstimation: neighbouring normals get the same side, the sign
+    carried along the minimum spanning forest of the radius graph (Hoppe et al. 1992; Open3D's
+    orient_normals_consistent_tangent_plane).  Without an option the smallest id of a component keeps its sign."""
+
+    def __init__(self, radius, *options):
+        self._radius = float(radius)
+        self._direction = self._viewpoint = None
+        for kind, value in options:
+            if kind == "direction":
+                self._direction = value
+            elif kind == "viewpoint":
+                self._viewpoint = value
+            else:
+                raise ValueError("unknown option %r" % (kind,))
+        if self._direction is not None and self._viewpoint is not None:
+            raise ValueError("WithDirection or WithViewpoint, not both")
+        self.flipped = self.component = self.n_components = None
+
+    def Compute(self, tree, normals):
+        """-> the oriented normals float32 (n,3); .flipped uint8 (n,), .component int64 (n,) and .n_components keep the
+        rest of what KDTree.OrientNormals returned"""
+        out, self.flipped, self.n_components, self.component = tree.OrientNormals(
+            self._radius, normals, Direction=self._direction, Viewpoint=self._viewpoint, Component=True)
+        return out

@@ -336,6 +336,33 @@ class KDTree {  // pc/storage/kdtree/kdtree.go:14-23
     r.ids.resize((size_t)m);
     return r;
   }
+  // Consistent normal orientation (extension: no reference parity; include/pcgx.h, pcgx_kdtree_orient_normals):
+  // neighbouring normals (one per point in id order) get the same side, the sign carried along the minimum spanning
+  // forest of the radius graph.  A component's overall sign: its smallest id keeps its own (OrientKeep); its topmost
+  // point along ref looks along ref (OrientDirection); the majority of its normals looks towards ref (OrientViewpoint).
+  // normals: the given bits, the signs inverted where flipped; component: the smallest id of the point's component, -1
+  // for a point that takes no part.
+  enum OrientMode : int32_t { OrientKeep = 0, OrientDirection = 1, OrientViewpoint = 2 };
+  struct OrientResult {
+    std::vector<Vec3> normals;
+    std::vector<uint8_t> flipped;
+    std::vector<int64_t> component;
+    int64_t components = 0;
+  };
+  OrientResult OrientNormals(float radius, const std::vector<Vec3> &normals, OrientMode mode = OrientKeep,
+                             const Vec3 &ref = Vec3{{0.0f, 0.0f, 0.0f}}) const {
+    const int64_t n = Len();
+    if ((int64_t)normals.size() != n) throw Error(PCGX_E_INVALID, "one normal per point of the tree is required");
+    OrientResult r;
+    r.normals.resize((size_t)n);
+    r.flipped.resize((size_t)n);
+    r.component.resize((size_t)n);
+    int64_t open = 0;
+    check(pcgx_kdtree_orient_normals(h_.get(), radius, n ? normals[0].data() : nullptr, (int32_t)mode, ref.data(),
+                                     n ? r.normals[0].data() : nullptr, r.flipped.data(), r.component.data(),
+                                     &r.components, &open));
+    return r;
+  }
   // Ray queries (extension: no reference parity; include/pcgx.h, pcgx_kdtree_raycast / _ray_pierce): ray j is
   // origins[j] + s directions[j], s in [sMin[j], sMax[j]] (an empty vector: 0 and +inf); directions are not normalised.
   // RayCast: per ray the first of the tree's points within `radius` of the ray's line -- ids (-1: none), along =

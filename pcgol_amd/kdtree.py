@@ -461,6 +461,50 @@ class KDTree:
             self._h, float(radius), L.ptr(int(d_normals)), int(MinGap), int(MinNeighbors), L.ptr(int(d_ids)),
             L.ptr(int(d_n_ids)), opt(d_gaps), opt(d_masks), opt(d_counts), L.ptr(stream) if stream else None))
 
+    # -- extension (no reference parity): consistent normal orientation along the radius graph's minimum spanning forest
+    def OrientNormals(self, radius, Normals, Direction=None, Viewpoint=None, Component=False):
+        """Normals (n,3) float32 in id order with their signs made consistent between neighbours (DistSq < radius^2,
+        Range's set): the sign is propagated along the minimum spanning forest of the radius graph, edges ordered by
+        |n_i . n_j| descending, then the smaller ids -> (normals float32 (n,3), flipped uint8 (n,), n_components), or
+        with Component=True (..., component int64 (n,)): the smallest id of each point's component, -1 for a point
+        that takes no part (deleted, non-finite, a zero or non-finite normal; its normal comes back as given).  A
+        component's overall sign: its smallest id keeps its own (default); Direction=u: its topmost point along u looks
+        along u (Hoppe's rule); Viewpoint=v: the majority of its normals looks towards v (include/pcgx.h,
+        pcgx_kdtree_orient_normals)."""
+        n = self.Len()
+        nrm = L.f32c(Normals).reshape(-1, 3)
+        if len(nrm) != n:
+            raise ValueError("one normal per point of the tree is required")
+        if Direction is not None and Viewpoint is not None:
+            raise ValueError("Direction or Viewpoint, not both")
+        mode = 1 if Direction is not None else 2 if Viewpoint is not None else 0
+        ref = L.f32c(Direction if mode == 1 else Viewpoint).reshape(3) if mode else None
+        out = np.empty((n, 3), np.float32)
+        flipped = np.empty(n, np.uint8)
+        comp = np.empty(n, np.int64) if Component else None
+        nc, no = C.c_int64(), C.c_int64()
+        L.check(L.lib().pcgx_kdtree_orient_normals(self._h, float(radius), L.ptr(nrm), mode, L.ptr(ref), L.ptr(out),
+                                                   L.ptr(flipped), L.ptr(comp), C.byref(nc), C.byref(no)))
+        res = (out, flipped, nc.value)
+        return res + (comp,) if Component else res
+
+    def OrientNormalsDev(self, radius, d_normals, d_normals_out, d_flipped, d_n_components, d_n_open, d_component=0,
+                         Direction=None, Viewpoint=None, MaxRounds=0, stream=0):
+        """Device-resident OrientNormals: raw device addresses (e.g. torch .data_ptr()); d_normals float32 [3 Len()]
+        (what NormalsDev wrote on the same stream), d_normals_out float32 [3 Len()] (may be d_normals; or 0),
+        d_flipped uint8 [Len()] (or 0, not both), d_component int32 [Len()] (optional), d_n_components and d_n_open one
+        int32 each.  MaxRounds rounds are enqueued (0: enough to finish for certain); *d_n_open > 0 afterwards means the
+        forest is that of MaxRounds rounds, not yet spanning.  Direction / Viewpoint are host values.  Enqueued on
+        `stream`, returns without waiting, reads nothing back."""
+        if Direction is not None and Viewpoint is not None:
+            raise ValueError("Direction or Viewpoint, not both")
+        mode = 1 if Direction is not None else 2 if Viewpoint is not None else 0
+        ref = L.f32c(Direction if mode == 1 else Viewpoint).reshape(3) if mode else None
+        opt = lambda a: L.ptr(int(a)) if a else None  # noqa: E731
+        L.check(L.lib().pcgx_kdtree_orient_normals_dev(
+            self._h, float(radius), opt(d_normals), mode, L.ptr(ref), int(MaxRounds), opt(d_normals_out), opt(d_flipped),
+            opt(d_component), opt(d_n_components), opt(d_n_open), L.ptr(stream) if stream else None))
+
     # -- extension (no reference parity): ray queries, the points inside a thin tube around each ray
     @staticmethod
     def _rays(origins, directions, s_min, s_max):
