@@ -750,6 +750,84 @@ func (k *KDTree) RayPierce(origins, directions []mat.Vec3, radius float32, sMin,
 	return counts, nil
 }
 
+// CylinderStats is what (*KDTree).CylinderStats returns, per cylinder: the number of the tree's live points in it and,
+// at Sums[2j] and Sums[2j+1], S1 = the sum of a and S2 = the sum of a a, a = (p - core) . axis in float64,
+// unnormalised.
+type CylinderStats struct {
+	Counts []int32
+	Sums   []float64
+}
+
+// CylinderStats returns the statistics of the cylinders with cores[j], axes[j] (not normalised), radius and halfLength
+// each way along the axis, over the tree's live points: what M3C2Finish turns into distances (extension: no reference
+// parity; include/pcgx.h, pcgx_kdtree_cylinder_stats).
+func (k *KDTree) CylinderStats(cores, axes []mat.Vec3, radius, halfLength float32) (*CylinderStats, error) {
+	runtime.LockOSThread() // the error text is thread-local on the C side: call and pcgx_last_error on one OS thread
+	defer runtime.UnlockOSThread()
+	defer runtime.KeepAlive(k) // the finalizer must not free the handle while a call is in flight
+	m := len(cores)
+	if len(axes) != m {
+		return nil, errors.New("pcgx: one axis per core is required")
+	}
+	res := &CylinderStats{Counts: make([]int32, m), Sums: make([]float64, 2*m)}
+	if m == 0 {
+		return res, nil
+	}
+	rc := C.pcgx_kdtree_cylinder_stats(k.t.h, (*C.float)(unsafe.Pointer(&cores[0])), (*C.float)(unsafe.Pointer(&axes[0])),
+		C.int64_t(m), C.float(radius), C.float(halfLength), (*C.int32_t)(unsafe.Pointer(&res.Counts[0])),
+		(*C.double)(unsafe.Pointer(&res.Sums[0])))
+	runtime.KeepAlive(cores)
+	runtime.KeepAlive(axes)
+	runtime.KeepAlive(res)
+	if err := status(rc); err != nil {
+		return nil, err
+	}
+	return res, nil
+}
+
+// M3C2Result is what M3C2Finish returns, per core: the signed distance along the axis, epoch 2 minus epoch 1, the level
+// of detection at 95 % and whether |Distance| exceeds it (NaN, NaN, false where a cylinder held too few points or the
+// axis is unusable).
+type M3C2Result struct {
+	Distance    []float64
+	LoD         []float64
+	Significant []bool
+}
+
+// M3C2Finish is M3C2's finish (Lague, Brodu and Leroux 2013) on the cylinder statistics of two epochs, taken with the
+// same cores, axes, radius and half length against each epoch's tree (extension: no reference parity; include/pcgx.h,
+// pcgx_m3c2_finish).
+func M3C2Finish(axes []mat.Vec3, epoch1, epoch2 *CylinderStats, registrationError float64, minCount int32) (*M3C2Result, error) {
+	runtime.LockOSThread() // the error text is thread-local on the C side: call and pcgx_last_error on one OS thread
+	defer runtime.UnlockOSThread()
+	m := len(axes)
+	if epoch1 == nil || epoch2 == nil || len(epoch1.Counts) != m || len(epoch2.Counts) != m || len(epoch1.Sums) != 2*m ||
+		len(epoch2.Sums) != 2*m {
+		return nil, errors.New("pcgx: one count and two sums per axis and epoch are required")
+	}
+	res := &M3C2Result{Distance: make([]float64, m), LoD: make([]float64, m), Significant: make([]bool, m)}
+	if m == 0 {
+		return res, nil
+	}
+	sig := make([]uint8, m)
+	rc := C.pcgx_m3c2_finish((*C.float)(unsafe.Pointer(&axes[0])), (*C.int32_t)(unsafe.Pointer(&epoch1.Counts[0])),
+		(*C.double)(unsafe.Pointer(&epoch1.Sums[0])), (*C.int32_t)(unsafe.Pointer(&epoch2.Counts[0])),
+		(*C.double)(unsafe.Pointer(&epoch2.Sums[0])), C.int64_t(m), C.double(registrationError), C.int32_t(minCount),
+		(*C.double)(unsafe.Pointer(&res.Distance[0])), (*C.double)(unsafe.Pointer(&res.LoD[0])),
+		(*C.uint8_t)(unsafe.Pointer(&sig[0])))
+	runtime.KeepAlive(axes)
+	runtime.KeepAlive(epoch1)
+	runtime.KeepAlive(epoch2)
+	runtime.KeepAlive(res)
+	if err := status(rc); err != nil {
+		return nil, err
+	}
+	for i, v := range sig {
+		res.Significant[i] = v != 0
+	}
+	return res, nil
+}
+
 // ISSKeypoints returns the ISS keypoints of the tree's points (Zhong 2009, Open3D's form; extension: no reference
 // parity; include/pcgx.h, pcgx_kdtree_iss_keypoints): ids ascending, and per point in id order the eigenvalues of
 // Normals' covariance at salientRadius (ascending, zero where Normals answers "degenerate") and the saliency (the

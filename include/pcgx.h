@@ -1657,6 +1657,73 @@ PCGX_API pcgx_status pcgx_kdtree_ray_pierce_dev(const pcgx_kdtree *t, const floa
                                                 const float *d_s_min, const float *d_s_max, int64_t nr, float radius,
                                                 int32_t *d_counts, void *stream);
 
+/* ------------------------------------------- cylinder statistics (extension: no reference parity)
+ * NOT in the reference.  What moved between two registered epochs, and by how much: M3C2 (Lague, Brodu and Leroux
+ * 2013) takes, for a core point with a normal, the points of each epoch inside a cylinder along the normal and compares
+ * their mean positions along it.  The primitive: for a batch of cylinders over one tree, how many of the tree's points
+ * lie in each and the sums of their positions along the axis and of the squares.  This comment is the contract,
+ * tests/m3c2_oracle.py restates it.
+ * A cylinder: a core o, an axis d (NOT normalised: any finite non-zero vector), a radius and a half length L, the last
+ *   two the same for the whole batch.  cores and axes are [3 m] float32.
+ * Member: all float64 from the float32 inputs widened, fixed order, each product rounded once, nothing fused, no square
+ *   root and no division.  w, a, dd, cc and rr are the ray queries' expressions above, with o the core and d the axis;
+ *   ll = half_length half_length.  A live tree point p with three finite coordinates is a member iff cc <= rr dd and
+ *   a a <= ll dd: the side surface and both end caps belong to the cylinder, and its metric size does not depend on |d|.
+ *   A deleted point is in no cylinder.  A cylinder is unusable, and has no members, if o or d has a non-finite component
+ *   or dd == 0.
+ * counts[m] int32: the number of members.  A property of the point set: the same on every kind of handle (grid,
+ *   PCGX_RANGE_WALK=1, after DeletePoint) and on every call.
+ * sums[2 m] float64: sums[2 i] = S1 = the sum of a over cylinder i's members, sums[2 i + 1] = S2 = the sum of a a.
+ *   Every term has its contract bits.  The order of the additions is the library's: the same handle, arguments and
+ *   build give the same bits on every call (lanes in the order of the visit, shuffles in a fixed tree, no floating-point
+ *   atomics); across handles, or against the exact sum, a value differs by at most n 2^-53 times the sum of the terms'
+ *   magnitudes, n the count -- the bound of any summation order while n n < 2^53, derived, not measured.
+ *   The sums are UNNORMALISED: the caller derives the metric mean S1 / n / sqrt(dd) and the metric variance, the sample
+ *   variance of a over dd (pcgx_m3c2_finish does both).  An unusable cylinder writes 0, 0, 0.
+ * PCGX_E_INVALID: a NULL tree; a radius or half_length that is not finite and > 0; m < 0 (or above 2^31 - 16); a NULL
+ *   array with m > 0; a tree whose finite points span 2^62 or more along an axis (csrc/ray_terms.h).  m == 0 is
+ *   PCGX_OK.  A tree with no live point gives zeros.
+ * Always computed on the device (csrc/m3c2.hip), in one launch: the enumeration of the ray queries -- the axis' range
+ *   [-L, L], clipped to the box of the tree's finite points, cut into slabs of about 2 radius (no shorter than a grid
+ *   cell), each one ball query whose candidates the float64 member test filters (csrc/m3c2_terms.h hands
+ *   csrc/ray_terms.h a range that holds every member, so its cover proof applies) -- with 8, 16 or 64 lanes per
+ *   cylinder, the fewest that hold the slabs 2 L / max(2 radius, cell) can make.  No temporaries.  A tree with a NaN or
+ *   infinite coordinate among its points is answered by a wave per cylinder over all points, from a copy of the
+ *   handle's points uploaded in the call (12 Len() bytes, Len() more after DeletePoint). */
+PCGX_API pcgx_status pcgx_kdtree_cylinder_stats(const pcgx_kdtree *t, const float *cores /* [3 m] */,
+                                                const float *axes /* [3 m] */, int64_t m, float radius,
+                                                float half_length, int32_t *counts /* [m] */, double *sums /* [2 m] */);
+/* Same, every array device resident, enqueued on `stream` (NULL: the library's); returns without waiting, reads
+ * nothing back. */
+PCGX_API pcgx_status pcgx_kdtree_cylinder_stats_dev(const pcgx_kdtree *t, const float *d_cores, const float *d_axes,
+                                                    int64_t m, float radius, float half_length, int32_t *d_counts,
+                                                    double *d_sums, void *stream);
+
+/* ------------------------------------------- M3C2 (extension: no reference parity)
+ * NOT in the reference.  The finish of M3C2 on the cylinder statistics of two epochs (the same cores, axes, radius and
+ * half length against the tree of each): per core the signed distance along the normal, the level of detection at 95 %
+ * and whether the change is significant.  tests/m3c2_oracle.py restates it.
+ * All float64 in the written order, division and square root IEEE (so the device's values equal a NumPy restatement's
+ *   bit for bit, given the sums): dd from the axis as above; for epoch c, n = counts_c[i], S1 = sums_c[2 i],
+ *   S2 = sums_c[2 i + 1]:  mean_c = S1 / n;  v = (S2 - (S1 S1) / n) / (n - 1);  var_c = (v > 0 ? v : 0) / dd.
+ *   distance = (mean_2 - mean_1) / sqrt(dd);  lod = 1.96 (sqrt(var_1 / n_1 + var_2 / n_2) + registration_error);
+ *   significant = |distance| > lod.
+ * A core with counts_1 < min_count or counts_2 < min_count, or with an unusable axis (a non-finite component, dd == 0),
+ *   gets distance = lod = NaN and significant = 0.
+ * PCGX_E_INVALID: m < 0 (or above 2^31 - 1); registration_error not >= 0; min_count < 2; a NULL array with m > 0.
+ *   m == 0 is PCGX_OK.  Left out: median / IQR statistics, multi-scale normals, a radius per core, the members' ids. */
+PCGX_API pcgx_status pcgx_m3c2_finish(const float *axes /* [3 m] */, const int32_t *counts1 /* [m] */,
+                                      const double *sums1 /* [2 m] */, const int32_t *counts2 /* [m] */,
+                                      const double *sums2 /* [2 m] */, int64_t m, double registration_error,
+                                      int32_t min_count, double *distance /* [m] */, double *lod /* [m] */,
+                                      uint8_t *significant /* [m] */);
+/* Same, every array device resident, enqueued on `stream` (NULL: the library's); returns without waiting.  The inputs
+ * can be what two pcgx_kdtree_cylinder_stats_dev calls wrote on the same stream. */
+PCGX_API pcgx_status pcgx_m3c2_finish_dev(const float *d_axes, const int32_t *d_counts1, const double *d_sums1,
+                                          const int32_t *d_counts2, const double *d_sums2, int64_t m,
+                                          double registration_error, int32_t min_count, double *d_distance,
+                                          double *d_lod, uint8_t *d_significant, void *stream);
+
 /* ------------------------------------------- score poses (extension: no reference parity)
  * NOT in the reference.  pcgx_pose_from_correspondences picks its pose by the inliers among the CORRESPONDENCES; on a
  * scene with repeated structure a wrong pose can collect more of them than the right one.  This call counts, for each of

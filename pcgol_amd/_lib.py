@@ -305,6 +305,10 @@ SIGNATURES = {
     "pcgx_kdtree_raycast_dev": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _f32, _vp, _vp, _vp, _vp]),
     "pcgx_kdtree_ray_pierce": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _f32, _vp]),
     "pcgx_kdtree_ray_pierce_dev": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, _f32, _vp, _vp]),
+    "pcgx_kdtree_cylinder_stats": (_i32, [_vp, _vp, _vp, _i64, _f32, _f32, _vp, _vp]),
+    "pcgx_kdtree_cylinder_stats_dev": (_i32, [_vp, _vp, _vp, _i64, _f32, _f32, _vp, _vp, _vp]),
+    "pcgx_m3c2_finish": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, C.c_double, _i32, _vp, _vp, _vp]),
+    "pcgx_m3c2_finish_dev": (_i32, [_vp, _vp, _vp, _vp, _vp, _i64, C.c_double, _i32, _vp, _vp, _vp, _vp]),
     "pcgx_kdtree_score_poses": (_i32, [_vp, _vp, _i64, _vp, _i64, _f32, _vp, _vp, C.POINTER(_i64), _vp]),
     "pcgx_kdtree_score_poses_dev": (_i32, [_vp, _vp, _i64, _vp, _i64, _f32, _vp, _vp, _vp, _vp]),
     "pcgx_score_tile": (_i32, []),

@@ -12,7 +12,7 @@ import sys
 HERE = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(HERE, "csrc")
 SO = os.path.join(HERE, "libpcgx.so")
-SOURCES = ["core.hip", "knn.hip", "knn_explicit.hip", "knn_grid.hip", "sort.hip", "icp.hip", "icp_small.hip", "strict.hip", "strict_check.hip", "comm.hip", "voxel.hip", "voxel_bucket.hip", "range.hip", "segment.hip", "sac.hip", "normals.hip", "mls.hip", "ndt.hip", "fpfh.hip", "fpfh_match.hip", "keypoints.hip", "cluster.hip", "dbscan.hip", "group_stats.hip", "group_hull.hip", "pose.hip", "pose_score.hip", "planes.hip", "shapes.hip", "ground.hip", "boundary.hip", "rays.hip", "thin.hip", "fps.hip", "orient.hip", "knearest.hip", "sor.hip", "pcd.hip", "kdtree_build_gpu.hip", "kdtree_build.cpp"]
+SOURCES = ["core.hip", "knn.hip", "knn_explicit.hip", "knn_grid.hip", "sort.hip", "icp.hip", "icp_small.hip", "strict.hip", "strict_check.hip", "comm.hip", "voxel.hip", "voxel_bucket.hip", "range.hip", "segment.hip", "sac.hip", "normals.hip", "mls.hip", "ndt.hip", "fpfh.hip", "fpfh_match.hip", "keypoints.hip", "cluster.hip", "dbscan.hip", "group_stats.hip", "group_hull.hip", "pose.hip", "pose_score.hip", "planes.hip", "shapes.hip", "ground.hip", "boundary.hip", "rays.hip", "m3c2.hip", "thin.hip", "fps.hip", "orient.hip", "knearest.hip", "sor.hip", "pcd.hip", "kdtree_build_gpu.hip", "kdtree_build.cpp"]
 # every header beside the sources, whoever includes it (round 5's wg_stamps.h was missing from a hand-kept list: an
 # edit there changed kernels without changing source_hash), and the public header
 HEADERS = sorted(f for f in os.listdir(CSRC) if f.endswith(".h")) + [os.path.join("..", "..", "include", "pcgx.h")]

@@ -168,7 +168,8 @@ void ray_launch(const pcgx_kdtree *t, const TreeView &tv, const XTreeView &xv, c
 }
 
 // The box of the handle's finite points (deleted ones too: the box may only be too wide), made once per handle.
-static RayBox ray_box(const pcgx_kdtree *tc) {
+// (m3c2.hip's cylinders clip to it too.)
+RayBox ray_box(const pcgx_kdtree *tc) {
   pcgx_kdtree *t = const_cast<pcgx_kdtree *>(tc);
   std::lock_guard<std::mutex> lock(t->mu);
   if (t->ray_box_state == 0) {

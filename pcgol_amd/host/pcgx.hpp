@@ -393,6 +393,25 @@ class KDTree {  // pc/storage/kdtree/kdtree.go:14-23
                                  radius, counts.data()));
     return counts;
   }
+  // Cylinder statistics (extension: no reference parity; include/pcgx.h, pcgx_kdtree_cylinder_stats): cylinder j has
+  // the core cores[j], the axis axes[j] (not normalised), `radius` and `halfLength` each way along the axis.  counts:
+  // the tree's live points in it; sums: S1 = sum of a and S2 = sum of a a at [2 j] and [2 j + 1], a = (p - core) . axis
+  // in float64, unnormalised.  M3C2Finish (below the class) turns the statistics of two epochs into distances.
+  struct CylinderStatsResult {
+    std::vector<int32_t> counts;
+    std::vector<double> sums;
+  };
+  CylinderStatsResult CylinderStats(const std::vector<Vec3> &cores, const std::vector<Vec3> &axes, float radius,
+                                    float halfLength) const {
+    const size_t m = cores.size();
+    if (axes.size() != m) throw Error(PCGX_E_INVALID, "one axis per core is required");
+    CylinderStatsResult r;
+    r.counts.resize(m);
+    r.sums.resize(2 * m);
+    check(pcgx_kdtree_cylinder_stats(h_.get(), m ? cores[0].data() : nullptr, m ? axes[0].data() : nullptr, (int64_t)m,
+                                     radius, halfLength, r.counts.data(), r.sums.data()));
+    return r;
+  }
   // Cluster extraction (extension: no reference parity; include/pcgx.h, pcgx_kdtree_clusters): the connected
   // components of the radius graph over the tree's own points, kept when max(minSize, 1) <= size (<= maxSize unless 0),
   // largest first, equal sizes by smallest id.  normals (empty: none): an edge also needs |n_i . n_j| >= minCos
@@ -682,6 +701,30 @@ class KDTree {  // pc/storage/kdtree/kdtree.go:14-23
   }
   std::shared_ptr<pcgx_kdtree> h_;
 };
+
+// M3C2's finish (extension: no reference parity; include/pcgx.h, pcgx_m3c2_finish) on the cylinder statistics of two
+// epochs (KDTree::CylinderStats with the same cores, axes, radius and half length against each epoch's tree): per core
+// the signed distance along the axis, epoch 2 minus epoch 1, the level of detection at 95 % and whether |distance|
+// exceeds it.  Fewer than minCount points in either cylinder, or an unusable axis: NaN, NaN, 0.
+struct M3C2Result {
+  std::vector<double> distance, lod;
+  std::vector<uint8_t> significant;
+};
+inline M3C2Result M3C2Finish(const std::vector<Vec3> &axes, const KDTree::CylinderStatsResult &epoch1,
+                             const KDTree::CylinderStatsResult &epoch2, double registrationError = 0.0,
+                             int32_t minCount = 4) {
+  const size_t m = axes.size();
+  if (epoch1.counts.size() != m || epoch2.counts.size() != m || epoch1.sums.size() != 2 * m || epoch2.sums.size() != 2 * m)
+    throw Error(PCGX_E_INVALID, "one count and two sums per axis and epoch are required");
+  M3C2Result r;
+  r.distance.resize(m);
+  r.lod.resize(m);
+  r.significant.resize(m);
+  check(pcgx_m3c2_finish(m ? axes[0].data() : nullptr, epoch1.counts.data(), epoch1.sums.data(), epoch2.counts.data(),
+                         epoch2.sums.data(), (int64_t)m, registrationError, minCount, r.distance.data(), r.lod.data(),
+                         r.significant.data()));
+  return r;
+}
 
 // Matching of FPFH descriptors (extension: no reference parity; include/pcgx.h, "FPFH matching").  Rows as
 // KDTree::FPFH returns them.  ids: the nearest usable row of b per row of a (-1: none), distSq its float32 squared

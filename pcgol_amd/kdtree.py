@@ -1,7 +1,7 @@
 """pc/storage/kdtree mirror: KDTree on the GPU behind the storage.Search shape
 (pc/storage/search.go:13-17): Vec3At / Len / Nearest, plus batched NearestBatch, and extensions with no
 reference counterpart: surface normals (Normals), moving-least-squares smoothing (MLS), FPFH descriptors
-(FPFH, FPFHAt), keypoints (LocalMaxima, ISSKeypoints), cluster extraction (Clusters), density clusters (DBSCAN), plane segmentation (Planes), cylinder and sphere segmentation (Shapes), ground segmentation (Ground), boundary points (Boundary), ray queries (RayCast, RayPierce), per-group
+(FPFH, FPFHAt), keypoints (LocalMaxima, ISSKeypoints), cluster extraction (Clusters), density clusters (DBSCAN), plane segmentation (Planes), cylinder and sphere segmentation (Shapes), ground segmentation (Ground), boundary points (Boundary), ray queries (RayCast, RayPierce), cylinder statistics (CylinderStats), per-group
 geometry (GroupStats), k nearest neighbours (KNearest) and their covariances (Covariances)."""
 import collections
 import ctypes as C
@@ -558,6 +558,31 @@ class KDTree:
         L.check(L.lib().pcgx_kdtree_ray_pierce_dev(
             self._h, opt(d_origins), opt(d_directions), opt(d_s_min), opt(d_s_max), int(nr), float(radius),
             opt(d_counts), L.ptr(stream) if stream else None))
+
+    # -- extension (no reference parity): cylinder statistics, what M3C2 (pcgol_amd/change.py) is made of
+    def CylinderStats(self, cores, axes, radius, half_length):
+        """Per cylinder (core o, axis d not normalised, `radius`, `half_length` each way along the axis) over the tree's
+        live points -> (counts int32 (m,), sums float64 (m, 2)): the number of members and S1 = sum of a, S2 = sum of
+        a a, a = (p - o) . d in float64.  Unnormalised: the metric mean is S1 / n / |d|, the metric variance the sample
+        variance of a over |d|^2.  counts are exact; sums carry the bound of a summation order
+        (include/pcgx.h, pcgx_kdtree_cylinder_stats)."""
+        o = L.f32c(cores).reshape(-1, 3)
+        d = L.f32c(axes).reshape(-1, 3)
+        if len(o) != len(d):
+            raise ValueError("one axis per core is required")
+        counts = np.zeros(len(o), np.int32)
+        sums = np.zeros((len(o), 2), np.float64)
+        L.check(L.lib().pcgx_kdtree_cylinder_stats(self._h, L.ptr(o), L.ptr(d), len(o), float(radius), float(half_length),
+                                                   L.ptr(counts), L.ptr(sums)))
+        return counts, sums
+
+    def CylinderStatsDev(self, d_cores, d_axes, m, radius, half_length, d_counts, d_sums, stream=0):
+        """Device-resident CylinderStats: raw device addresses (e.g. torch .data_ptr()); d_cores, d_axes float32 [3 m],
+        d_counts int32 [m], d_sums float64 [2 m].  Enqueued on `stream`, returns without waiting, reads nothing back."""
+        opt = lambda a: L.ptr(int(a)) if a else None  # noqa: E731
+        L.check(L.lib().pcgx_kdtree_cylinder_stats_dev(
+            self._h, opt(d_cores), opt(d_axes), int(m), float(radius), float(half_length), opt(d_counts), opt(d_sums),
+            L.ptr(stream) if stream else None))
 
     # -- extension (no reference parity): clusters, the connected components of the radius graph
     def Clusters(self, radius, Normals=None, MinCos=0.0, Oriented=False, Curvature=None, MaxCurvature=0.0, MinSize=1,
